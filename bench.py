@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- SGAP pre-propagation SpMM throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S1_products] [--no-cpu-baseline] [--no-papers] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S1_products] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-papers] [--no-extras]]
 
 One "step" = one full k-hop propagation (prop_steps SpMM launches, k=3 for the headline config
 "SGC prop_steps=3 on ogbn-products") over a synthetic ogbn-products-shaped graph (Chung-Lu, N=2 449 029,
@@ -22,16 +23,23 @@ bit-checksums of the exchanged rows + sampled rows recomputed in fp64).  --layou
 build alternatives that REPLICATE A_hat (reported under config.plan.alternatives).  Total work is fixed -> "scaling": "strong".
 The helper modules live in benchlib/ (engine, rows = the contract layout, layouts = the alternatives, diagnostics, papers).
 
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, higher_is_better, dtype,
+ms_per_step (+ the per-step spread of the timed steps and the roofline fraction those steps imply).  --dump-outputs DIR
+writes what the last timed step computed (N = 1): a fixed, seeded sample of rows of every hop matrix and the float64 column
+sums of every whole hop, as DIR/<name>.npy.  Everything that takes work of its own after the timed region -- self-validation,
+diagnostics, the gather-ceiling probe, the CPU baseline, the secondary sections and the papers100M-shaped section -- runs
+only with --full:
+
 Prints ONE JSON line (rank 0) with the driver's contract keys plus
   roofline     : dominant kernel (spmm_kernel) algorithmic bytes per launch / measured launch time vs 8 TB/s HBM
-  cpu_baseline : the reference's own CPU kernel (oracle/_ref, else the C restatement) timed on this node's host
+  cpu_baseline : (--full) the reference's own CPU kernel (oracle/_ref, else the C restatement) timed on this node's host
                  cores on a bounded row sample of the same workload (N=1 only)
-  sections     : (S1 single-GPU runs only, unless --no-extras) the BASELINE configs the headline does not cover, each with workload,
+  sections     : (--full, S1 single-GPU runs only, unless --no-extras) the BASELINE configs the headline does not cover, each with workload,
                  ms, roofline, validated: S0_pubmed (config 1, compared with the CPU oracle and timed beside the reference CPU
                  path), S2_gamlp (config 3), S4_products (config 5's operator sweep + a torch-CPU aggregator baseline),
                  S1_community (the products degree law WITH communities: reorder=None vs "auto"), S4_papers_shard (configs 4/5 as
                  one rank of the 8-GPU job: NAFS + every MessageOp); benchlib/extras.py
-  papers100M   : (S1 runs only, unless --no-papers) the same measurement on an ogbn-papers100M-shaped graph
+  papers100M   : (--full, S1 runs only, unless --no-papers) the same measurement on an ogbn-papers100M-shaped graph
                  (111 M nodes, ~3.34 G non-zeros, d=128, k=3, rows generated per rank on device), row-sharded in
                  storage over the same N ranks: value, ms per hop, roofline fraction.  Bounded by a watchdog: if it
                  overruns, the line is printed without it.
@@ -44,7 +52,7 @@ import os
 import sys
 import time
 
-import numpy as np  # noqa: F401
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -71,7 +79,7 @@ def parse_args(argv=None):
                     help="column chunks of the feature block for the software-pipelined exchange (N>1); 1 = plain; default 3 "
                          "(32 + 32 + 36 columns at d = 100: what profiles/r03_scale_model.md predicts fastest below the link peak); "
                          "auto (opt-in) = 2, 3 and 4 are all built, validated and timed during setup and the fastest runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--strict", action="store_true", help="bit-exact reference summation order")
     ap.add_argument("--exchange", choices=("auto", "halo", "halo_a2a", "p2p", "allgather", "push"),
                     default=os.environ.get("SGL_BENCH_EXCHANGE", "halo"),
@@ -96,14 +104,14 @@ def parse_args(argv=None):
                     help="N>1: seconds after which a job that is stuck (a collective some rank never entered) is ended: rank 0 "
                          "prints a JSON line with value null, the phase it was in and exits non-zero instead of hanging")
     ap.add_argument("--no-papers", action="store_true",
-                    help="skip the ogbn-papers100M-shaped secondary measurement of an S1_products run")
+                    help="--full: skip the ogbn-papers100M-shaped secondary measurement of an S1_products run")
     ap.add_argument("--papers-budget", type=float, default=float(os.environ.get("SGL_BENCH_PAPERS_BUDGET", "150")),
                     help="watchdog (s) of the papers100M-shaped section: on overrun the JSON line is printed without it")
     ap.add_argument("--papers-k", type=int, default=3,
                     help="prop_steps of the papers100M-shaped section (3 by default; 10 = BASELINE config 5's hop count: raise --papers-budget)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary sections of an S1_products single-GPU run (BASELINE configs 1, 3, 5 and the per-rank share "
-                         "of 4/5: benchlib/extras.py); with --no-papers and --no-cpu-baseline this is the fast path")
+                    help="--full: skip the secondary sections of an S1_products single-GPU run (BASELINE configs 1, 3, 5 and the "
+                         "per-rank share of 4/5: benchlib/extras.py)")
     ap.add_argument("--extras-budget", type=float, default=float(os.environ.get("SGL_BENCH_EXTRAS_BUDGET", "240")),
                     help="seconds the secondary sections may take in total: a section that would start later is recorded as skipped")
     ap.add_argument("--detail-out", default=os.environ.get("SGL_BENCH_DETAIL_OUT"),
@@ -114,6 +122,13 @@ def parse_args(argv=None):
                     help="N = 1: process the rows of A_hat in a plan-time locality order (GraphOp(reorder=...): bit-identical results); "
                          "auto keeps the order only when it makes the graph measurably more local (workload S1_community: yes; S1_products: no)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what takes work of its own: self-validation, diagnostics, the gather-ceiling "
+                         "probe, the CPU baseline and (S1_products) the secondary and papers100M-shaped sections; a plain run only "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write what the last timed step computed to DIR/<name>.npy (a fixed, seeded sample of rows of every "
+                         "hop matrix in float32 + the float64 column sums of every whole hop; at most 64 MB in all)")
     ap.add_argument("--dup2", action="store_true",
                     help="edge weight 2.0 instead of 1.0: the reference's Ogbn loader symmetrises an already "
                          "bidirectional edge list and CSR construction sums the duplicates (dataset/ogbn.py:45-53)")
@@ -129,6 +144,24 @@ def _step_stats(step_ms):
     return {"n": int(a.size), "median": float(np.median(a)), "min": float(a[0]), "max": float(a[-1]),
             "p10": float(np.percentile(a, 10)), "p90": float(np.percentile(a, 90)),
             "spread_pct": float((a[-1] - a[0]) / np.median(a) * 100.0)}
+
+
+def dump_outputs(engine, out_dir, max_bytes=48 << 20, seed=1234):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy.  Per hop matrix: the rows of a fixed, seeded sample
+    (float32, the same rows for every hop; the sampled row ids go to sample_rows.npy) and the float64 column sums of the whole
+    matrix.  The sample is capped at max_bytes in all, so a full-size graph writes some 50 MB and a small one every row."""
+    hops = engine.step_outputs()
+    if not hops:
+        raise RuntimeError("--dump-outputs: the engine kept no outputs of the timed step")
+    os.makedirs(out_dir, exist_ok=True)
+    n_rows, d = next(iter(hops.values())).shape
+    m = int(min(n_rows, max(1, max_bytes // (4 * max(d, 1) * len(hops)))))
+    rows = np.arange(n_rows) if m == n_rows else np.sort(np.random.default_rng(seed).choice(n_rows, size=m, replace=False))
+    np.save(os.path.join(out_dir, "sample_rows.npy"), rows.astype(np.float64))
+    for name, y in hops.items():
+        idx = torch.from_numpy(rows).to(y.device)
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), y[idx].to(torch.float32).cpu().numpy())
+        np.save(os.path.join(out_dir, f"{name}_colsum.npy"), torch.sum(y, 0, dtype=torch.float64).cpu().numpy())
 
 
 def run(args, engine_cls=None, workloads=None, emit=print):
@@ -175,6 +208,10 @@ def run(args, engine_cls=None, workloads=None, emit=print):
         guard = threading.Timer(args.watchdog, stuck)
         guard.daemon = True
         guard.start()
+    full = getattr(args, "full", False)
+    dump_dir = getattr(args, "dump_outputs", None)
+    if dump_dir and (world > 1 or args.force_sharded):
+        raise SystemExit("--dump-outputs: only the single-GPU path (--gpus 1) writes its outputs")
     if world > 1 and not dist.is_initialized():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         _phase("init_process_group")
@@ -217,6 +254,9 @@ def run(args, engine_cls=None, workloads=None, emit=print):
     gpu_ms = t_elapsed_ms()
     timed_done[0] = True
     step_ms = marks.durations_ms(t_start.event if hasattr(t_start, "event") else None) if marks is not None else None
+    if dump_dir and rank == 0:
+        _phase("dump outputs")
+        dump_outputs(engine, dump_dir)
 
     # ---- the line exists from here on: whatever follows (self-validation, diagnostics, baselines, the papers100M-shaped section)
     # only ADDS to it, and the watchdog prints it as it stands instead of losing a measured value to a stuck collective ------------
@@ -266,10 +306,10 @@ def run(args, engine_cls=None, workloads=None, emit=print):
         }
         line_box[0] = out
 
-    # ---- self-validation of what the timed steps left behind (never part of `value`) -------------------------------------------
+    # ---- self-validation of what the timed steps left behind (never part of `value`; --full) --------------------------------------
     _phase("validation")
     if not sharded:
-        if hasattr(engine, "validate_single"):
+        if full and hasattr(engine, "validate_single"):
             try:
                 v = engine.validate_single()
             except Exception as e:  # noqa: BLE001
@@ -284,22 +324,23 @@ def run(args, engine_cls=None, workloads=None, emit=print):
                if info.get("layout", "rows") == "rows" else "last hop against the single-GPU chain on a gathered replica of A_hat (1e-5)")
         out["config"]["validation"] = {"when": "setup, before timing", "how": how, "ok": True}
 
-    _phase("diagnostics")
-    job.single_gpu_ms_replayed = (_replayed_profile(args.workload, 1) or {}).get("single_gpu_ms_per_step")
-    try:
-        diag = _diagnostics(job, halves, measured_step_ms=elapsed * 1e3 / args.steps) if job.budget_left() > -60 else \
-            {"skipped": "setup budget exhausted"}
-    except Exception as e:  # noqa: BLE001  (reporting only; the measured value is already in hand)
-        diag = {"failed": repr(e)}
-    if rank == 0:
-        out["config"]["diagnostics"] = diag
+    if full:
+        _phase("diagnostics")
+        job.single_gpu_ms_replayed = (_replayed_profile(args.workload, 1) or {}).get("single_gpu_ms_per_step")
+        try:
+            diag = _diagnostics(job, halves, measured_step_ms=elapsed * 1e3 / args.steps) if job.budget_left() > -60 else \
+                {"skipped": "setup budget exhausted"}
+        except Exception as e:  # noqa: BLE001  (reporting only; the measured value is already in hand)
+            diag = {"failed": repr(e)}
+        if rank == 0:
+            out["config"]["diagnostics"] = diag
 
-    if not sharded and rank == 0 and hasattr(engine, "gather_ceiling"):
+    if full and not sharded and rank == 0 and hasattr(engine, "gather_ceiling"):
         ceiling = engine.gather_ceiling(job.col, job.x0, d)
         out["roofline"]["gather_ceiling_Ggathers_per_s"] = ceiling
         out["roofline"]["frac_of_gather_ceiling"] = (nnz / world / hop_s / 1e9 / ceiling) if ceiling else None
 
-    if not sharded and not args.no_cpu_baseline and rank == 0:
+    if full and not sharded and not args.no_cpu_baseline and rank == 0:
         try:
             cpu = cpu_baseline(job.rowptr, job.col, job.val, job.x0, d)
         except Exception as e:  # noqa: BLE001  (baseline is reporting only; never blocks the GPU number)
@@ -323,7 +364,7 @@ def run(args, engine_cls=None, workloads=None, emit=print):
                 quiet.mute()                  # late library chatter (communicator teardown) goes to stderr too
 
     small = getattr(args, "extras_scale", "full") == "small" and args.workload == "S1_small"      # (tests: the same sections, in seconds)
-    can_extra = (args.workload == "S1_products" or small) and not args.force_sharded and hasattr(engine, "hashed_block")
+    can_extra = full and (args.workload == "S1_products" or small) and not args.force_sharded and hasattr(engine, "hashed_block")
     want_papers = can_extra and not small and not args.no_papers
     want_extras = can_extra and world == 1 and not getattr(args, "no_extras", False)
     if want_papers or want_extras:

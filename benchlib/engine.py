@@ -302,6 +302,14 @@ class GpuEngine:
         out["ok"] = bool(ok)
         return out
 
+    def step_outputs(self):
+        """what a step of the single-GPU path hands its caller, as it stands after the last step: {"hop<h>": rows x d} for every hop
+        matrix still held (all K, or the last two when the hop matrices alternate between two buffers)"""
+        st = getattr(self, "_single", None)
+        if st is None:
+            return {}
+        return {name: y[:, :st["d"]] for name, y in st["hops"].items()}
+
     def single_step(self, args, rowptr, col, val, x0, n, d, K):
         from sgl_amd import device as dev
         reorder_info = None
@@ -336,7 +344,8 @@ class GpuEngine:
             info["hops_retained"] = "last two only (K hop matrices of this size do not fit one GPU)"
         # what validate_single() looks at after the timed region: the operand and the result of the LAST launch of a step
         self._single = {"rowptr": rowptr, "col": col, "val": val, "d": d, "n": n, "strict": bool(args.strict),
-                        "x_prev": x_in if (K == 1 or n_out != n) else outs[K - 2], "y_last": outs[K - 1]}
+                        "x_prev": x_in if (K == 1 or n_out != n) else outs[K - 2], "y_last": outs[K - 1],
+                        "hops": {f"hop{h + 1}": outs[h] for h in range(K) if not pingpong or h >= K - 2}}
         if n_out != n:
             # a row block against the full replica (S3_papers_shard): K launches of the same hop
             def step():

@@ -18,6 +18,7 @@ Fixture families:
   g6 / g7 / g8   consumers of the SpMM (label propagation, C&S, NAFS task), ingest, hop-range quirks
   g10_label_reuse.npz BASELINE config 3: the label use / reuse loop around preprocess, through the reference's task code
   g9_config5.npz BASELINE config 5 at its own hop count: PPR / Laplacian k = 10, every MessageOp over H = 11 hops (d = 16, 128)
+  g13_ref_spmm.npz one SpMM through the reference's own compiled kernel (oracle/_ref/libmatmul.so) on three normalised graphs
 Dense inputs are regenerated from tests/golden/inputs.py (integer hash), not stored.
 """
 import importlib.util
@@ -863,6 +864,21 @@ def gen_g12():
     np.savez_compressed(os.path.join(HERE, "g12_fp64_truth.npz"), **out)
 
 
+def gen_g13():
+    """the reference's compiled FloatCSRMulDenseOMP (matmul.c, built in place into oracle/_ref by oracle/Makefile) on the same
+    normalised graphs and inputs as tests/test_oracle_golden.py::test_spmm_oracle_equals_reference_binary"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    import oracle
+    g = np.load(os.path.join(HERE, "graphs.npz"))
+    out = {}
+    for gname, d in (("pl2000", 37), ("dir40", 5), ("pl256", 128)):
+        n = len(g[gname + "|indptr"]) - 1
+        a = sp.csr_matrix((g[gname + "|data"], g[gname + "|indices"], g[gname + "|indptr"]), shape=(n, n))
+        ptr, col, val = oracle.sym_norm_csr(a.indptr, a.indices, a.data, n, 0.5)
+        out[f"{gname}|d{d}"] = oracle.reference_spmm(ptr, col, val, hash_matrix(n, d, seed=9))
+    np.savez_compressed(os.path.join(HERE, "g13_ref_spmm.npz"), **out)
+
+
 def main():
     if len(sys.argv) > 2 and sys.argv[1] == "--only":       # regenerate one family without touching the others
         globals()["gen_" + sys.argv[2]]()
@@ -883,6 +899,7 @@ def main():
     gen_g10()
     gen_g11()
     gen_g12()
+    gen_g13()
     tot = 0
     for fn in sorted(os.listdir(HERE)):
         if fn.endswith((".npz", ".json")):

@@ -113,10 +113,15 @@ def _make_engine():
 
             def step():
                 cur = x0.numpy()
-                for _ in range(K):
+                self.hops = {}
+                for h in range(K):
                     cur = oracle.oracle_spmm(rp, c, v, cur)
+                    self.hops[f"hop{h + 1}"] = torch.from_numpy(cur)
                 self.last = cur
             return step, {"n_items": 0}
+
+        def step_outputs(self):
+            return self.hops
 
         def piece_spmms(self, args, rowptr, col, val, n, my_bounds, rp_host):
             fns = []
@@ -172,7 +177,7 @@ def _worker(rank, world, port, out_dir, extra=(), a2a=False, break_halo=False):
     if a2a:
         _emulate_all_to_all_single(rank, world)
     args = bench.parse_args(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "T_tiny",
-                             "--pieces", "3", "--no-cpu-baseline", *extra])
+                             "--pieces", "3", "--full", "--no-cpu-baseline", *extra])
     lines = []
     engine_cls = _make_engine()
     engine_cls.halo_collective = bool(a2a)
@@ -384,7 +389,63 @@ def test_bench_single_rank_contract(tmp_path, monkeypatch):
     assert j["n_gpus"] == 1 and j["config"]["parallelism"] == "single GPU" and j["value"] > 0
     # default CLI values finish quickly and match the documented contract
     d = bench.parse_args([])
-    assert d.gpus == 1 and d.steps == 10 and d.warmup == 2 and d.workload == "S1_products"
+    assert d.gpus == 1 and d.steps == 10 and d.warmup == 2 and d.workload == "S1_products" and not d.full and d.dump_outputs is None
+
+
+def test_plain_run_times_only_and_dumps_its_outputs(tmp_path, monkeypatch):
+    """a run without --full: set up, warm up, time exactly --steps steps, print the line -- no self-validation, diagnostics or CPU
+    baseline.  --dump-outputs writes the last step's hop matrices (sampled rows + float64 column sums); the same arguments give
+    the same files"""
+    sys.path.insert(0, ROOT)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    import bench
+    import oracle
+    from benchlib import engine as bench_engine
+
+    def no_cpu_baseline(*a, **k):
+        raise AssertionError("a plain run must not time the CPU baseline")
+    monkeypatch.setattr(bench, "cpu_baseline", no_cpu_baseline)
+    monkeypatch.setattr(bench_engine, "cpu_baseline", no_cpu_baseline)
+    steps = []
+
+    class Counting(_make_engine()):
+        def single_step(self, args, *a):
+            step, info = super().single_step(args, *a)
+
+            def counted():
+                steps.append(1)
+                step()
+            return counted, info
+
+    outs = []
+    for i in range(2):
+        lines = []
+        args = bench.parse_args(["--steps", "3", "--warmup", "2", "--workload", "T_tiny", "--dump-outputs", str(tmp_path / f"d{i}")])
+        steps.clear()
+        bench.run(args, engine_cls=Counting, workloads=TINY, emit=lines.append)
+        assert len(lines) == 1 and len(steps) == 5
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["warmup"] == 2 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert j["unit"] == "edge\u00b7featdim/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert j["cpu_baseline"] is None and j["config"]["validated"] is None and j["config"]["diagnostics"] is None
+        assert "sections" not in j and "papers100M" not in j
+        outs.append({p.name: np.load(p) for p in sorted((tmp_path / f"d{i}").iterdir())})
+    a, b = outs
+    assert set(a) == {"sample_rows.npy"} | {f"hop{h}_{kind}.npy" for h in (1, 2, 3) for kind in ("rows", "colsum")}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    # what the dump holds is the timed path's result: the CPU engine's last hop, recomputed here from the same inputs
+    eng = Counting(0)
+    wargs = bench.parse_args(["--workload", "T_tiny"])
+    ptr, col, val, x = eng.build_workload(wargs, TINY["T_tiny"])
+    want = x.numpy()
+    for _ in range(TINY["T_tiny"]["k"]):
+        want = oracle.oracle_spmm(ptr.numpy(), col.numpy(), val.numpy(), want)
+    rows = a["sample_rows.npy"].astype(np.int64)
+    assert np.array_equal(a["hop3_rows.npy"], want[rows])
+    assert np.allclose(a["hop3_colsum.npy"], want.astype(np.float64).sum(0), rtol=1e-6, atol=1e-6)
 
 
 def test_cpu_baseline_leg_reports_reference_kernel_cores_and_scipy():
@@ -674,7 +735,8 @@ def test_a_crash_in_the_secondary_sections_cannot_cost_the_headline(monkeypatch)
     class WithSections(_make_engine()):
         hashed_block = staticmethod(lambda *a, **k: None)        # (what marks an engine that can run the secondary sections)
     workloads = {"S1_products": TINY["T_tiny"]}
-    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--workload", "S1_products", "--no-cpu-baseline", "--no-papers"])
+    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--workload", "S1_products", "--full", "--no-cpu-baseline",
+                             "--no-papers"])
 
     def run(fn):
         monkeypatch.setattr(extras, "run_extras", fn)

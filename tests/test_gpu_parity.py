@@ -2745,7 +2745,7 @@ def test_bench_single_gpu_line_validates_itself(cuda, monkeypatch):
         monkeypatch.delenv(k, raising=False)
     import bench
     tiny = {"T_small": dict(n=30_000, m=300_000, d_max=900, d=100, k=3)}
-    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--workload", "T_small", "--no-cpu-baseline"])
+    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--workload", "T_small", "--full", "--no-cpu-baseline"])
     lines = []
     bench.run(args, workloads=tiny, emit=lines.append)
     j = json.loads(lines[0])
@@ -2872,8 +2872,8 @@ def test_bench_secondary_sections_cover_every_baseline_config(cuda, monkeypatch,
     import bench
     from benchlib import extras
     detail = str(tmp_path / "detail.json")
-    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--workload", "S1_small", "--extras-scale", "small", "--no-cpu-baseline",
-                             "--detail-out", detail])
+    args = bench.parse_args(["--steps", "2", "--warmup", "1", "--workload", "S1_small", "--extras-scale", "small", "--full",
+                             "--no-cpu-baseline", "--detail-out", detail])
     lines = []
     bench.run(args, emit=lines.append)
     j = json.loads(lines[0])

@@ -446,7 +446,7 @@ def test_bench_cli_prints_exactly_one_json_line(cuda, launcher):
     if launcher == "torchrun":
         cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                 "--master-port", "29653"]
-    cmd += [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "S1_small"]
+    cmd += [os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "S1_small", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -485,8 +485,8 @@ def _bench_worker(rank, world, port, out_dir, extra=(), halo=True):
     if not halo:
         OneGpuGlooEngine.block_halo = None    # keep the need-aware exchange out of the candidates (the push test)
     tiny = {"T_small": dict(n=20_000, m=150_000, d_max=800, d=100, k=3)}
-    args = bench.parse_args(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "T_small", "--no-cpu-baseline",
-                             *extra])
+    args = bench.parse_args(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--workload", "T_small", "--full",
+                             "--no-cpu-baseline", *extra])
     lines = []
     bench.run(args, engine_cls=OneGpuGlooEngine, workloads=tiny, emit=lines.append)
     with open(_os.path.join(out_dir, f"rank{rank}.json"), "w") as f:
