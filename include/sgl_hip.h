@@ -156,6 +156,31 @@ enum { SGL_ACC_SUM = 0, SGL_ACC_WSUM = 1, SGL_ACC_MAX = 2, SGL_ACC_MIN = 3 };
 int sgl_spmm_acc_f32(sgl_csr_t *csr, const float *d_x, int64_t ldx, float *d_y, int64_t ldy, int64_t d, float *d_acc,
                      int64_t ldacc, float w, int mode, float divisor, void *stream);
 
+/* ---- bfloat16 hop storage (opt-in: GraphOp(hop_dtype="bfloat16")) ------------------------------------------- */
+/* The same products with X and Y stored as bfloat16 (raw 16-bit patterns, row-major, ldx / ldy in ELEMENTS); A's values stay
+ * fp32, on the same handle and plan (items, split rows + fix-up, XCD order, row map).  A gathered element is widened exactly,
+ * the sum is accumulated with fmaf in fp32 in the term order of sgl_spmm_f32 (strict order: one sequential chain per row; any two
+ * plans of one matrix agree bit for bit), split-row partial sums stay fp32, and the result is rounded ONCE, to nearest even
+ * (NaN stays NaN, +-inf stays +-inf, overflow rounds to inf, subnormals are kept).  16-byte lanes of 8 elements when rows are
+ * 16-byte aligned and d, ldx, ldy are multiples of 8; narrower lanes otherwise.  This is another precision class than the fp32
+ * path (about 3 significant digits per stored hop): never a default.  X and Y must not overlap. */
+int sgl_spmm_bf16(sgl_csr_t *csr, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int64_t d, void *stream);
+/* the hop loop, like sgl_spmm_chain_f32 (HOST arrays of n_hops device pointers / leading dimensions; A must be square) */
+int sgl_spmm_chain_bf16(sgl_csr_t *csr, int n_hops, const uint16_t *d_x0, int64_t ldx0, uint16_t *const *h_y,
+                        const int64_t *h_ldy, int64_t d, void *stream);
+/* Y = A . X in bf16 and the running aggregate of sgl_spmm_acc_f32 (same modes, same arithmetic) in fp32: the Y that enters ACC is
+ * the ROUNDED value widened again, so the aggregate equals, bit for bit, sgl_hop_reduce_f32 over the widened stored hops. */
+int sgl_spmm_acc_bf16(sgl_csr_t *csr, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int64_t d, float *d_acc,
+                      int64_t ldacc, float w, int mode, float divisor, void *stream);
+/* out[i, 0:d] = float(X[idx[i], 0:d]) (exact), out[i, d:d+pad_cols] = 0: the mini-batch row gather over a bf16 hop matrix; the
+ * result is fp32.  Negative indices count from the end.  An index outside [-n_rows, n_rows) fills its output row with NaN (the
+ * kernel never traps).  Nothing beyond column d of a source row is read. */
+int sgl_gather_rows_bf16_f32(const uint16_t *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t n_idx, float *d_out,
+                             int64_t ldo, int64_t d, int64_t pad_cols, void *stream);
+/* the same rows of up to 16 bf16 hop matrices in ONE launch (mirrors sgl_gather_hops_padded_f32; more -> SGL_ERR_UNSUPPORTED) */
+int sgl_gather_hops_bf16_f32(int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, int64_t n_rows, const int64_t *d_idx,
+                             int64_t n_idx, float *const *h_out, const int64_t *h_ldo, int64_t d, int64_t pad_cols, void *stream);
+
 /* ---- device memory -> pageable host memory --------------------------------------------------------------------------------- */
 /* Contiguous copy through a team of host threads and pinned staging buffers, huge pages requested for a freshly allocated
  * destination: the reference contract's CPU hop tensors (base_op.py:36 returns torch.FloatTensor(host array)) without a pinned

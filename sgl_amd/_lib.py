@@ -48,6 +48,14 @@ PROTOTYPES = {
                                         c_float, c_float, c_void_p]),
     "sgl_spmm_acc_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_int,
                                  c_float, c_void_p]),
+    "sgl_spmm_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p]),
+    "sgl_spmm_chain_bf16": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sgl_spmm_acc_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_float, c_int,
+                                  c_float, c_void_p]),
+    "sgl_gather_rows_bf16_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                         c_void_p]),
+    "sgl_gather_hops_bf16_f32": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                         c_void_p]),
     "sgl_allgather_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "sgl_exchange_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sgl_exchange_backend": (c_char_p, []),
@@ -222,8 +230,8 @@ def ptr(t):
 
 
 def hop_arrays(tensors):
-    """(host array of device pointers, host array of leading dimensions) for a list of 2-D row-major
-    float32 CUDA tensors (column stride 1)."""
+    """(host array of device pointers, host array of leading dimensions in elements) for a list of 2-D row-major
+    CUDA tensors (column stride 1)."""
     n = len(tensors)
     ptrs = (c_void_p * n)(*[t.data_ptr() for t in tensors])
     lds = (c_int64 * n)(*[t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)) for t in tensors])

@@ -51,6 +51,15 @@ delta_propagate  True (default) -> GraphOp.propagate remembers a 64-bit content 
               run in another lane layout (same result within 1e-5).  Only for feature matrices of at least delta_propagate_min_mb
               (default 64) and when the range is at most delta_propagate_max_fraction (default 0.7) of the columns; `op.delta_info`
               says what the last call did
+hop_dtype     "float32" (default) -> hop matrices are stored as float32: the 1e-5 contract.  "bfloat16" (SGL_AMD_HOP_DTYPE=bfloat16, or
+              GraphOp(hop_dtype="bfloat16")) -> OPT-IN reduced-precision storage: X is rounded once to bfloat16, every hop is
+              accumulated in fp32 from the stored bf16 rows of the previous one and rounded once, to nearest even, when it is stored
+              (sgl_spmm_chain_bf16); propagate() returns K + 1 bfloat16 device matrices of half the size, propagate_reduce() and the
+              mini-batch gathers hand float32 to everything downstream.  Another precision class (about 3 significant digits per
+              hop: max error / max|hop| of a few 1e-3), OUTSIDE the 1e-5 contract and never a default.  Single GPU,
+              device-resident hops only: with host_output or slab_hops it raises; delta_propagate, share_hops and the on-disk hop
+              cache are bypassed (they hold float32 entries only).  Read by GraphOp (LaplacianGraphOp / PprGraphOp) only: the
+              multi-GPU ShardedGraphOp has no bfloat16 form, takes no hop_dtype argument (a TypeError) and always stores float32
 hop_cache_dir None -> every propagate() computes; a directory -> the hop matrices of propagate() are kept on disk under a key of
               the CONTENT of adjacency + features + operator parameters and loaded on a hit (sgl_amd/hopcache.py; the reference
               recomputes them in every run of every task)
@@ -83,4 +92,5 @@ fuse_aggregate = "auto" if _fa == "auto" else _fa in ("1", "true", "yes", "on")
 slab_hops = _env_bool("SGL_AMD_SLAB_HOPS", False)
 reorder = os.environ.get("SGL_AMD_REORDER") or None
 hop_cache_dir = os.environ.get("SGL_AMD_HOP_CACHE") or None
+hop_dtype = (os.environ.get("SGL_AMD_HOP_DTYPE") or "float32").strip().lower()
 trace = _env_bool("SGL_AMD_TRACE", False)

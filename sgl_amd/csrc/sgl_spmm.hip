@@ -18,10 +18,7 @@
 //   * U independent gathers are kept in flight per lane (memory-level parallelism), x up to 8 waves per SIMD;
 //   * block -> item mapping is XCD-aware: each of the 8 XCDs walks its own contiguous range of rows, so rows that
 //     share neighbours (and the CSR stream) stay in one XCD's L2.
-#include "sgl_common.h"
-
-#include <atomic>
-#include <memory>
+#include "sgl_csr.h"
 
 namespace {
 
@@ -464,28 +461,6 @@ hipError_t launch_group(const SpmmArgs &a, int grid, hipStream_t st, bool nt, in
 }
 
 }  // namespace
-
-struct sgl_csr {
-    int64_t n_rows = 0, n_cols = 0, nnz = 0;
-    const int64_t *d_rowptr = nullptr;
-    const int32_t *d_col = nullptr;
-    const float *d_val = nullptr;
-    uint32_t flags = 0;
-    int64_t n_items = 0, n_pieces = 0, n_long = 0;
-    int32_t *d_items = nullptr;
-    sgl::Piece *d_pieces = nullptr;
-    int32_t *d_long_row = nullptr;
-    int32_t *d_long_first = nullptr;
-    float *d_partial = nullptr;
-    size_t partial_cap = 0;  // floats
-    std::vector<float *> retired;   // outgrown workspaces: a captured hipGraph may still replay into them (freed at destroy)
-    int device = 0;
-    const int32_t *d_rowmap = nullptr;   // caller's [n_rows] storage row -> output row (sgl_csr_set_rowmap), not owned
-    int32_t *d_long_out = nullptr;       // output rows of the split rows under the row map
-    // bumped by sgl_csr_set_values / sgl_csr_set_rowmap, set to ~0 by sgl_csr_destroy: a captured chain graph has the value and
-    // row-map pointers of its capture baked in and refuses to replay once they changed (shared: outlives the handle)
-    std::shared_ptr<std::atomic<uint64_t>> epoch = std::make_shared<std::atomic<uint64_t>>(0);
-};
 
 // permutation check of a row map on the device: every entry in range, no output row named twice
 __global__ __launch_bounds__(256) void rowmap_check_kernel(const int32_t *__restrict__ map, const int64_t n, unsigned *__restrict__ seen,

@@ -26,16 +26,40 @@ def round_up(x, m):
     return (x + m - 1) // m * m
 
 
-def expected_lines(ld, d):
-    """average number of 128-byte cache lines a d-float row touches when rows are laid out at a pitch of ld floats"""
+HOP_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
+
+
+def hop_torch_dtype(dtype):
+    """torch dtype of a hop storage dtype given as "float32" / "bfloat16" or as the torch dtype itself"""
+    if isinstance(dtype, str):
+        if dtype.strip().lower() not in HOP_DTYPES:
+            raise ValueError(f"hop_dtype must be one of {sorted(HOP_DTYPES)}, not {dtype!r}")
+        return HOP_DTYPES[dtype.strip().lower()]
+    if dtype not in HOP_DTYPES.values():
+        raise ValueError(f"hop matrices are stored as float32 or bfloat16, not {dtype}")
+    return dtype
+
+
+def _esize(dtype):
+    return 2 if dtype == torch.bfloat16 else 4
+
+
+def expected_lines(ld, d, elem_size=4):
+    """average number of 128-byte cache lines a row of d elements touches when rows are laid out at a pitch of ld elements of
+    `elem_size` bytes (4: float32, the default; 2: bfloat16)"""
     import math
-    step = math.gcd(ld * 4, 128)
+    step = math.gcd(ld * elem_size, 128)
     offs = range(0, 128, step)
-    return sum((o + d * 4 + 127) // 128 for o in offs) / len(offs)
+    return sum((o + d * elem_size + 127) // 128 for o in offs) / len(offs)
 
 
-def row_pitch(d, growth=1.25):
-    """Leading dimension (floats) for a hop matrix of width d.
+def row_pitch(d, growth=1.25, elem_size=4):
+    """Leading dimension (elements) for a hop matrix of width d; elem_size = 4 (float32 rows, the default) or 2 (bfloat16 rows).
+
+    2-byte rows follow the same reasoning with 16-byte vectors of 8 elements and lines of 64: the pitch is a multiple of 8, rounded
+    up to whole lines (or, for narrow rows, to a power of two) when that makes a gathered row touch measurably fewer lines within
+    the growth cap -- d = 100 -> 128 (always exactly 2 lines; 104 would average 2.5; both measured, profiles/bf16_hop_dtype.json),
+    d = 147 -> 152, d = 500 -> 512.  For float32 rows:
 
     Always a multiple of 4 floats (16-byte aligned rows -> 16-byte lane accesses).  The SpMM is bound by the number of
     128-byte lines it pulls through the fabric, so when rounding the pitch up to a whole number of lines
@@ -43,25 +67,29 @@ def row_pitch(d, growth=1.25):
     fewer lines, take it: d = 147 -> 160 floats (5 lines instead of 5.5 on average, +8 % memory), d = 500 -> 512,
     d = 12 -> 16; d = 100 stays 100 (always exactly 4 lines either way).  `growth` caps the memory overhead."""
     d = max(int(d), 1)
-    ld4, ld32 = round_up(d, 4), round_up(d, 32)
+    if elem_size not in (2, 4):
+        raise ValueError("row_pitch: elem_size must be 4 (float32) or 2 (bfloat16)")
+    vec, line = 16 // elem_size, 128 // elem_size            # elements per 16-byte lane access / per 128-byte line
+    ld4, ld32 = round_up(d, vec), round_up(d, line)
     cands = [(ld32, growth)]
-    if d < 32:
-        p2 = 4
+    if d < line:
+        p2 = vec
         while p2 < d:
             p2 *= 2
         cands.insert(0, (p2, max(growth, 1.34)))
-    best, best_lines = ld4, expected_lines(ld4, d)
+    best, best_lines = ld4, expected_lines(ld4, d, elem_size)
     for ld, cap in cands:
-        if ld != ld4 and ld <= cap * ld4 and expected_lines(ld, d) <= 0.97 * best_lines:
-            best, best_lines = ld, expected_lines(ld, d)
+        if ld != ld4 and ld <= cap * ld4 and expected_lines(ld, d, elem_size) <= 0.97 * best_lines:
+            best, best_lines = ld, expected_lines(ld, d, elem_size)
     return best
 
 
-def alloc_rows(n, d, device, zero_pad=True):
-    """[n, d] float32 view of a row-padded buffer (pitch = row_pitch(d)): every row starts 16-byte aligned, so the
-    kernels use 16-byte lane accesses for any d, and rows are placed to touch as few cache lines as possible."""
-    ld = row_pitch(d)
-    buf = torch.empty((n, ld), dtype=torch.float32, device=device)
+def alloc_rows(n, d, device, zero_pad=True, dtype=torch.float32):
+    """[n, d] view (float32 by default; torch.bfloat16 for bf16 hop storage) of a row-padded buffer (pitch = row_pitch(d) for the
+    element size): every row starts 16-byte aligned, so the kernels use 16-byte lane accesses for any d, and rows are placed to
+    touch as few cache lines as possible.  Pad columns are zero and stay zero under propagation."""
+    ld = row_pitch(d, elem_size=_esize(dtype))
+    buf = torch.empty((n, ld), dtype=dtype, device=device)
     if zero_pad and ld != d:
         buf[:, d:].zero_()
     return buf[:, :d] if ld != d else buf
@@ -74,13 +102,13 @@ def own_pad(t):
     if n <= 1:
         return 0
     ld = t.stride(0)
-    return ld - d if (ld > d and ld % 4 == 0 and t.stride(1) == 1 and t.data_ptr() % 16 == 0) else 0
+    return ld - d if (ld > d and (ld * t.element_size()) % 16 == 0 and t.stride(1) == 1 and t.data_ptr() % 16 == 0) else 0
 
 
 def padded_parent(t):
     """For a [n, d] view created by alloc_rows return the [n, ld] parent view (pad columns included)."""
     n, d = t.shape
-    ld = t.stride(0) if n > 1 else row_pitch(d)
+    ld = t.stride(0) if n > 1 else row_pitch(d, elem_size=t.element_size())
     if ld == d:
         return t
     return torch.as_strided(t, (n, ld), (ld, 1), t.storage_offset())
@@ -172,9 +200,10 @@ def _wrote(*tensors):
             torch.autograd.graph.increment_version(t)
 
 
-def _check_mat(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
-        raise TypeError(f"{name} must be a 2-D float32 CUDA tensor")
+def _check_mat(t, name, bf16=False):
+    """bf16=True: the entry point also has a bfloat16 form (bf16 hop storage)"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 and (t.dtype == torch.float32 or (bf16 and t.dtype == torch.bfloat16))):
+        raise TypeError(f"{name} must be a 2-D float32{' or bfloat16' if bf16 else ''} CUDA tensor")
     if t.shape[1] > 1 and t.stride(1) != 1:
         raise ValueError(f"{name} must be row-major (column stride 1)")
     if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
@@ -183,6 +212,34 @@ def _check_mat(t, name):
 
 def _ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def _same_hop_dtype(who, *tensors):
+    """the one dtype of x / out (float32 or bfloat16): the bf16 entry points read and write bf16, nothing converts on the way"""
+    dts = {t.dtype for t in tensors}
+    if len(dts) != 1:
+        raise TypeError(f"{who}: x and out must have the same dtype (float32 or bfloat16), got {sorted(str(d_) for d_ in dts)}")
+    return dts.pop()
+
+
+def _no_bf16(who, *tensors):
+    if any(torch.is_tensor(t) and t.dtype == torch.bfloat16 for t in tensors):
+        raise TypeError(f"{who} has no bfloat16 form (bf16 hop storage covers spmm, spmm_chain, spmm_acc and the row gathers)")
+
+
+def widen_hops(feats):
+    """bfloat16 hop matrices as float32 copies (exact), each in a padded buffer of its own; float32 ones are passed through.  The
+    full-matrix aggregators have no bf16 kernels: given bf16 hops they widen them hop by hop through torch with this and then run
+    the fp32 kernels -- a correctness fallback that costs 4 more bytes per element of every widened hop while the aggregate is
+    computed, not the fast path (that is the fused propagate_reduce, or the mini-batch gathers, which widen what they gather)."""
+    out = []
+    for f in feats:
+        if torch.is_tensor(f) and f.is_cuda and f.dtype == torch.bfloat16 and f.dim() == 2:
+            w = alloc_rows(f.shape[0], f.shape[1], f.device)
+            w.copy_(f)
+            f = w
+        out.append(f)
+    return out
 
 
 def default_long_row_nnz(nnz):
@@ -258,19 +315,27 @@ class DeviceCSR:
         return dict(zip(keys, list(a)))
 
     def spmm(self, x, out=None, accumulate=False):
-        """out = A @ x (+ out when accumulate).  x: [n_cols, d] float32 CUDA row-major; returns [n_rows, d]."""
-        _check_mat(x, "x")
+        """out = A @ x (+ out when accumulate).  x: [n_cols, d] float32 CUDA row-major; returns [n_rows, d].
+        A bfloat16 x (and out) runs sgl_spmm_bf16: bf16 in, fp32 accumulation, one rounding to bf16 out; no accumulate form."""
+        _check_mat(x, "x", bf16=True)
         if x.shape[0] != self.shape[1]:
             raise ValueError("Dimension mismatch detected for the adjacency and the feature matrix!")
         d = x.shape[1]
         if out is None:
             if accumulate:
                 raise ValueError("accumulate=True needs an `out` tensor")
-            out = alloc_rows(self.shape[0], d, x.device, zero_pad=True)
+            out = alloc_rows(self.shape[0], d, x.device, zero_pad=True, dtype=x.dtype)
         else:
-            _check_mat(out, "out")
+            _check_mat(out, "out", bf16=True)
             if out.shape != (self.shape[0], d):
                 raise ValueError("out has the wrong shape")
+        if _same_hop_dtype("spmm", x, out) == torch.bfloat16:
+            if accumulate:
+                raise ValueError("spmm: bfloat16 hops have no accumulate form")
+            with torch.cuda.device(self.device):
+                check(lib().sgl_spmm_bf16(self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, current_stream_ptr()), "sgl_spmm_bf16")
+            _wrote(out)
+            return out
         with torch.cuda.device(self.device):
             check(lib().sgl_spmm_f32(self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, int(bool(accumulate)),
                                      current_stream_ptr()), "sgl_spmm_f32")
@@ -284,15 +349,16 @@ class DeviceCSR:
         divisor != 1, or acc <- max / min(acc, out) (sgl_spmm_acc_f32): the running hop aggregate of Sum / Mean /
         SimpleWeighted / Max / Min"""
         mode = self.ACC_MODES[mode] if mode is not None else int(bool(weighted))
-        _check_mat(x, "x")
-        _check_mat(out, "out")
+        _check_mat(x, "x", bf16=True)
+        _check_mat(out, "out", bf16=True)
         _check_mat(acc, "acc")
         if x.shape[0] != self.shape[1] or out.shape != (self.shape[0], x.shape[1]) or acc.shape != out.shape:
             raise ValueError("Dimension mismatch detected for the adjacency and the feature matrix!")
+        fn, name = ((lib().sgl_spmm_acc_bf16, "sgl_spmm_acc_bf16") if _same_hop_dtype("spmm_acc", x, out) == torch.bfloat16
+                    else (lib().sgl_spmm_acc_f32, "sgl_spmm_acc_f32"))     # bf16 hops: acc stays float32 and takes the ROUNDED out
         with torch.cuda.device(self.device):
-            check(lib().sgl_spmm_acc_f32(self._h, ptr(x), _ld(x), ptr(out), _ld(out), x.shape[1], ptr(acc), _ld(acc),
-                                         float(w), mode, float(divisor), current_stream_ptr()),
-                  "sgl_spmm_acc_f32")
+            check(fn(self._h, ptr(x), _ld(x), ptr(out), _ld(out), x.shape[1], ptr(acc), _ld(acc),
+                                         float(w), mode, float(divisor), current_stream_ptr()), name)
         _wrote(out, acc)
         return out
 
@@ -300,6 +366,7 @@ class DeviceCSR:
         """A @ x stored into several [n_rows, d] matrices given as RAW device addresses (the first is normally local,
         the others peer-GPU replicas mapped through IPC) with leading dimension `ld`.  row_mask: optional uint8 CUDA
         tensor [n_rows]; bit q set = destination q+1 gets that row."""
+        _no_bf16("spmm_multi", x)
         _check_mat(x, "x")
         if x.shape[0] != self.shape[1]:
             raise ValueError("Dimension mismatch detected for the adjacency and the feature matrix!")
@@ -317,32 +384,35 @@ class DeviceCSR:
 
     def spmm_chain(self, x, n_hops, outs=None):
         """[A x, A^2 x, ..., A^k x] with ONE library call (the hop loop runs in C).  x: [n, d] row-major CUDA; the
-        results are row-padded buffers of the same width as x (or the caller's `outs`)."""
-        _check_mat(x, "x")
+        results are row-padded buffers of the same width and dtype as x (or the caller's `outs`).  bfloat16 x: sgl_spmm_chain_bf16,
+        every hop rounded once to bf16 and read back as such by the next."""
+        _check_mat(x, "x", bf16=True)
         if x.shape[0] != self.shape[1] or self.shape[0] != self.shape[1]:
             raise ValueError("Dimension mismatch detected for the adjacency and the feature matrix!")
         d = x.shape[1]
         if outs is None:
-            outs = [alloc_rows(self.shape[0], d, x.device, zero_pad=True) for _ in range(n_hops)]
+            outs = [alloc_rows(self.shape[0], d, x.device, zero_pad=True, dtype=x.dtype) for _ in range(n_hops)]
         else:
             if len(outs) != n_hops:
                 raise ValueError("need one output matrix per hop")
             for o in outs:
-                _check_mat(o, "outs[*]")
+                _check_mat(o, "outs[*]", bf16=True)
                 if o.shape != (self.shape[0], d):
                     raise ValueError("an output matrix has the wrong shape")
         if n_hops:
+            bf16 = _same_hop_dtype("spmm_chain", x, *outs) == torch.bfloat16
+            fn, name = (lib().sgl_spmm_chain_bf16, "sgl_spmm_chain_bf16") if bf16 else (lib().sgl_spmm_chain_f32, "sgl_spmm_chain_f32")
             ptrs = (c_void_p * n_hops)(*[o.data_ptr() for o in outs])
             lds = (c_int64 * n_hops)(*[_ld(o) for o in outs])
             with torch.cuda.device(self.device):
-                check(lib().sgl_spmm_chain_f32(self._h, n_hops, ptr(x), _ld(x), ptrs, lds, d, current_stream_ptr()),
-                      "sgl_spmm_chain_f32")
+                check(fn(self._h, n_hops, ptr(x), _ld(x), ptrs, lds, d, current_stream_ptr()), name)
             _wrote(*outs)
         return outs
 
     def capture_chain(self, x, outs):
         """hipGraph of `spmm_chain(x, len(outs), outs)`: returns a ChainGraph whose replay() re-runs the k hops on the
         current stream with one launch (x and outs are baked in: refill x in place between replays)."""
+        _no_bf16("capture_chain", x, *outs)
         _check_mat(x, "x")
         for o in outs:
             _check_mat(o, "outs[*]")
@@ -360,6 +430,7 @@ class DeviceCSR:
 
     def spmm_axpb_clamp(self, x, alpha, res=None, lo=float("-inf"), hi=float("inf"), out=None):
         """out = clamp(alpha * (A @ x) + res, lo, hi) in one kernel (the label-propagation step)"""
+        _no_bf16("spmm_axpb_clamp", x, res, out)
         _check_mat(x, "x")
         if x.shape[0] != self.shape[1]:
             raise ValueError("Dimension mismatch detected for the adjacency and the feature matrix!")
@@ -774,7 +845,9 @@ def _widened(feats, out):
 
 
 def hop_reduce(op, feats, weights=None):
-    """sum / mean / max / min / 1-D weighted sum over the hop list -> new [n, d] tensor"""
+    """sum / mean / max / min / 1-D weighted sum over the hop list -> new [n, d] float32 tensor.  bfloat16 hops are widened to
+    float32 copies first (widen_hops: a correctness fallback, 4 more bytes per element of every hop while it runs)."""
+    feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
     result = alloc_rows(n, d, feats[0].device)
@@ -792,6 +865,9 @@ def hop_reduce(op, feats, weights=None):
 
 
 def hop_concat(feats):
+    """the hops side by side -> [n, H d] float32.  bfloat16 hops are widened to float32 copies first (widen_hops: a correctness
+    fallback, 4 more bytes per element of every hop while it runs)."""
+    feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
     H = len(feats)
@@ -807,7 +883,9 @@ def hop_lincomb(feats, weights, outs=None):
     """out_k = sum_j weights[k, j] * feats[j]: a small dense matrix applied across the hop dimension, every input element read once
     for all outputs (sgl_hop_lincomb_f32; zero weights skipped, one fma chain in j order per output).  feats: up to 16 [n, d] hop
     matrices; weights: [n_out, len(feats)] (host or device); outs: optional list of n_out [n, d] matrices (not aliasing the inputs).
-    Returns the list of outputs."""
+    Returns the list of outputs.  bfloat16 inputs are widened to float32 copies first (widen_hops: 4 more bytes per element of every
+    hop while it runs); the outputs are float32."""
+    feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
     w = torch.as_tensor(weights, dtype=torch.float32).to(feats[0].device).contiguous()
@@ -882,8 +960,9 @@ class _ReduceGrad(torch.autograd.Function):
 
 
 def hop_reduce_grad(op, feats, divisor=None):
-    """hop_reduce for hop matrices that carry gradients (op: SGL_REDUCE_SUM / MEAN / MAX / MIN)"""
-    return _ReduceGrad.apply(op, divisor, *feats)
+    """hop_reduce for hop matrices that carry gradients (op: SGL_REDUCE_SUM / MEAN / MAX / MIN); bfloat16 hops are widened first
+    (widen_hops)"""
+    return _ReduceGrad.apply(op, divisor, *widen_hops(feats))
 
 
 class _ConcatGrad(torch.autograd.Function):
@@ -903,7 +982,7 @@ class _ConcatGrad(torch.autograd.Function):
 
 
 def hop_concat_grad(feats):
-    return _ConcatGrad.apply(*feats)
+    return _ConcatGrad.apply(*widen_hops(feats))
 
 
 class _WSum2D(torch.autograd.Function):
@@ -1304,7 +1383,9 @@ def hop_scores2(feats, v, u, mask, h0, h1):
 
 
 def nafs_aggregate(feats, return_weights=False):
-    """OverSmoothDistanceWeightedOp._combine (over_smooth_distance_op.py:11-33) on device"""
+    """OverSmoothDistanceWeightedOp._combine (over_smooth_distance_op.py:11-33) on device.  bfloat16 hops are widened to float32
+    copies first (widen_hops: a correctness fallback, 4 more bytes per element of every hop while it runs)."""
+    feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
     H = len(feats)
@@ -1327,7 +1408,9 @@ def nafs_prefix(feats, emit_hops, outs=None, combine=NAFS_STORE, divisor=1.0, ou
     ensemble: NAFS_ADD, NAFS_ADD_DIV with `divisor`, NAFS_MAX), allocated when None; any 16-byte aligned [n, d] views whose pitch
     is a multiple of 4 floats -- e.g. column slices of one wide slab (the 'concat' ensemble).  outs_padded=True declares that the
     tail of every output's pitch is its own padding (matrices from alloc_rows): it is then written as zeros so that every line of a
-    row is written whole.  Returns the list of outputs."""
+    row is written whole.  Returns the list of outputs.  bfloat16 hops are widened to float32 copies first (widen_hops: 4 more
+    bytes per element of every hop while it runs)."""
+    feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
     emit_hops = [int(h) for h in emit_hops]
@@ -1423,7 +1506,14 @@ def gather_hops(feats, idx, one_launch=None):
     feats = list(feats)
     if not feats:
         return []
-    _check_mat(feats[0], "feat_list[0]")
+    _check_mat(feats[0], "feat_list[0]", bf16=True)
+    if feats[0].dtype == torch.bfloat16:
+        # bf16 hop storage: the gathered rows come back as float32 (widened exactly), one launch for all hops
+        for i, f in enumerate(feats):
+            _check_mat(f, f"feat_list[{i}]", bf16=True)
+            if f.dtype != torch.bfloat16 or f.shape != feats[0].shape or f.device != feats[0].device:
+                raise ValueError("gather_hops: bfloat16 hop matrices must all be bfloat16, of one shape, on one device")
+        return _gather_bf16(feats, _device_index(idx, feats[0].shape[0], feats[0].device))
     same_rows = all(torch.is_tensor(f) and f.is_cuda and f.dim() == 2 and f.shape[0] == feats[0].shape[0] and f.device == feats[0].device
                     for f in feats)
     if same_rows:
@@ -1461,12 +1551,50 @@ def _gather_hops_one_launch(feats, idx):
     return outs
 
 
+def _gather_bf16(feats, idx, outs=None):
+    """[x[idx] as float32 for x in feats] for bfloat16 matrices of one shape (sgl_gather_hops_bf16_f32: up to 16 hops per launch).
+    Our own outputs are padded float32 buffers whose pad columns are written as zeros by the kernel."""
+    n_rows, d = feats[0].shape
+    m = int(idx.numel())
+    pad = 0
+    if outs is None:
+        outs = [alloc_rows(m, d, feats[0].device, zero_pad=m <= 1) for _ in feats]
+        ldo = outs[0].stride(0)
+        if m > 1 and ldo > d:
+            pad = (ldo - d) if ldo - d < 32 else (round_up(d, 4) - d)
+            if pad != ldo - d:
+                for o in outs:
+                    padded_parent(o)[:, d + pad:].zero_()
+    if m == 0 or d == 0:
+        return outs
+    with torch.cuda.device(feats[0].device):
+        for a in range(0, len(feats), 16):
+            fs, os_ = feats[a:a + 16], outs[a:a + 16]
+            ptrs, lds = _lib.hop_arrays(fs)
+            optrs, olds = _lib.hop_arrays(os_)
+            if len(fs) == 1:
+                check(lib().sgl_gather_rows_bf16_f32(ptr(fs[0]), _ld(fs[0]), n_rows, ptr(idx), m, ptr(os_[0]), _ld(os_[0]), d, pad,
+                                                     current_stream_ptr()), "sgl_gather_rows_bf16_f32")
+            else:
+                check(lib().sgl_gather_hops_bf16_f32(len(fs), ptrs, lds, n_rows, ptr(idx), m, optrs, olds, d, pad, current_stream_ptr()),
+                      "sgl_gather_hops_bf16_f32")
+    _wrote(*outs)
+    return outs
+
+
 def gather_rows(x, idx, out=None):
     """x[idx] on device (BaseSGAPModel.forward's per-step row gather, models/base_model.py:58,60).  `out`: optional
-    preallocated [len(idx), d] destination (the pack step of the need-aware exchange re-uses one send buffer per hop)."""
-    _check_mat(x, "x")
+    preallocated [len(idx), d] destination (the pack step of the need-aware exchange re-uses one send buffer per hop).
+    A bfloat16 x (bf16 hop storage) is gathered into float32 (sgl_gather_rows_bf16_f32): `out`, given or not, is float32."""
+    _check_mat(x, "x", bf16=True)
     n_rows, d = x.shape
     idx = _device_index(idx, n_rows, x.device)
+    if x.dtype == torch.bfloat16:
+        if out is not None:
+            _check_mat(out, "out")
+            if out.shape != (idx.numel(), d):
+                raise ValueError("gather_rows: `out` must be [len(idx), d]")
+        return _gather_bf16([x], idx, None if out is None else [out])[0]
     own_out = out is None
     if out is None:
         # (the pad columns of our own output are written by the kernel below whenever the vector path applies: no separate zero fill)

@@ -25,8 +25,8 @@ def take_rows(feat, idx, device):
     kernels and the head's GEMM take a row pitch), and a copy would move every hop matrix once more (2 x 1.6 GB per hop at the
     products shape)."""
     if torch.is_tensor(feat) and feat.is_cuda:
-        if isinstance(idx, range) and idx.step == 1 and 0 <= idx.start <= idx.stop <= feat.shape[0]:
-            return feat[idx.start:idx.stop].to(device)
+        if isinstance(idx, range) and idx.step == 1 and 0 <= idx.start <= idx.stop <= feat.shape[0] and feat.dtype != torch.bfloat16:
+            return feat[idx.start:idx.stop].to(device)          # (bfloat16 hop storage: always gathered, the gather widens to float32)
         return dev.gather_rows(feat, idx).to(device)
     if isinstance(idx, range):
         idx = list(idx)
@@ -37,9 +37,11 @@ def take_hop_rows(feats, idx, device):
     """[take_rows(feat, idx, device) for feat in feats] (reference: models/base_model.py:58-60) -- for device-resident hop matrices
     the indices are validated and uploaded once for all of them (device.gather_hops)"""
     feats = list(feats)
-    same = len(feats) > 1 and all(torch.is_tensor(f) and f.is_cuda and f.dtype == torch.float32 and f.dim() == 2
-                                  and f.shape[0] == feats[0].shape[0] and f.device == feats[0].device for f in feats)
-    contiguous_range = isinstance(idx, range) and idx.step == 1
+    same = len(feats) > 1 and all(torch.is_tensor(f) and f.is_cuda and f.dtype in (torch.float32, torch.bfloat16) and f.dim() == 2
+                                  and f.dtype == feats[0].dtype and f.shape[0] == feats[0].shape[0] and f.device == feats[0].device
+                                  for f in feats)
+    bf16 = same and feats[0].dtype == torch.bfloat16    # bfloat16 hop storage: the one-launch gather widens, mini-batches are float32
+    contiguous_range = isinstance(idx, range) and idx.step == 1 and not bf16
     if not same or contiguous_range:
         return [take_rows(feat, idx, device) for feat in feats]
     return [t.to(device) for t in dev.gather_hops(feats, idx)]
@@ -145,7 +147,9 @@ class BaseSGAPModel(nn.Module):
                 and hasattr(self._pre_msg_op, "fused_spec") and not gop._opt("host_output")):
             # last / sum / mean / max / min / simple_weighted: accumulated in the SpMM epilogue, the K+1 hop matrices never coexist
             spec = self._pre_msg_op.fused_spec(gop._prop_steps + 1)
-            if spec is not None and (spec["kind"] == "last" or config.fuse_aggregate is True or self._hops_are_heavy(feature)):
+            # (bfloat16 hop storage always folds: the separate pass would first widen every hop matrix to float32, device.widen_hops)
+            bf16 = hasattr(gop, "_bf16_hops") and gop._bf16_hops()
+            if spec is not None and (spec["kind"] == "last" or config.fuse_aggregate is True or bf16 or self._hops_are_heavy(feature)):
                 with torch.no_grad():
                     fused = gop.propagate_reduce(adj, feature, **spec)
                 if fused is not None:

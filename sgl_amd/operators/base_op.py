@@ -132,8 +132,9 @@ def _lib_reduce(kind):
 
 class GraphOp:
     def __init__(self, prop_steps, device=None, host_output=None, strict_types=None, strict_order=None, cache_adj=None,
-                 slab_hops=None, reorder=None, hop_cache_dir=None):
+                 slab_hops=None, reorder=None, hop_cache_dir=None, hop_dtype=None):
         self._prop_steps = prop_steps
+        self._hop_dtype = hop_dtype
         self._reorder = reorder
         self._adj = None
         self._device = device
@@ -160,6 +161,18 @@ class GraphOp:
     def _opt(self, name):
         v = getattr(self, "_" + name)
         return getattr(config, name) if v is None else v
+
+    def _bf16_hops(self):
+        """is the (opt-in) bfloat16 hop storage asked for?  Raises for anything but "float32" / "bfloat16", and for the options it
+        does not combine with."""
+        if dev.hop_torch_dtype(self._opt("hop_dtype")) != torch.bfloat16:
+            return False
+        for other in ("host_output", "slab_hops"):
+            if self._opt(other):
+                raise ValueError(f"hop_dtype='bfloat16' cannot be combined with {other}=True: bfloat16 hops are device-resident "
+                                 f"matrices of their own (host_output returns the reference's float32 CPU tensors, slab_hops lays "
+                                 f"float32 hops out side by side)")
+        return True
 
     def _construct_adj(self, adj):
         raise NotImplementedError
@@ -267,7 +280,10 @@ class GraphOp:
             w = [float(v) for v in torch.as_tensor(weights, dtype=torch.float32).reshape(-1)]
             if len(w) != e - s:
                 return None
+        bf16 = self._bf16_hops()
         self._checked(adj, feature)
+        if bf16:
+            return self._propagate_reduce_bf16(feature, kind, s, e, w if kind == "wsum" else None, divisor)
         cur = self._device_features(feature)
         d = cur.shape[1]
         src = dev.padded_parent(cur) if cur.stride(0) % 4 == 0 else cur
@@ -299,6 +315,66 @@ class GraphOp:
             acc = acc / torch.tensor(float(divisor if divisor is not None else 1), device=acc.device)   # true division
         return acc[:, :d] if acc.shape[1] != d else acc
 
+    def _propagate_reduce_bf16(self, feature, kind, s, e, w, divisor):
+        """propagate_reduce over bfloat16 hops (sgl_spmm_acc_bf16): the hops are stored (two buffers alive) and read back as bf16,
+        the running aggregate is float32, starts from the widened STORED hop s and takes every later hop as stored -- bit for bit
+        hop_reduce over the widened hops propagate() would return.  `last` returns the bfloat16 hop K itself."""
+        x0 = self._device_features_bf16(feature)
+        d = x0.shape[1]
+        x = dev.padded_parent(x0)
+        n, W = self._adj.shape[0], x.shape[1]
+        bufs = [dev.padded_parent(dev.alloc_rows(n, d, x.device, dtype=torch.bfloat16)) for _ in range(min(2, e - 1))]
+
+        def begin(x_s):           # the aggregate's first term, with the aggregator kernel's own arithmetic, over the whole pitch
+            wide = torch.empty((n, W), dtype=torch.float32, device=x_s.device)
+            wide.copy_(x_s)
+            if kind == "wsum":
+                return dev.padded_parent(dev.hop_reduce(_lib_reduce("wsum"), [wide], torch.tensor(w[:1])))
+            return dev.padded_parent(dev.hop_reduce(_lib_reduce(kind if kind in ("max", "min") else "sum"), [wide]))
+
+        acc = begin(x) if (s == 0 and kind != "last") else None
+        for h in range(1, e):
+            y = bufs[(h - 1) % len(bufs)]
+            if acc is not None:
+                last = h == e - 1
+                div = float(divisor if divisor is not None else (e - s)) if (kind == "mean" and last) else 1.0
+                self._adj.spmm_acc(x, y, acc[:, :W] if acc.shape[1] != W else acc, w=w[h - s] if kind == "wsum" else 1.0, divisor=div,
+                                   mode=kind if kind in ("wsum", "max", "min") else "sum")
+            else:
+                self._adj.spmm(x, out=y)
+                if h == s and kind != "last":
+                    acc = begin(y)
+            x = y
+        if kind == "last":
+            return x[:, :d] if x.shape[1] != d else x
+        if kind == "mean" and e - s == 1:      # a single hop in range: the division has no SpMM to ride on
+            acc = acc / torch.tensor(float(divisor if divisor is not None else 1), device=acc.device)   # true division
+        return acc[:, :d] if acc.shape[1] != d else acc
+
+    def _device_features_bf16(self, feature):
+        """the input features rounded ONCE to bfloat16 (torch's round-to-nearest-even) in a padded bf16 device buffer of our own:
+        never an alias of the caller's tensor"""
+        device = self._adj.device
+        t = torch.from_numpy(np.ascontiguousarray(feature, dtype=np.float32)) if isinstance(feature, np.ndarray) else feature.detach()
+        t = t.to(device=device, dtype=torch.float32)
+        x0 = dev.alloc_rows(t.shape[0], t.shape[1], device, dtype=torch.bfloat16)
+        x0.copy_(t.to(torch.bfloat16))
+        return x0
+
+    def _propagate_bf16(self, adj, feature):
+        """[bf16(X), hop 1, ..., hop K] as bfloat16 device matrices (config.hop_dtype): the chain runs over the whole row pitch
+        (pad columns are zeros and stay zeros), every hop read back as stored"""
+        self._checked(adj, feature)
+        self._phase_done("adjacency")
+        x0 = self._device_features_bf16(feature)
+        self._phase_done("features")
+        n, d = x0.shape
+        outs = [dev.alloc_rows(n, d, x0.device, dtype=torch.bfloat16) for _ in range(self._prop_steps)]
+        self._adj.spmm_chain(dev.padded_parent(x0), self._prop_steps, outs=[dev.padded_parent(o) for o in outs])
+        dev._wrote(*outs)
+        self._phase_done("hops")
+        return [x0] + outs
+
     def propagate(self, adj, feature):
         if not config.trace:
             return self._propagate_or_cache(adj, feature)
@@ -329,6 +405,11 @@ class GraphOp:
             self._mark(name)
 
     def _propagate_or_cache(self, adj, feature):
+        if self._bf16_hops():
+            # neither the process-wide hop store, nor the on-disk cache, nor the column-delta memory is consulted or fed: they hold
+            # float32 entries only, and a bfloat16 request must never be served one (nor the reverse)
+            self._delta = None
+            return self._propagate_bf16(adj, feature)
         cache_dir = self._opt("hop_cache_dir")
         if config.share_hops and not cache_dir and not self._opt("host_output") and not self._opt("slab_hops"):
             # process-wide store of device-resident hop lists (hopcache.SharedHops): the reference's exceptions first, then the lookup.
@@ -548,5 +629,9 @@ class MessageOp(nn.Module):
         for feat in feat_list:
             if not isinstance(feat, Tensor):
                 raise TypeError("The feature matrices must be tensors!")
+        if self._aggr_type != "last" and any(f.dtype == torch.bfloat16 and f.is_cuda for f in feat_list):
+            # bfloat16 hop storage: no aggregator computes in bf16.  Whole hop matrices are widened (exact) before the fp32 kernels --
+            # the correctness fallback of device.widen_hops; the fast paths never get here (propagate_reduce, mini-batch gathers)
+            feat_list = dev.widen_hops(feat_list)
 
         return self._combine(feat_list)

@@ -60,6 +60,8 @@ class PprGraphOp(GraphOp):
     def propagate_from_laplacian(self, lap_hops):
         """this operator's hop matrices from those of LaplacianGraphOp(prop_steps, r) over the same graph and features
         (ppr_hops_from_laplacian): no propagation, one mixing pass.  Refused under strict_order (not bit-identical to the chain)."""
+        if self._bf16_hops():
+            raise ValueError("propagate_from_laplacian mixes float32 hop matrices: not with hop_dtype='bfloat16'")
         if bool(self._opt("strict_order")):
             raise ValueError("propagate_from_laplacian is not bit-identical to the propagation chain: not with strict_order")
         if len(lap_hops) != self._prop_steps + 1:
