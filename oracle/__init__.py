@@ -1,11 +1,13 @@
 """CPU oracle for the SGAP pre-propagation path -- TEST INFRASTRUCTURE ONLY.
 
 Nothing under ``sgl_amd/`` imports this package.  Allowed users: ``tests/``,
-``__graft_entry__.smoke()`` and the ``cpu_baseline`` leg of ``bench.py``.
+``__graft_entry__.smoke()``, the ``cpu_baseline`` leg of ``bench.py`` and the value
+checks that measurement tools under ``tools/`` make before they time a kernel.
 
 Contents
 --------
-spmm_ref.c / liboracle_spmm.so   C restatement of FloatCSRMulDenseOMP (matmul.c:23-40)
+spmm_ref.c / liboracle_spmm.so   C restatement of FloatCSRMulDenseOMP (matmul.c:23-40), and the exact model
+                                 of the HIP kernels' default summation order (oracle_spmm_slots)
 _ref/libmatmul.so                the reference's own matmul.c compiled in place (git-ignored)
 ref_ops.py                       numpy restatement of the normalisation (operators/utils.py:76-88),
                                  GraphOp.propagate (base_op.py:19-36) and every MessageOp._combine

@@ -14,7 +14,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 __all__ = [
-    "load_oracle_lib", "load_reference_lib", "oracle_spmm", "oracle_spmm_scalar", "reference_spmm",
+    "load_oracle_lib", "load_reference_lib", "oracle_spmm", "oracle_spmm_scalar", "oracle_spmm_slots",
+    "oracle_spmm_slots_bf16", "reference_spmm",
     "canonical_csr", "sym_norm_csr", "laplacian_adj", "ppr_adj", "propagate",
     "agg_last", "agg_concat", "agg_mean", "agg_sum", "agg_max", "agg_min",
     "alpha_weights", "one_dim_weighted_add", "two_dim_weighted_add",
@@ -49,6 +50,10 @@ def load_oracle_lib():
         lib.sgl_oracle_spmm_f32_scalar.restype = None
         lib.sgl_oracle_FloatCSRMulDenseOMP.argtypes = [_f32p, _f32p, _i32p, _i32p, _f32p, ctypes.c_int, ctypes.c_int]
         lib.sgl_oracle_FloatCSRMulDenseOMP.restype = None
+        if hasattr(lib, "sgl_oracle_spmm_slots_f32_ld"):      # absent from a library built before the symbol existed
+            vp, i64 = ctypes.c_void_p, ctypes.c_int64
+            lib.sgl_oracle_spmm_slots_f32_ld.argtypes = [vp, i64, _f32p, _i32p, _i64p, vp, i64, vp, i64, i64, ctypes.c_int32, i64]
+            lib.sgl_oracle_spmm_slots_f32_ld.restype = ctypes.c_int
         _oracle_lib = lib
     return _oracle_lib
 
@@ -96,6 +101,60 @@ def oracle_spmm_scalar(indptr, indices, data, x):
         np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(indptr, dtype=np.int64),
         x.reshape(-1), n_rows, d)
     return y
+
+
+def _row_major_f32(a):
+    """(array to keep alive, leading dimension in elements) of a 2-D float32 matrix; a row-major view with a row pitch (columns
+    contiguous) is passed as it is, anything else is copied"""
+    a = np.asarray(a)
+    if not (a.dtype == np.float32 and a.ndim == 2 and a.shape[1] > 0 and a.strides[1] == 4 and a.strides[0] % 4 == 0
+            and a.strides[0] >= 4 * a.shape[1]):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        return a, max(a.shape[1], 1)
+    return a, a.strides[0] // 4
+
+
+def oracle_spmm_slots(indptr, indices, data, x, R, long_row_nnz, rows=None):
+    """Y = A @ X in the DEFAULT ("fast") summation order of the HIP SpMM kernels, bit for bit (spmm_ref.c:
+    sgl_oracle_spmm_slots_f32_ld; the order is the one documented in csrc/sgl_spmm.hip run_rows and sgl_spmm_bf16.hip).
+
+    A row of more than `long_row_nnz` non-zeros is cut into pieces of `long_row_nnz` from its start (<= 0: never).  Inside a
+    piece non-zero t belongs to slot t mod R; every slot is an fmaf chain from +0.f in index order; the R slots are added by
+    the pairwise tree; a cut row is 0.f + p0 + p1 + ...  R = 64 / GROUP of the kernel that ran: 1, 2, 4 or 8.
+    `rows`: evaluate only these rows (against the full `x`); the result then has one row per entry."""
+    lib = load_oracle_lib()
+    if not hasattr(lib, "sgl_oracle_spmm_slots_f32_ld"):
+        raise RuntimeError("oracle/liboracle_spmm.so was built before sgl_oracle_spmm_slots_f32_ld existed: "
+                           "rebuild it with `make -C oracle` (or __graft_entry__.build())")
+    if int(R) not in (1, 2, 4, 8):
+        raise ValueError("R must be 1, 2, 4 or 8")
+    x, ldx = _row_major_f32(x)
+    d = x.shape[1]
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    if rows is None:
+        rows_arr, n_out, rows_p = None, len(indptr) - 1, None
+    else:
+        rows_arr = np.ascontiguousarray(rows, dtype=np.int64)
+        if rows_arr.size and (rows_arr.min() < 0 or rows_arr.max() >= len(indptr) - 1):
+            raise IndexError("rows outside the matrix")
+        n_out, rows_p = rows_arr.size, rows_arr.ctypes.data_as(ctypes.c_void_p)
+    y = np.zeros((n_out, d), dtype=np.float32)
+    rc = lib.sgl_oracle_spmm_slots_f32_ld(
+        y.ctypes.data_as(ctypes.c_void_p), max(d, 1), np.ascontiguousarray(data, dtype=np.float32),
+        np.ascontiguousarray(indices, dtype=np.int32), indptr, x.ctypes.data_as(ctypes.c_void_p), ldx, rows_p, n_out, d,
+        int(R), int(long_row_nnz))
+    if rc != 0:
+        raise RuntimeError(f"sgl_oracle_spmm_slots_f32_ld failed ({rc})")
+    return y
+
+
+def oracle_spmm_slots_bf16(indptr, indices, data, x_bf16, R, long_row_nnz, rows=None):
+    """the bfloat16 kernels' result: rne(model(widen(x))).  x_bf16 is a CPU torch.bfloat16 matrix; widening is exact, the
+    fp32 model runs as above, and the finished sum is rounded once by torch on the CPU (.to(bfloat16): round to nearest
+    even, the one definition of rounding of the bf16 tests).  Returns a CPU torch.bfloat16 tensor."""
+    import torch
+    y = oracle_spmm_slots(indptr, indices, data, x_bf16.float().numpy(), R, long_row_nnz, rows=rows)
+    return torch.from_numpy(y).to(torch.bfloat16)
 
 
 def reference_spmm(indptr, indices, data, x, n_rows=None):

@@ -307,9 +307,10 @@ def test_sgl_amd_never_imports_the_oracle():
 
 def test_only_the_checkers_use_the_oracle():
     """outside tests/: __graft_entry__.smoke() and the bench's cpu_baseline legs (benchlib/engine.py: the headline's; benchlib/cpu_legs.py:
-    the secondary sections') -- nothing under tools/, examples/, the rest of benchlib/ or bench.py itself imports the oracle or loads
-    its library"""
-    allowed = {os.path.join(ROOT, "benchlib", "engine.py"), os.path.join(ROOT, "benchlib", "cpu_legs.py"), os.path.join(ROOT, "__graft_entry__.py")}
+    the secondary sections'), and the value check tools/bench_hop_dtype.py makes before it times a kernel -- nothing else under tools/,
+    examples/, the rest of benchlib/ or bench.py itself imports the oracle or loads its library"""
+    allowed = {os.path.join(ROOT, "benchlib", "engine.py"), os.path.join(ROOT, "benchlib", "cpu_legs.py"), os.path.join(ROOT, "__graft_entry__.py"),
+               os.path.join(ROOT, "tools", "bench_hop_dtype.py")}
     bad = []
     for top in ("tools", "examples", "benchlib", "sgl_amd"):
         for dp, _, files in os.walk(os.path.join(ROOT, top)):
@@ -325,6 +326,9 @@ def test_only_the_checkers_use_the_oracle():
             bad.append(f)
     assert not bad, bad
     # and where it is allowed it is the baseline / the checker, inside one function each
+    hop = open(os.path.join(ROOT, "tools", "bench_hop_dtype.py")).read()
+    assert len(re.findall(r"^\s*import oracle\b", hop, flags=re.M)) == 1 and re.search(r"def check\(self.*?\n\s+\"\"\".*?\"\"\"\n\s+import oracle\b", hop, flags=re.S)
+    assert hop.index("v.check(host_csr") < hop.index("v.timed()")               # values are checked before anything is timed
     eng = open(os.path.join(ROOT, "benchlib", "engine.py")).read()
     assert len(re.findall(r"^\s*import oracle\b", eng, flags=re.M)) == 1 and "def cpu_baseline" in eng
     legs = open(os.path.join(ROOT, "benchlib", "cpu_legs.py")).read()

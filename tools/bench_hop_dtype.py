@@ -7,6 +7,10 @@ a warm-up of every variant: fp32 hops (the kernel of the default path, unchanged
 pitches (104 and 128 elements), and fp32 / bf16 at d = 128 and d = 147.  Prints the medians and the spread, writes
 profiles/bf16_hop_dtype.json (--out) and says which d = 100 pitch is faster.
 
+Before anything is timed, one hop of every variant is checked on sampled rows (the longest included), bit for bit, against the CPU
+model of the kernels' default summation order (oracle.oracle_spmm_slots with the R of the kernel the dispatch rule picks,
+tests/spmm_order_common.py).  A mismatch ends the run with a non-zero exit status: no ratio comes from an unchecked kernel.
+
     python tools/bench_hop_dtype.py [--steps 20] [--warmup 3] [--workload S1_products] [--out profiles/bf16_hop_dtype.json]
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/bench_hop_dtype.py --steps 3 --out ''` for kernel times, and under
@@ -21,7 +25,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
 from sgl_amd import _lib, device as dev, synthetic  # noqa: E402
+from spmm_order_common import default_long_row_nnz, dispatch  # noqa: E402
 
 K = 3
 
@@ -47,6 +53,33 @@ class Variant:
         self.csr.spmm_chain(self.x, K, outs=self.outs)
         if self.unroll:
             _lib.set_tuning("spmm_unroll", 0)
+
+    def check(self, host_csr, rows):
+        """one hop against the model on `rows`: number of elements whose bits differ (0 = checked and equal)"""
+        import oracle  # the checker: the CPU model of the kernels' summation order, never part of what is timed
+        rp, cc, vv = host_csr
+        n, bf16 = len(rp) - 1, self.dtype == torch.bfloat16
+        y = self.outs[0]
+        tuning = {"spmm_unroll": self.unroll} if self.unroll else {}
+        slices = dispatch("bf16" if bf16 else "f32", self.x.shape[1], self.x.stride(0), y.stride(0), self.x.data_ptr(), y.data_ptr(),
+                          False, len(cc) / n, tuning)
+        for k, val in tuning.items():
+            _lib.set_tuning(k, val)
+        try:
+            self.csr.spmm(self.x, out=y)
+        finally:
+            for k in tuning:
+                _lib.set_tuning(k, 0)
+        xh = self.x.cpu().float().numpy()
+        lr = default_long_row_nnz(len(cc))
+        want = np.empty((len(rows), xh.shape[1]), np.float32)
+        for c0, dc, var in slices:
+            want[:, c0:c0 + dc] = oracle.oracle_spmm_slots(rp, cc, vv, xh[:, c0:c0 + dc], 64 // var[1], lr, rows=rows)
+        got = y[torch.from_numpy(rows).to(y.device)].cpu()
+        if bf16:
+            w = torch.from_numpy(want).to(torch.bfloat16).view(torch.int16).numpy()
+            return int((got.view(torch.int16).numpy() != w).sum()), slices
+        return int((got.numpy().view(np.uint32) != want.view(np.uint32)).sum()), slices
 
     def timed(self):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -84,6 +117,10 @@ def main():
     rowptr, col, val = dev.normalize_adj(a_ptr, a_col, a_val, n, 0.5, None)
     del a_ptr, a_col, a_val
     csr = dev.DeviceCSR(rowptr, col, val, (n, n))
+    host_csr = (rowptr.cpu().numpy(), col.cpu().numpy(), val.cpu().numpy())
+    deg = np.diff(host_csr[0])
+    check_rows = np.unique(np.concatenate([np.random.default_rng(args.seed).choice(n, min(n, 2047), replace=False),
+                                           [int(deg.argmax())]])).astype(np.int64)
     result = {"workload": args.workload, "n_nodes": n, "nnz_a_hat": int(col.numel()), "prop_steps": K, "steps": args.steps,
               "warmup": args.warmup, "device": torch.cuda.get_device_name(device), "variants": {}, "ratios_bf16_over_fp32": {}}
     for d in [int(v) for v in args.dims.split(",")]:
@@ -95,6 +132,12 @@ def main():
             for un in [int(v) for v in args.bf16_unroll.split(",") if v]:
                 variants.append(Variant(f"d{d}_bf16_pitch{ld}_unroll{un}", csr, x, d, ld, torch.bfloat16, unroll=un))
         del x
+        for v in variants:                     # values first: a ratio from a kernel that computes something else is worth nothing
+            n_bad, slices = v.check(host_csr, check_rows)
+            print(f"EXP hop_dtype {v.name}: {len(check_rows)} sampled rows of one hop against the model: "
+                  f"{'bit-equal' if n_bad == 0 else f'{n_bad} ELEMENTS DIFFER'} (kernel {[s_[2] for s_ in slices]})", flush=True)
+            if n_bad:
+                raise SystemExit(f"bench_hop_dtype.py: {v.name} does not compute the documented sums; nothing was timed")
         for _ in range(args.warmup):
             for v in variants:
                 v.step()
