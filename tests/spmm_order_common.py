@@ -61,14 +61,9 @@ def dense_graph():
 _NAME = re.compile(r"spmm_(bf16_)?kernel")
 
 
-def parse_kernel_name(name):
-    """("bf16", (BV, GROUP, NCH, U)) / ("f32", (VEC, GROUP, NCH, U, NT)) from the name of an spmm_bf16_kernel / spmm_kernel
-    instance, None for any other kernel (the fix-up kernels included).  Accepts the demangled form
-    `... spmm_kernel<4, 64, 1, 16, false, false>(...)` and the mangled one `_ZN..11spmm_kernelILi4ELi64ELi1ELi16ELb0ELb0EEEv...`."""
-    m = _NAME.search(name)
-    if not m:
-        return None
-    rest = name[m.end():]
+def parse_template_args(rest):
+    """the integer template arguments that follow a kernel's name (shared with agg_rows_common.py): `<4, 64, (bool)1, false>(...)`
+    of a demangled name or `ILi4ELi64ELb1ELb0EEEv...` of a mangled one; None when there are none"""
     if rest.startswith("<"):
         inner = rest[1:rest.index(">")]
         args = []
@@ -76,11 +71,23 @@ def parse_kernel_name(name):
             tok = tok.strip()
             tok = tok[tok.rfind(")") + 1:] if ")" in tok else tok           # `(bool)1`, `(int)4`
             args.append(1 if tok == "true" else 0 if tok == "false" else int(tok))
-    else:
-        mm = re.match(r"I((?:L[a-z]\d+E)+)E", rest)
-        if not mm:
-            return None
-        args = [int(v) for v in re.findall(r"L[a-z](\d+)E", mm.group(1))]
+        return args
+    mm = re.match(r"I((?:L[a-z]\d+E)+)E", rest)
+    if not mm:
+        return None
+    return [int(v) for v in re.findall(r"L[a-z](\d+)E", mm.group(1))]
+
+
+def parse_kernel_name(name):
+    """("bf16", (BV, GROUP, NCH, U)) / ("f32", (VEC, GROUP, NCH, U, NT)) from the name of an spmm_bf16_kernel / spmm_kernel
+    instance, None for any other kernel (the fix-up kernels included).  Accepts the demangled form
+    `... spmm_kernel<4, 64, 1, 16, false, false>(...)` and the mangled one `_ZN..11spmm_kernelILi4ELi64ELi1ELi16ELb0ELb0EEEv...`."""
+    m = _NAME.search(name)
+    if not m:
+        return None
+    args = parse_template_args(name[m.end():])
+    if args is None:
+        return None
     if m.group(1):
         if len(args) != 4:
             raise ValueError(f"unexpected template arguments in {name!r}")

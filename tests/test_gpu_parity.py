@@ -12,6 +12,7 @@ import scipy.sparse as sp
 import torch
 
 import oracle
+from agg_rows_common import recursive_step_by_step as _recursive_step_by_step
 from inputs import hash_matrix
 from sgl_amd import _lib
 from sgl_amd import device as dev
@@ -1292,9 +1293,10 @@ def test_reorder_auto_and_row_sharded_blocks(cuda):
 
 def test_round5_kernels_fuzz_random_shapes(cuda):
     """40 random (rows, width, hops) shapes through the kernels added in round 5: every NAFS prefix from one pass against the
-    oracle per prefix (widths up to 512: every lane layout; 1 ... 40 hops: more than the fused kernel holds), the ensemble
-    combinations, the max / min backward against torch's autograd of stack(...).max(0) with ties and NaNs planted, the padded row
-    gather from aligned matrices, column views and duplicate / negative indices"""
+    oracle per prefix (widths up to 512, 1 ... 40 hops: more than the fused kernel holds), the ensemble combinations, the
+    max / min backward against torch's autograd of stack(...).max(0) with ties and NaNs planted, the padded row gather from
+    aligned matrices, column views and duplicate / negative indices.  The draws reach some of the lane layouts, by chance and
+    without checking which: every compiled layout of nafs_prefix_kernel is launched, by name, in test_gpu_agg_variants.py."""
     rng = np.random.default_rng(20260928)
     for case in range(40):
         n = int(rng.integers(1, 300))
@@ -1350,8 +1352,10 @@ def test_round5_kernels_fuzz_random_shapes(cuda):
 def test_aggregators_fuzz_random_shapes(cuda):
     """40 random (rows, width, hops, padded / dense) shapes through every aggregator kernel family: the bit-exact ones
     (sum / max / concat) against numpy bit for bit, the weighted ones and their gradients within tolerance -- widths 1..600
-    hit every lane layout (8 / 16 / 32 / 64 lanes, 1 / 2 chunks), the LDS concat tiles, the masked tails and the unaligned
-    gradient path; hop counts 1..20 hit every register instantiation and the general fallbacks"""
+    and hop counts 1..20 reach several lane layouts and hop capacities of the register-resident kernels, the LDS concat tiles,
+    the masked tails, the unaligned gradient path and the general fallbacks.  Which instances run is left to the draws and not
+    checked here (40 draws cannot reach the 54 and more instances per kernel, and none sets a layout tuning key):
+    test_gpu_agg_variants.py launches every compiled instance and identifies it by name."""
     from sgl_amd import _lib
     from sgl_amd import device as dev
     rng = np.random.default_rng(20260927)
@@ -1490,26 +1494,6 @@ def test_single_pass_gate_matches_two_pass_and_autograd(cuda, n, d, H):
     for h in range(H):
         rep = oracle.truth_report(fx[h].grad.cpu().numpy(), df32[h].cpu().numpy(), df64[h].cpu().numpy())
         assert rep["ok"], (h, rep)
-
-
-def _recursive_step_by_step(feats, weight, bias, cond=None):
-    """the reference's loop as written (iterate_learnable_weighted_message_op.py:28-51), any dtype, plain torch.  cond (a dict):
-    receives the condition magnitudes of the Linear's gradients -- the sums of the ABSOLUTE terms of weight.grad and bias.grad"""
-    d = feats[0].shape[1]
-    acc, weights = feats[0], None
-    for i in range(len(feats)):
-        inp = torch.hstack((feats[i], acc))
-        z = inp @ weight.view(-1, 1) + bias
-        if cond is not None and z.requires_grad:
-            def hook(g_, inp=inp.detach()):
-                cond["bias"] = cond.get("bias", 0) + g_.abs().sum()
-                cond["weight"] = cond.get("weight", 0) + g_.abs().t() @ inp.abs()
-            z.register_hook(hook)
-        score = torch.sigmoid(z)
-        weights = score if weights is None else torch.hstack((weights, score))
-        weights = torch.softmax(weights, dim=1)
-        acc = sum(weights[:, j:j + 1] * feats[j] for j in range(i + 1))
-    return acc, weights
 
 
 @pytest.mark.parametrize("n,d,H", [(3000, 128, 11), (2500, 100, 4), (700, 147, 6), (64, 16, 16), (90, 20, 12), (1, 500, 2), (900, 260, 5),
