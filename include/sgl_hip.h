@@ -27,6 +27,9 @@
  *   sgl_hop_concat_f32         ConcatMessageOp._combine (message_op/concat_message_op.py:11-12, torch.hstack).
  *   sgl_nafs_f32               OverSmoothDistanceWeightedOp._combine (message_op/over_smooth_distance_op.py:11-33).
  *   sgl_gather_rows_f32        the `feat[idx]` row gather of BaseSGAPModel.forward (sgl/models/base_model.py:58,60).
+ *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
+ *   sgl_hop_concat_bf16(_f32), STORED as bfloat16 (opt-in hop storage): read in place, widened exactly, float32 arithmetic in
+ *   sgl_nafs_bf16_f32          the float32 entries' order -- bit-identical to widening every hop first, without the copies.
  *
  * Conventions
  *   - every function returns int: 0 = success, non-zero = failure (hipError_t value or SGL_ERR_*); the message is
@@ -180,6 +183,31 @@ int sgl_gather_rows_bf16_f32(const uint16_t *d_x, int64_t ldx, int64_t n_rows, c
 /* the same rows of up to 16 bf16 hop matrices in ONE launch (mirrors sgl_gather_hops_padded_f32; more -> SGL_ERR_UNSUPPORTED) */
 int sgl_gather_hops_bf16_f32(int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, int64_t n_rows, const int64_t *d_idx,
                              int64_t n_idx, float *const *h_out, const int64_t *h_ldo, int64_t d, int64_t pad_cols, void *stream);
+
+/* -- full-matrix aggregators over bf16 hops: the hops are read in place (no float32 copy of any hop), every element is widened
+ * exactly and the arithmetic is that of the float32 entry named, in the same order, so each result is bit-identical to "widen every
+ * hop, then call the float32 entry".  h_x / h_ldx: HOST arrays of n_hops device pointers / leading dimensions in ELEMENTS (h_ldx
+ * NULL = d), 1 <= n_hops <= SGL_MAX_HOPS, d >= 1.  pad_cols as in the *_padded_f32 entries: columns [width, width + pad_cols) of an
+ * output row (width = d, for concat n_hops * d) are the row's own padding and are written as zeros, width + pad_cols <= ldo; with
+ * pad_cols = 0 nothing beyond the row is touched.  What lies beyond column d of a source row is the caller's padding: it may hold
+ * anything and never influences a written value. */
+/* sgl_hop_reduce_f32 (op = SGL_REDUCE_*; d_w: n_hops device floats for SGL_REDUCE_WSUM) -> float32.  Element-wise: 16-byte lanes of 8
+ * elements when hop rows are 16-byte aligned on pitches that are multiples of 8 (and the output rows 16-byte aligned), narrower lanes
+ * otherwise, any d. */
+int sgl_hop_reduce_bf16_f32(int op, int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, const float *d_w, float *d_out,
+                            int64_t ldo, int64_t pad_cols, int64_t n, int64_t d, void *stream);
+/* out[:, h*d:(h+1)*d] = X_h: a copy of bit patterns (bf16 -> bf16) / an exact widening (bf16 -> float32); any d >= 1.  The output
+ * must not alias an input. */
+int sgl_hop_concat_bf16(int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, uint16_t *d_out, int64_t ldo, int64_t pad_cols,
+                        int64_t n, int64_t d, void *stream);
+int sgl_hop_concat_bf16_f32(int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, float *d_out, int64_t ldo, int64_t pad_cols,
+                            int64_t n, int64_t d, void *stream);
+/* sgl_nafs_padded_f32's register-resident kernel in the same lane layout (8-byte loads of 4 elements) -> float32 out [n, d] and,
+ * when d_w_out is not NULL, the float32 weights [n, n_hops].  Takes n_hops <= 16, d <= 512, hop rows that are 8-byte aligned on
+ * pitches that are multiples of 4 elements, an output with 16-byte aligned rows on a pitch that is a multiple of 4 floats; anything
+ * else returns SGL_ERR_UNSUPPORTED (there is no two-pass bf16 form: callers widen the hops and use sgl_nafs_padded_f32). */
+int sgl_nafs_bf16_f32(int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, float *d_out, int64_t ldo, int64_t pad_cols,
+                      float *d_w_out, int64_t ldw, int64_t n, int64_t d, void *stream);
 
 /* ---- device memory -> pageable host memory --------------------------------------------------------------------------------- */
 /* Contiguous copy through a team of host threads and pinned staging buffers, huge pages requested for a freshly allocated

@@ -18,6 +18,7 @@ SGL_CSR_STRICT_ORDER = 0x1
 SGL_CSR_NO_XCD_REMAP = 0x2
 SGL_REDUCE_SUM, SGL_REDUCE_MEAN, SGL_REDUCE_MAX, SGL_REDUCE_MIN, SGL_REDUCE_WSUM = 0, 1, 2, 3, 4
 SGL_MAX_HOPS = 64
+SGL_ERR_UNSUPPORTED = 1003
 SGL_MEM_DEFAULT, SGL_MEM_CONTIGUOUS, SGL_MEM_VMM = 0, 1, 2
 
 _lib = None
@@ -56,6 +57,12 @@ PROTOTYPES = {
                                          c_void_p]),
     "sgl_gather_hops_bf16_f32": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                          c_void_p]),
+    "sgl_hop_reduce_bf16_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                        c_void_p]),
+    "sgl_hop_concat_bf16": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "sgl_hop_concat_bf16_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "sgl_nafs_bf16_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                  c_void_p]),
     "sgl_allgather_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "sgl_exchange_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "sgl_exchange_backend": (c_char_p, []),

@@ -55,7 +55,10 @@ hop_dtype     "float32" (default) -> hop matrices are stored as float32: the 1e-
               GraphOp(hop_dtype="bfloat16")) -> OPT-IN reduced-precision storage: X is rounded once to bfloat16, every hop is
               accumulated in fp32 from the stored bf16 rows of the previous one and rounded once, to nearest even, when it is stored
               (sgl_spmm_chain_bf16); propagate() returns K + 1 bfloat16 device matrices of half the size, propagate_reduce() and the
-              mini-batch gathers hand float32 to everything downstream.  Another precision class (about 3 significant digits per
+              mini-batch gathers hand float32 to everything downstream; the sum / mean / max / min / simple_weighted / concat /
+              over_smooth_dis_weighted aggregators read the stored bfloat16 hops in place (float32 results, bit-identical to
+              aggregating widened copies, which are never made; a concat pre-aggregator's _processed_feature stays bfloat16),
+              every other aggregator widens whole hop matrices first (device.widen_hops).  Another precision class (about 3 significant digits per
               hop: max error / max|hop| of a few 1e-3), OUTSIDE the 1e-5 contract and never a default.  Single GPU,
               device-resident hops only: with host_output or slab_hops it raises; delta_propagate, share_hops and the on-disk hop
               cache are bypassed (they hold float32 entries only).  Read by GraphOp (LaplacianGraphOp / PprGraphOp) only: the

@@ -224,14 +224,16 @@ def _same_hop_dtype(who, *tensors):
 
 def _no_bf16(who, *tensors):
     if any(torch.is_tensor(t) and t.dtype == torch.bfloat16 for t in tensors):
-        raise TypeError(f"{who} has no bfloat16 form (bf16 hop storage covers spmm, spmm_chain, spmm_acc and the row gathers)")
+        raise TypeError(f"{who} has no bfloat16 form (bf16 hop storage covers spmm, spmm_chain, spmm_acc, the row gathers and the "
+                        "reduce / concat / NAFS aggregators)")
 
 
 def widen_hops(feats):
-    """bfloat16 hop matrices as float32 copies (exact), each in a padded buffer of its own; float32 ones are passed through.  The
-    full-matrix aggregators have no bf16 kernels: given bf16 hops they widen them hop by hop through torch with this and then run
-    the fp32 kernels -- a correctness fallback that costs 4 more bytes per element of every widened hop while the aggregate is
-    computed, not the fast path (that is the fused propagate_reduce, or the mini-batch gathers, which widen what they gather)."""
+    """bfloat16 hop matrices as float32 copies (exact), each in a padded buffer of its own; float32 ones are passed through.
+    hop_reduce, hop_concat and nafs_aggregate read a list of bf16 hops in place and do not come here; what has no bf16 kernel does
+    (hop_lincomb, nafs_prefix, the gradient-carrying wrappers, the learnable gates on whole matrices, lists that mix dtypes, the
+    NAFS shapes the register-resident kernel does not take): the hops are widened hop by hop through torch and the fp32 kernels run
+    -- a correctness fallback that costs 4 more bytes per element of every widened hop while the aggregate is computed."""
     out = []
     for f in feats:
         if torch.is_tensor(f) and f.is_cuda and f.dtype == torch.bfloat16 and f.dim() == 2:
@@ -816,11 +818,12 @@ def normalize_block(rowptr, col, val, row0, n_cols, r, alpha=None, symmetric=Tru
 # ------------------------------------------------------------------------------------------------
 # aggregators
 # ------------------------------------------------------------------------------------------------
-def _check_hops(feats):
+def _check_hops(feats, bf16=False):
+    """bf16=True: a list that _all_bf16() accepted, for an entry point that reads bfloat16 hops in place"""
     if len(feats) < 1 or len(feats) > _lib.SGL_MAX_HOPS:
         raise ValueError(f"between 1 and {_lib.SGL_MAX_HOPS} hop matrices are supported")
     for i, f in enumerate(feats):
-        _check_mat(f, f"feat_list[{i}]")
+        _check_mat(f, f"feat_list[{i}]", bf16=bf16)
         if f.shape != feats[0].shape or f.device != feats[0].device:
             raise ValueError("all hop matrices must have the same shape and device")
 
@@ -844,9 +847,41 @@ def _widened(feats, out):
     return wide, torch.as_strided(out, (n, dp), (out.stride(0), 1), out.storage_offset()), dp
 
 
+def _all_bf16(feats):
+    """every member a bfloat16 CUDA matrix: the list goes to a kernel that reads bf16 hops in place, nothing is copied"""
+    return len(feats) > 0 and all(torch.is_tensor(f) and f.is_cuda and f.dim() == 2 and f.dtype == torch.bfloat16 for f in feats)
+
+
+def _alloc_out(n, d, device, dtype=torch.float32):
+    """(alloc_rows output, its own_pad) for a kernel that writes the declared pad columns itself, as zeros; where there is padding
+    the kernel is not told about (a single row), it is zeroed here"""
+    out = alloc_rows(n, d, device, zero_pad=False, dtype=dtype)
+    pad = own_pad(out)
+    if pad == 0:
+        parent = padded_parent(out)
+        if parent.shape[1] != d:
+            parent[:, d:].zero_()
+    return out, pad
+
+
 def hop_reduce(op, feats, weights=None):
-    """sum / mean / max / min / 1-D weighted sum over the hop list -> new [n, d] float32 tensor.  bfloat16 hops are widened to
-    float32 copies first (widen_hops: a correctness fallback, 4 more bytes per element of every hop while it runs)."""
+    """sum / mean / max / min / 1-D weighted sum over the hop list -> new [n, d] float32 tensor.  A list of bfloat16 hops is read in
+    place (sgl_hop_reduce_bf16_f32: every element widened exactly, the float32 kernel's operations in its order -- the same bits
+    as over widened copies, without the copies); a list that mixes dtypes widens its bfloat16 members first (widen_hops)."""
+    if _all_bf16(feats):
+        _check_hops(feats, bf16=True)
+        n, d = feats[0].shape
+        w = None
+        if op == _lib.SGL_REDUCE_WSUM:
+            w = weights.detach().to(device=feats[0].device, dtype=torch.float32).contiguous()
+            if w.numel() != len(feats):
+                raise ValueError("The feature list and the weight list have different lengths!")
+        result, pad = _alloc_out(n, d, feats[0].device)
+        ptrs, lds = _lib.hop_arrays(feats)
+        with torch.cuda.device(feats[0].device):
+            check(lib().sgl_hop_reduce_bf16_f32(op, len(feats), ptrs, lds, ptr(w) if w is not None else None, ptr(result), _ld(result),
+                                                pad, n, d, current_stream_ptr()), "sgl_hop_reduce_bf16_f32")
+        return result
     feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
@@ -864,9 +899,25 @@ def hop_reduce(op, feats, weights=None):
     return result
 
 
-def hop_concat(feats):
-    """the hops side by side -> [n, H d] float32.  bfloat16 hops are widened to float32 copies first (widen_hops: a correctness
-    fallback, 4 more bytes per element of every hop while it runs)."""
+def hop_concat(feats, out_dtype=None):
+    """the hops side by side -> [n, H d] float32.  A list of bfloat16 hops is read in place (sgl_hop_concat_bf16_f32: an exact
+    widening), and with out_dtype=torch.bfloat16 stays bfloat16 (sgl_hop_concat_bf16: a copy of bit patterns into an
+    alloc_rows(..., dtype=torch.bfloat16) matrix); a list that mixes dtypes widens its bfloat16 members first (widen_hops)."""
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"hop_concat: out_dtype is float32 or bfloat16, not {out_dtype}")
+    if _all_bf16(feats):
+        _check_hops(feats, bf16=True)
+        n, d = feats[0].shape
+        H = len(feats)
+        out, pad = _alloc_out(n, H * d, feats[0].device, dtype=out_dtype or torch.float32)
+        fn, name = ((lib().sgl_hop_concat_bf16, "sgl_hop_concat_bf16") if out_dtype == torch.bfloat16
+                    else (lib().sgl_hop_concat_bf16_f32, "sgl_hop_concat_bf16_f32"))
+        ptrs, lds = _lib.hop_arrays(feats)
+        with torch.cuda.device(feats[0].device):
+            check(fn(H, ptrs, lds, ptr(out), _ld(out), pad, n, d, current_stream_ptr()), name)
+        return out
+    if out_dtype == torch.bfloat16:
+        raise TypeError("hop_concat: a bfloat16 result is a copy of bfloat16 hop matrices (every member of the list), nothing is rounded here")
     feats = widen_hops(feats)
     _check_hops(feats)
     n, d = feats[0].shape
@@ -1383,16 +1434,28 @@ def hop_scores2(feats, v, u, mask, h0, h1):
 
 
 def nafs_aggregate(feats, return_weights=False):
-    """OverSmoothDistanceWeightedOp._combine (over_smooth_distance_op.py:11-33) on device.  bfloat16 hops are widened to float32
-    copies first (widen_hops: a correctness fallback, 4 more bytes per element of every hop while it runs)."""
-    feats = widen_hops(feats)
-    _check_hops(feats)
+    """OverSmoothDistanceWeightedOp._combine (over_smooth_distance_op.py:11-33) on device -> float32.  A list of bfloat16 hops is
+    read in place by the register-resident kernel (sgl_nafs_bf16_f32: the float32 kernel's lane layout and arithmetic, the same
+    bits as over widened copies); the shapes that kernel does not take (more than 16 hops, d > 512, rows that are not 8-byte
+    aligned) and lists that mix dtypes are widened to float32 copies first (widen_hops) and go to the fp32 entry."""
+    direct = _all_bf16(feats)
+    if not direct:
+        feats = widen_hops(feats)
+    _check_hops(feats, bf16=direct)
     n, d = feats[0].shape
     H = len(feats)
     out = alloc_rows(n, d, feats[0].device)
     w = torch.empty((n, H), dtype=torch.float32, device=feats[0].device)
-    ptrs, lds = _lib.hop_arrays(feats)
     with torch.cuda.device(out.device):
+        if direct:
+            ptrs, lds = _lib.hop_arrays(feats)
+            rc = lib().sgl_nafs_bf16_f32(H, ptrs, lds, ptr(out), _ld(out), own_pad(out), ptr(w), H, n, d, current_stream_ptr())
+            if rc == _lib.SGL_ERR_UNSUPPORTED:         # not a shape of the bf16 kernel: today's route, no second bf16 kernel
+                feats = widen_hops(feats)
+            else:
+                check(rc, "sgl_nafs_bf16_f32")
+                return (out, w) if return_weights else out
+        ptrs, lds = _lib.hop_arrays(feats)
         check(lib().sgl_nafs_padded_f32(H, ptrs, lds, ptr(out), _ld(out), own_pad(out), ptr(w), H, n, d, current_stream_ptr()),
               "sgl_nafs_padded_f32")
     return (out, w) if return_weights else out

@@ -160,7 +160,14 @@ class BaseSGAPModel(nn.Module):
         self._processed_feat_list = self._pre_graph_op.propagate(adj, feature)
         if not self._pre_msg_learnable:
             with torch.no_grad():
-                self._processed_feature = self._pre_msg_op.aggregate(self._processed_feat_list)
+                hops = self._processed_feat_list
+                if (self._pre_msg_op.aggr_type == "concat" and isinstance(hops, list)
+                        and dev._all_bf16(hops[self._pre_msg_op._start:self._pre_msg_op._end])):
+                    # bfloat16 hop storage: the concatenation is a copy of the stored values and stays bfloat16 (the rule the folded
+                    # result of SGC follows); forward() gathers its rows into float32 mini-batches
+                    self._processed_feature = dev.hop_concat(hops[self._pre_msg_op._start:self._pre_msg_op._end], out_dtype=torch.bfloat16)
+                else:
+                    self._processed_feature = self._pre_msg_op.aggregate(hops)
 
     def _hops_are_heavy(self, feature):
         """fuse_aggregate = "auto": would the K+1 hop matrices take more than a quarter of the free device memory?"""

@@ -604,6 +604,10 @@ class GraphOp:
         return out
 
 
+# aggregator types whose _combine reaches a device function that reads bfloat16 hop matrices in place
+_BF16_IN_PLACE = ("sum", "mean", "max", "min", "simple_weighted", "concat", "over_smooth_dis_weighted")
+
+
 class MessageOp(nn.Module):
     def __init__(self, start=None, end=None):
         super(MessageOp, self).__init__()
@@ -630,8 +634,12 @@ class MessageOp(nn.Module):
             if not isinstance(feat, Tensor):
                 raise TypeError("The feature matrices must be tensors!")
         if self._aggr_type != "last" and any(f.dtype == torch.bfloat16 and f.is_cuda for f in feat_list):
-            # bfloat16 hop storage: no aggregator computes in bf16.  Whole hop matrices are widened (exact) before the fp32 kernels --
-            # the correctness fallback of device.widen_hops; the fast paths never get here (propagate_reduce, mini-batch gathers)
-            feat_list = dev.widen_hops(feat_list)
+            # bfloat16 hop storage: no aggregator computes in bf16.  The reductions, concat and NAFS read the stored hops in place
+            # (device.hop_reduce / hop_concat / nafs_aggregate widen each element in registers; hops outside [start, end) are never
+            # touched) and return what they return over widened copies, bit for bit.  Everything else -- the learnable aggregators,
+            # and any list through which a gradient has to flow -- gets whole hop matrices widened (exact) before the fp32 kernels:
+            # the correctness fallback of device.widen_hops.
+            if self._aggr_type not in _BF16_IN_PLACE or (torch.is_grad_enabled() and any(f.requires_grad for f in feat_list)):
+                feat_list = dev.widen_hops(feat_list)
 
         return self._combine(feat_list)

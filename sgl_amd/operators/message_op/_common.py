@@ -7,11 +7,14 @@ from ..utils import _as_device_list, _rowmajor
 
 
 def device_hops(feat_list):
-    """-> (list of row-major float32 CUDA tensors, original device or None when already on the GPU)"""
+    """-> (list of row-major float32 CUDA tensors, original device or None when already on the GPU).  bfloat16 CUDA matrices
+    (bf16 hop storage) stay bfloat16 when no gradient has to flow: device.hop_reduce / hop_concat / nafs_aggregate read them in
+    place."""
     if len(feat_list) == 0:
         raise ValueError("empty feature list")
     feats, home = _as_device_list(feat_list)
-    return [_rowmajor(f) for f in feats], home
+    direct = not wants_grad(feats)
+    return [_rowmajor(f, keep_bf16=direct) for f in feats], home
 
 
 def back_home(t, home):

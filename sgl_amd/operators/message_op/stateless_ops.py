@@ -36,8 +36,8 @@ class ConcatMessageOp(MessageOp):
     def _slab_view(feats):
         """the hops side by side in one buffer already (GraphOp slab_hops layout)?  Then their concatenation is a view."""
         f0 = feats[0]
-        if not (torch.is_tensor(f0) and f0.dim() == 2 and f0.shape[0] > 0):
-            return None
+        if not (torch.is_tensor(f0) and f0.dim() == 2 and f0.shape[0] > 0) or f0.dtype == torch.bfloat16:
+            return None                                 # (a bfloat16 list is concatenated into the float32 result the op returns)
         n, d = f0.shape
         base = f0.untyped_storage().data_ptr()
         for k, f in enumerate(feats):

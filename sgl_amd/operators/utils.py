@@ -115,10 +115,12 @@ def _as_device_list(feat_list):
     return [dev.upload_rows(f, "cuda") if not f.requires_grad else f.to("cuda") for f in feat_list], first.device
 
 
-def _rowmajor(f):
+def _rowmajor(f, keep_bf16=False):
+    """keep_bf16: the caller hands the list to a device function that reads bfloat16 hop matrices in place (device.hop_reduce /
+    hop_concat / nafs_aggregate): a bfloat16 CUDA matrix stays what it is"""
     if f.dim() != 2:
         raise ValueError("feature matrices must be 2-D")
-    if f.dtype != torch.float32:
+    if f.dtype != torch.float32 and not (keep_bf16 and f.dtype == torch.bfloat16 and f.is_cuda):
         f = f.float()
     if (f.shape[1] > 1 and f.stride(1) != 1) or (f.shape[0] > 1 and f.stride(0) < f.shape[1]):
         f = f.contiguous()
@@ -133,7 +135,9 @@ def one_dim_weighted_add(feat_list, weight_list):
     elif len(weight_list.shape) != 1:
         raise ValueError("The weight list should be a 1d tensor!")
     feats, home = _as_device_list(feat_list)
-    feats = [_rowmajor(f) for f in feats]
+    # bfloat16 hops go to the kernel as they are, unless a gradient has to come back through this call (its backward is float32)
+    direct = not (torch.is_grad_enabled() and (weight_list.requires_grad or any(f.requires_grad for f in feats)))
+    feats = [_rowmajor(f, keep_bf16=direct) for f in feats]
     out = dev.hop_wsum1d(feats, weight_list.to(feats[0].device))
     return out if home is None else out.to(home)
 
