@@ -27,6 +27,8 @@
  *   sgl_hop_concat_f32         ConcatMessageOp._combine (message_op/concat_message_op.py:11-12, torch.hstack).
  *   sgl_nafs_f32               OverSmoothDistanceWeightedOp._combine (message_op/over_smooth_distance_op.py:11-33).
  *   sgl_gather_rows_f32        the `feat[idx]` row gather of BaseSGAPModel.forward (sgl/models/base_model.py:58,60).
+ *   sgl_edge_dot_f32           `torch.mm(Z, Z.t())[e0, e1]`, the edge scores of link prediction (sgl/tasks/link_prediction.py:282-283,
+ *                              sgl/tasks/utils.py:281-285), without the N x N matrix.
  *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
  *   sgl_hop_concat_bf16(_f32), STORED as bfloat16 (opt-in hop storage): read in place, widened exactly, float32 arithmetic in
  *   sgl_nafs_bf16_f32          the float32 entries' order -- bit-identical to widening every hop first, without the copies.
@@ -491,6 +493,18 @@ int sgl_gather_hops_padded_f32(int n_hops, const float *const *h_x, const int64_
  * by own row, so that a row several peers gather is read from HBM once. */
 int sgl_scatter_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_src, const int64_t *d_dst,
                          int64_t n_idx, float *d_out, int64_t ldo, int64_t n_out_rows, int64_t d, void *stream);
+
+/* Scores of an edge list: out[e] = sum_k A[u_e, k] * B[v_e, k] for the n_edges pairs (u_e, v_e) of d_edges (int64 [n_edges, 2]
+ * row-major on device, the reference's LongTensor layout; B may be A).  What `sim = torch.mm(Z, Z.t())` followed by
+ * `sim[edges[:, 0], edges[:, 1]]` computes (sgl/tasks/link_prediction.py:282-283 with sgl/tasks/utils.py:266, and under autograd
+ * sgl/tasks/utils.py:281-285) without the N x N matrix.  Negative indices count from the end; an index outside [-n, n) makes THAT
+ * edge's output NaN -- the kernel never traps (the rule of sgl_gather_rows_bf16_f32).  Columns d .. pitch are never used (they may
+ * hold NaN), nothing beyond column d of a matrix's last row is read.  16-byte aligned bases with pitches that are multiples of 4
+ * floats get 16-byte lane accesses for any d, everything else (column views at odd offsets) one float per lane.  The summation order
+ * depends on d and that layout alone: not on n_edges, the position of the edge, or which row is u.  d = 0 gives zeros; more edges
+ * than one launch covers -> SGL_ERR_UNSUPPORTED (split the list: edges are independent). */
+int sgl_edge_dot_f32(const float *d_a, int64_t lda, int64_t n_a, const float *d_b, int64_t ldb, int64_t n_b,
+                     const int64_t *d_edges, int64_t n_edges, int64_t d, float *d_out, void *stream);
 
 /* Per-column content signature of a DEVICE matrix: d_sig[c] = wrapping 64-bit sum over the rows r of mix(bits(X[r, c]), r), for
  * c < round_up(d, 4) (uint64 on device; rows 16-byte aligned, pitch a multiple of 4 floats covering round_up(d, 4)).  One streaming

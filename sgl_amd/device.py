@@ -18,7 +18,7 @@ __all__ = [
     "normalize_block", "degree_powers", "PreparedAdjacency", "PreparedBlock",
     "placed_empty", "MEM_MODES",
     "hop_reduce", "hop_concat", "hop_reduce_grad", "hop_concat_grad", "hop_lincomb", "hop_wsum1d", "hop_wsum2d", "hop_scores", "hop_scores2", "hop_gate", "gate_fusable", "nafs_aggregate", "nafs_prefix",
-    "gather_rows",
+    "gather_rows", "edge_dot",
 ]
 
 
@@ -1643,6 +1643,76 @@ def _gather_bf16(feats, idx, outs=None):
                       "sgl_gather_hops_bf16_f32")
     _wrote(*outs)
     return outs
+
+
+def _device_edges(edges, n_a, n_b, device):
+    """an edge list of any kind as a contiguous int64 [E, 2] tensor on `device`.  `edges`: an [E, 2] tensor / ndarray (host or
+    device), or a pair (u, v) -- a tuple or list of two index sequences of one length (a Python list of two is always read as that
+    pair).  Host indices are validated here, column 0 against n_a and column 1 against n_b, as _device_index does; device index
+    tensors are not (the kernel turns a bad pair into NaN)."""
+    if isinstance(edges, (tuple, list)) and len(edges) == 2:
+        u, v = edges
+        if torch.is_tensor(u) and torch.is_tensor(v) and u.is_cuda and v.is_cuda:
+            if u.dim() != 1 or u.shape != v.shape:
+                raise ValueError("edge_dot: u and v must be 1-D and of one length")
+            return torch.stack((u.to(device=device, dtype=torch.int64), v.to(device=device, dtype=torch.int64)), dim=1).contiguous()
+        u, v = (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t) for t in (u, v))
+        if u.ndim != 1 or u.shape != v.shape:
+            raise ValueError("edge_dot: u and v must be 1-D and of one length")
+        edges = np.stack((u.astype(np.int64, copy=False), v.astype(np.int64, copy=False)), axis=1) if u.size else np.zeros((0, 2), np.int64)
+    if not (torch.is_tensor(edges) and edges.is_cuda):
+        host = edges.numpy() if torch.is_tensor(edges) else np.asarray(edges)
+        if host.size == 0:
+            host = host.reshape(0, 2)
+        if host.ndim != 2 or host.shape[1] != 2:
+            raise ValueError("edge_dot: edges must be [E, 2] (or a pair (u, v))")
+        if host.dtype.kind not in "iu":
+            raise TypeError("edge_dot: edges must be integers")
+        host = host.astype(np.int64, copy=False)
+        if host.shape[0] and (host[:, 0].min() < -n_a or host[:, 0].max() >= n_a or host[:, 1].min() < -n_b or host[:, 1].max() >= n_b):
+            raise IndexError("index out of range in edge list")
+        edges = torch.from_numpy(np.ascontiguousarray(host))
+    elif edges.dim() != 2 or edges.shape[1] != 2:
+        raise ValueError("edge_dot: edges must be [E, 2] (or a pair (u, v))")
+    return edges.to(device=device, dtype=torch.int64).contiguous()
+
+
+EDGE_DOT_MAX_EDGES = 1 << 27          # edges per launch (every lane layout's grid fits one launch); longer lists are split
+
+
+def edge_dot(a, b, edges, out=None):
+    """out[e] = <a[u_e], b[v_e]> for the pairs of `edges` (sgl_edge_dot_f32): the entries `torch.mm(a, b.t())[u, v]` of the reference's
+    link-prediction scores (tasks/link_prediction.py:282-283, tasks/utils.py:281-285) without the [n_a, n_b] matrix.
+    a, b: [n_a, d] / [n_b, d] float32 CUDA matrices (b may be a; padded buffers and column views are read in place); edges: see
+    _device_edges.  Negative indices count from the end; in a DEVICE index tensor a pair outside the matrices gives NaN for that edge
+    (host indices raise IndexError).  Returns / fills a float32 [E] tensor.  Lists too long for one launch are split: edges are
+    independent, the bits do not change."""
+    _no_bf16("edge_dot", a, b)
+    _check_mat(a, "a")
+    _check_mat(b, "b")
+    if a.shape[1] != b.shape[1] or a.device != b.device:
+        raise ValueError("edge_dot: a and b must have the same row length and live on one device")
+    d = a.shape[1]
+    edges = _device_edges(edges, a.shape[0], b.shape[0], a.device)
+    n_e = edges.shape[0]
+    if out is None:
+        out = torch.empty(n_e, dtype=torch.float32, device=a.device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == a.device and out.dtype == torch.float32 and out.dim() == 1
+              and out.numel() == n_e and out.is_contiguous()):
+        raise ValueError("edge_dot: `out` must be a contiguous float32 [E] tensor on the matrices' device")
+    step, lo = max(int(EDGE_DOT_MAX_EDGES), 1), 0
+    with torch.cuda.device(a.device):
+        while lo < n_e:
+            m = min(step, n_e - lo)
+            rc = lib().sgl_edge_dot_f32(ptr(a), _ld(a), a.shape[0], ptr(b), _ld(b), b.shape[0], c_void_p(edges.data_ptr() + 16 * lo), m, d,
+                                        c_void_p(out.data_ptr() + 4 * lo), current_stream_ptr())
+            if rc == _lib.SGL_ERR_UNSUPPORTED and m > 1:      # more than one launch covers: halve
+                step = (m + 1) // 2
+                continue
+            check(rc, "sgl_edge_dot_f32")
+            lo += m
+    _wrote(out)
+    return out
 
 
 def gather_rows(x, idx, out=None):
