@@ -289,7 +289,12 @@ int sgl_shim_cache_stats(int64_t *hits, int64_t *misses);
  * end (where utils.py:32 rounds).  Two-step protocol so the caller owns the output buffers:
  *   1. sgl_norm_prepare(...)  -> *nnz_out   (counts missing diagonal entries; synchronises `stream`)
  *   2. sgl_norm_execute(...)  fills d_out_rowptr [n+1], d_out_col [nnz_out], d_out_val [nnz_out]
- *      (and d_out_val64 [nnz_out] when not NULL: the fp64 values before rounding, for parity tests). */
+ *      (and d_out_val64 [nnz_out] when not NULL: the fp64 values before rounding, for parity tests).
+ * The pattern is ALWAYS the union of A's stored entries and the diagonal: an entry whose value comes out exactly 0 (a stored
+ * zero of A, a_ii = -1, a degree of 0 whose inf factor is replaced by 0) is kept as a stored 0.0, where scipy -- the reference
+ * -- stores nothing.  Values agree; 0 * inf = NaN reaches an SpMM output row only through such a stored zero.  The Python layer
+ * (sgl_amd.device) drops the entries whose fp64 value is exactly 0 and so returns the reference's pattern; a C caller that feeds
+ * such weights and needs it does the same with d_out_val64. */
 int sgl_norm_prepare(int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_col, int64_t *nnz_out,
                      void *stream);
 int sgl_norm_execute(int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_col, const float *d_val,
@@ -329,6 +334,8 @@ int sgl_norm_build_symcheck(int64_t n, int64_t nnz, const int64_t *d_rowptr, con
                             uint64_t *d_sym_hash, void *stream);
 int sgl_norm_block_colsum(int64_t n_cols, int64_t nnz, const int32_t *d_col, const double *d_val64, double *d_colsum,
                           void *stream);
+/* A_hat[j, i] = (T'[j, i] L[j]) R[i] [+ the PPR mix] over the block's rows as sgl_norm_block_build laid them out: one value per
+ * stored entry of T + I, exact zeros included (see sgl_norm_execute: the C ABI keeps stored zeros, sgl_amd.device drops them). */
 int sgl_norm_block_scale(int64_t n, int64_t row0, const int64_t *d_rowptr, const int32_t *d_col, const double *d_val64,
                          const double *d_left_local, const double *d_right_global, int use_alpha, double alpha,
                          float *d_out_val, double *d_out_val64, void *stream);

@@ -230,18 +230,35 @@ def sym_norm_csr(indptr, indices, data, n, r, alpha=None):
         left[np.isinf(left)] = 0.0           # utils.py:80
         right = np.power(deg, -r)            # utils.py:83
         right[np.isinf(right)] = 0.0         # utils.py:84
-    # (A' diag(left))^T diag(right)  (utils.py:87): entry (i,j) of A' lands at (j,i)
-    v = (val2 * left[col2]) * right[rows2]
+    # (A' diag(left))^T diag(right)  (utils.py:87): entry (i,j) of A' lands at (j,i).  Both products are scipy sparse matmuls, and
+    # those store no sum that is exactly 0 (neither does the A + I above, nor the PPR sum below): a zero degree factor
+    # (inf -> 0) or a zero weight removes the entry from the PATTERN, which is what decides who reads a non-finite feature row.
+    with np.errstate(invalid="ignore"):
+        v = val2 * left[col2]
+        keep = v != 0.0                          # (NaN != 0: a negative degree's NaN factor stays stored)
+        rows2, col2, v = rows2[keep], col2[keep], v[keep]
+        v = v * right[rows2]
+        keep = v != 0.0
+        rows2, col2, v = rows2[keep], col2[keep], v[keep]
     t_rows, t_cols = col2, rows2
     order = np.lexsort((t_cols, t_rows))     # .tocsr() of the transposed product: sorted rows/cols
     t_rows, t_cols, v = t_rows[order], t_cols[order], v[order]
-    if alpha is not None:                    # ppr_graph_op.py:20
+    if alpha is not None:                    # ppr_graph_op.py:20: (1 - alpha) * A_hat (a scalar product: pattern kept) + alpha * I
         v = (1 - alpha) * v
+        # the sum is over the UNION pattern: a diagonal that A_hat does not store (a_ii = -1 cancelled at A + I, or a zero degree)
+        # still receives alpha
+        has_diag = np.zeros(n, dtype=bool)
+        has_diag[t_rows[t_rows == t_cols]] = True
+        miss = np.nonzero(~has_diag)[0]
+        if len(miss):
+            t_rows = np.concatenate([t_rows, miss])
+            t_cols = np.concatenate([t_cols, miss])
+            v = np.concatenate([v, np.zeros(len(miss))])
+            order = np.lexsort((t_cols, t_rows))
+            t_rows, t_cols, v = t_rows[order], t_cols[order], v[order]
         diag = t_rows == t_cols
         v[diag] = v[diag] + alpha
-        # (the diagonal is always structurally present because A' = A + I; scipy's binop
-        #  would drop an exactly-zero sum -- replicate)
-        keep = v != 0.0
+        keep = v != 0.0                          # scipy's binop drops an exactly-zero sum
         if not keep.all():
             t_rows, t_cols, v = t_rows[keep], t_cols[keep], v[keep]
     out_ptr = np.zeros(n + 1, dtype=np.int64)

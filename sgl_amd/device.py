@@ -587,6 +587,37 @@ def clear_power_cache():
     _POW_CACHE.clear()
 
 
+def _all_positive(val, deg=None):
+    """one flag per preparation: is every stored weight of A (and every degree handed in) > 0?  Then A + I holds no stored zero and
+    no degree is 0, so no entry of A_hat can be exactly 0 and the kernels' union pattern of A and I IS the reference's.  Anything
+    else -- a stored 0, a negative or NaN weight, a_ii = -1, a degree <= 0 -- may leave exact zeros behind, which scipy never
+    stores (_drop_exact_zeros).  Two reductions and one read-back per preparation, none per (r, alpha)."""
+    flags = [t.min() > 0 for t in (val, deg) if t is not None and t.numel()]
+    return bool(torch.stack(flags).all().item()) if flags else True
+
+
+def _drop_exact_zeros(rowptr, col, val32, val64):
+    """(rowptr, col, val32, val64) without the entries whose fp64 value is exactly 0 (NaN is kept): what scipy leaves of them -- it
+    stores no exact zero after A + I, after either diagonal product, or after the PPR sum (operators/utils.py:77-87,
+    ppr_graph_op.py:20).  Only ever entered for a preparation that _all_positive() did not clear (or alpha = 1); the inputs are
+    left as they are, so a cached Laplacian and the diagonal positions keep describing the uncompacted block."""
+    keep = val64 != 0
+    if bool(keep.all().item()):
+        return rowptr, col, val32, val64
+    before = torch.zeros(keep.numel() + 1, dtype=torch.int64, device=keep.device)
+    before[1:] = torch.cumsum(keep, 0)
+    return before[rowptr], col[keep], val32[keep], val64[keep]
+
+
+def _reference_pattern(prune, return_fp64, rowptr, col, values):
+    """the tail of every normalize(): `values` = (val32, val64) over (rowptr, col) when `prune` (the preparation may hold a zero,
+    or alpha = 1: (1 - alpha) A_hat is all zeros and the reference keeps alpha I alone), else what the caller asked for"""
+    if prune:
+        rowptr, col, v32, v64 = _drop_exact_zeros(rowptr, col, *values)
+        values = (v32, v64) if return_fp64 else (v32,)
+    return (rowptr, col) + values
+
+
 class PreparedAdjacency:
     """A + I of a whole matrix on the device (CSR, fp64 values), its row sums = degrees, and whether A is symmetric --
     everything about a graph that does not depend on r / alpha (sgl_norm_build_symcheck).  One preparation serves every
@@ -610,7 +641,10 @@ class PreparedAdjacency:
             check(lib().sgl_norm_build_symcheck(n, nnz, ptr(rowptr), ptr(col), ptr(val), m, ptr(self.rowptr), ptr(self.col),
                                                 ptr(self.t64), ptr(self.deg), ptr(fp), current_stream_ptr()),
                   "sgl_norm_build_symcheck")
-            self.symmetric = int(fp.item()) == 0
+            # one read-back for both answers: is A symmetric, and can an entry of A_hat be exactly 0 (see _all_positive)
+            ok = val.min() > 0 if nnz else torch.ones((), dtype=torch.bool, device=dev)
+            asym, ok = torch.stack([fp[0] != 0, ok]).tolist()
+            self.symmetric, self.may_hold_zero = not asym, not ok
         self.nnz_out = m
         self.device = dev
         if self.symmetric:
@@ -646,8 +680,10 @@ class PreparedAdjacency:
         dev = self.device
         with torch.cuda.device(dev):
             if self.symmetric:
-                vals = _scaled_values(self, self.n, 0, self.rowptr, self.col, self.t64, self.deg, r, alpha, return_fp64, host_pow)
-                return (self.rowptr, self.col) + vals
+                prune = self.may_hold_zero or alpha == 1.0
+                vals = _scaled_values(self, self.n, 0, self.rowptr, self.col, self.t64, self.deg, r, alpha, return_fp64 or prune,
+                                      host_pow)
+                return _reference_pattern(prune, return_fp64, self.rowptr, self.col, vals)
             # directed / value-asymmetric A: A_hat[j, i] = (T'[j, i] L[j]) R[i] with T = A^T.  The transposition (one stable sort:
             # sgl_coo_to_csr with rows and columns swapped) does not depend on (r, alpha) either: done ONCE, after which every
             # (r, alpha) is the same single pass as in the symmetric case -- 2 ms instead of the 21 ms of the general pipeline
@@ -717,7 +753,9 @@ def normalize_adj(rowptr, col, val, n, r, alpha=None, return_fp64=False, host_po
     rowptr int64 [n+1], col int32, val float32 (CUDA).  Returns (rowptr, col, val[, val64]).
     host_pow (default): the two degree powers are evaluated by the host's numpy like the reference's, everything per
     non-zero stays on the GPU; the rounded A_hat is then bit-identical to scipy's.  `prepared`: a PreparedAdjacency of the
-    same matrix (re-used across r / alpha); host_pow=False is the all-device pipeline with the GPU's pow()."""
+    same matrix (re-used across r / alpha); host_pow=False is the all-device pipeline with the GPU's pow().
+    The pattern is the reference's on every route: entries that come out exactly 0 (stored zeros of A, a_ii = -1, a degree of
+    0) are not returned, as scipy does not store them (_drop_exact_zeros; graphs of positive weights never get there)."""
     _lib.require_gpu()
     if host_pow or prepared is not None:
         prep = prepared if prepared is not None else PreparedAdjacency(rowptr, col, val, n)
@@ -732,11 +770,13 @@ def normalize_adj(rowptr, col, val, n, r, alpha=None, return_fp64=False, host_po
         o_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
         o_col = torch.empty(m, dtype=torch.int32, device=dev)
         o_val = torch.empty(m, dtype=torch.float32, device=dev)
-        o_v64 = torch.empty(m, dtype=torch.float64, device=dev) if return_fp64 else None
+        prune = not _all_positive(val) or alpha == 1.0
+        o_v64 = torch.empty(m, dtype=torch.float64, device=dev) if (return_fp64 or prune) else None
         check(lib().sgl_norm_execute(n, nnz, ptr(rowptr), ptr(col), ptr(val), float(r), int(alpha is not None),
                                      float(alpha if alpha is not None else 0.0), m, ptr(o_ptr), ptr(o_col), ptr(o_val),
-                                     ptr(o_v64) if return_fp64 else None, current_stream_ptr()), "sgl_norm_execute")
-    return (o_ptr, o_col, o_val, o_v64) if return_fp64 else (o_ptr, o_col, o_val)
+                                     ptr(o_v64) if o_v64 is not None else None, current_stream_ptr()), "sgl_norm_execute")
+        # the C entry point keeps the union pattern of A and I; the reference's pattern is this layer's business
+        return _reference_pattern(prune, return_fp64, o_ptr, o_col, (o_val, o_v64) if o_v64 is not None else (o_val,))
 
 
 class PreparedBlock:
@@ -786,6 +826,7 @@ class PreparedBlock:
                       "sgl_norm_block_colsum")
                 if multi:
                     dist.all_reduce(deg, group=group)
+            self.may_hold_zero = not _all_positive(val, deg)
         self.deg = deg
         self.nnz_out = m
         self._hat64 = None
@@ -793,9 +834,10 @@ class PreparedBlock:
     def normalize(self, r, alpha=None, return_fp64=False, host_pow=True, keep_hat64=None):
         """(rowptr, col, val[, val64]) of this block of A_hat (local row pointers, global column ids)"""
         with torch.cuda.device(self.rowptr.device):
-            vals = _scaled_values(self, self.n_local, self.row0, self.rowptr, self.col, self.t64, self.deg, r, alpha, return_fp64,
-                                  host_pow, keep_hat64)
-        return (self.rowptr, self.col) + vals
+            prune = self.may_hold_zero or alpha == 1.0
+            vals = _scaled_values(self, self.n_local, self.row0, self.rowptr, self.col, self.t64, self.deg, r, alpha,
+                                  return_fp64 or prune, host_pow, keep_hat64)
+            return _reference_pattern(prune, return_fp64, self.rowptr, self.col, vals)
 
     def drop_values(self):
         """release the cached fp64 Laplacian (8 bytes per non-zero)"""

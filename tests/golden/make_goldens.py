@@ -19,6 +19,8 @@ Fixture families:
   g10_label_reuse.npz BASELINE config 3: the label use / reuse loop around preprocess, through the reference's task code
   g9_config5.npz BASELINE config 5 at its own hop count: PPR / Laplacian k = 10, every MessageOp over H = 11 hops (d = 16, 128)
   g13_ref_spmm.npz one SpMM through the reference's own compiled kernel (oracle/_ref/libmatmul.so) on three normalised graphs
+  g14_link_prediction.npz (make_g14_link_prediction.py) the NAFS link-prediction task's logits and ranking metrics
+  g15_norm_edges.npz (make_g15_norm_edges.py) normalisation and propagation of stored zeros, a_ii = -1, zero and negative degrees
 Dense inputs are regenerated from tests/golden/inputs.py (integer hash), not stored.
 """
 import importlib.util

@@ -30,6 +30,51 @@ def test_g1_normalisation_matches_reference(goldens, gname):
         assert np.array_equal(val.astype(np.float32), ref.astype(np.float32)), key
 
 
+G15_VARIANTS = G1_VARIANTS + [("ppr", 0.5, 1.0)]
+
+
+def _g15_key(gname, kind, r, a):
+    return f"{gname}|{kind}|{r}" + ("" if a is None else f"|{a}")
+
+
+@pytest.mark.parametrize("gname", ["edge48", "edge48s"])
+def test_g15_zero_cancelling_and_negative_weights_match_reference(goldens, gname):
+    """stored zeros, a_ii = -1, zero and negative degrees (tests/golden/make_g15_norm_edges.py): scipy stores no exact zero, so the
+    reference's pattern depends on (r, alpha) and is recorded per variant; NaN (the negative degree at a fractional r) sits where
+    the reference has it"""
+    g15 = goldens.npz("g15_norm_edges")
+    gp, gc, gv = g15[gname + "|indptr"], g15[gname + "|indices"], g15[gname + "|data"]
+    assert (gv == 0).sum() >= 4                                    # the fixture's stored zeros reach the oracle
+    n = len(gp) - 1
+    for kind, r, a in G15_VARIANTS:
+        key = _g15_key(gname, kind, r, a)
+        ptr, col, val = oracle.sym_norm_csr(gp, gc, gv, n, r, a)
+        assert np.array_equal(ptr, g15[key + "|indptr"]), key
+        assert np.array_equal(col, g15[key + "|indices"]), key
+        ref = g15[key + "|data"]
+        assert np.array_equal(np.isnan(val), np.isnan(ref)), key
+        assert np.isnan(ref).any() == (r in (0.3, 0.5)), key
+        assert np.allclose(val, ref, rtol=5e-16, atol=0, equal_nan=True), key
+        assert np.array_equal(val.astype(np.float32), ref.astype(np.float32), equal_nan=True), key
+
+
+@pytest.mark.parametrize("gname", ["edge48", "edge48s"])
+def test_g15_propagate_matches_recorded_hops(goldens, gname):
+    """GraphOp.propagate over those matrices, on a finite x and on one with inf in rows that others reach only through a zero
+    weight or a zero degree factor: every hop equal to the reference's, NaN and inf included"""
+    g15 = goldens.npz("g15_norm_edges")
+    gp, gc, gv = g15[gname + "|indptr"], g15[gname + "|indices"], g15[gname + "|data"]
+    n = len(gp) - 1
+    for kind, r, a in (("lap", 0.5, None), ("ppr", 0.5, 0.15)):
+        norm = oracle.sym_norm_csr(gp, gc, gv, n, r, a)
+        for xname in ("fin", "inf"):
+            feats = oracle.propagate(norm, g15["x_" + xname], 2)
+            for h in (1, 2):
+                want = g15[f"{_g15_key(gname, kind, r, a)}|{xname}|h{h}"]
+                assert np.array_equal(feats[h], want, equal_nan=True), (gname, kind, xname, h)
+                assert not np.isfinite(want).all()               # the negative degree reaches every recorded hop
+
+
 def _g2_cases(goldens):
     return goldens.json("g2_prop")
 
