@@ -69,6 +69,25 @@ int build_plan(Plan &plan, const int64_t *rowptr, int64_t n_rows, int32_t item_n
 // tuning knobs (sgl_set_tuning)
 int64_t tuning(const char *key, int64_t dflt);
 
+// what sgl_csr_create takes for item_nnz <= 0 / long_row_nnz == 0: functions of the matrix's nnz only (sgl_core.cpp)
+int32_t default_item_nnz(int64_t nnz);
+int32_t default_long_row_nnz(int64_t nnz);
+
+// ---- SpMM launch rule (host, sgl_core.cpp): one rule for the fp32 and the bfloat16 kernel --------------------
+struct SpmmLayout {
+    int group, nch, ulevel, waves;   // lanes per feature row (R = 64 / group non-zero slots) x column chunks per lane; level of unroll_of; wavefronts per workgroup
+    bool nt;                         // non-temporal CSR stream / Y stores (fp32 only)
+};
+// `lanes` = columns of the slice / elements per lane; reads the tuning keys spmm_group, spmm_unroll, spmm_nt, spmm_waves
+SpmmLayout spmm_layout(int lanes, bool strict, int64_t nnz, int64_t n_rows, bool bf16);
+
+// gathers in flight per lane (the template argument U of spmm_kernel / spmm_bf16_kernel), scaled down with the number of column
+// chunks to bound registers.  Level 3 (32 in flight, one-row-per-step layout only) is compiled for fp32 alone.
+constexpr int unroll_of(int group, int nch, int ulevel) {
+    const int uh = (nch == 1) ? 8 : (nch == 2 ? 4 : 2);
+    return ulevel == 2 ? uh * 2 / (nch == 1 ? 1 : 2) : ulevel == 3 ? ((nch == 1 && group == 64) ? 32 : uh) : ulevel == 0 ? uh / 2 : uh;
+}
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // A HIP launch carries at most 2^32 - 1 threads per grid dimension; beyond that the launch is silently truncated on this
@@ -78,6 +97,8 @@ inline bool launch_fits(int64_t blocks, int64_t threads_per_block) {
 }
 
 }  // namespace sgl
+
+inline bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 struct sgl_plan {
     sgl::Plan p;

@@ -1,4 +1,4 @@
-// Host-only part of libsgl_hip.so: error text, tuning knobs, and the SpMM execution-plan builder.
+// Host-only part of libsgl_hip.so: error text, tuning knobs, the SpMM launch rule and the SpMM execution-plan builder.
 // No device code here, so these entry points work (and are unit-tested) on a machine without a GPU.
 #include <algorithm>
 #include <atomic>
@@ -54,6 +54,73 @@ int64_t tuning(const char *key, int64_t dflt) {
     auto it = m.find(key);
     if (it == m.end()) return dflt;
     return it->second;
+}
+
+// One wavefront per item: small matrices get smaller items so that the chip (256 CUs x 4 SIMDs x 8 waves) still
+// sees enough wavefronts to hide memory latency; large ones use the 512-nnz default.  In between -- a launch of fewer
+// than ~200 000 such items, e.g. a rank's block of a sharded job: a few "rounds" of the 8 192 resident wavefronts --
+// 256-nnz items end the launch more evenly (profiles/r03_probe_small_launch.log: -3 % at an eighth of the
+// products-sized graph, neutral on the whole of it).  Results do not depend on the item size.
+int32_t default_item_nnz(int64_t nnz) {
+    const int64_t want_items = 256 * 4 * 8;
+    const int64_t cap = nnz >= kSmallLaunchNnz ? kDefaultItemNnz : kDefaultItemNnz / 2;
+    return (int32_t)std::min<int64_t>(cap, std::max<int64_t>(16, nnz / want_items));
+}
+
+// Where a row is cut into pieces.  A row is ONE sequential chain of gathers in one wavefront; on a small matrix the whole
+// launch is only a few such chains long, so its longest row IS the launch (Pubmed-sized S0: a 171-nnz hub row of 2 KB gathers
+// took 62 us per hop whatever the item size; cut at 32 non-zeros the hop takes 44 us, 0.52 -> 0.73 of the roofline,
+// profiles/r04_small_graph_sweep.log).  The threshold depends on the matrix (its nnz) only -- never on the plan -- so any two
+// plans of one matrix still cut the same rows at the same places and agree bit for bit; strict order never cuts.
+int32_t default_long_row_nnz(int64_t nnz) {
+    return nnz < (1 << 18) ? 32 : nnz < (1 << 20) ? 128 : nnz < (1 << 22) ? 512 : kDefaultLongRowNnz;
+}
+
+SpmmLayout spmm_layout(int lanes, bool strict, int64_t nnz, int64_t n_rows, bool bf16) {
+    SpmmLayout L;
+    // Lane layout (measured on MI355X, profiles/r01_sweep*.log): rows wider than 16 lanes (64 floats) are gathered one
+    // non-zero per step by the whole wavefront (R = 1): as fast as two half-wave slots and it keeps the reference's
+    // sequential fmaf order; narrower rows (bf16: d <= 128 with 16-byte lanes, the d = 100 hop is 13 lanes) pack
+    // R = 64/GROUP non-zeros per step or the lanes would idle.  Rows wider than 64 lanes go in column chunks; strict
+    // order always walks one non-zero per step.
+    L.group = 64;
+    L.nch = 1;
+    if (lanes > 64) {
+        const int need = (lanes + 63) / 64;
+        L.nch = need <= 2 ? need : 4;
+    } else if (!strict && lanes <= 16) {
+        L.group = 8;
+        while (L.group < lanes) L.group <<= 1;
+    }
+    const int64_t forced = tuning("spmm_group", 0);   // strict order keeps its one chain per row whatever the key says
+    if (!strict && (forced == 8 || forced == 16 || forced == 32 || forced == 64) && L.nch == 1 && forced >= lanes) L.group = (int)forced;
+    // gathers in flight per lane: 16 for the one-row-per-step layout, 8 for the packed ones (0 = this default).  A row's
+    // remainder (nnz mod U) is gathered one dependent load at a time, so short rows want smaller batches: measured
+    // (profiles/r02_flat_*.log) 51 nnz/row: U=16 8.73 ms vs U=8 8.79; 30 nnz/row (papers100M-shaped shard): U=8 37.2 ms
+    // vs U=16 38.1; 6 nnz/row: U=4 11.27 vs U=8 11.36 vs U=16 13.9.  (A walk that batches across row ends was measured
+    // too: within 1 % of this one with the right U, 2-4 % slower for d = 147 and in strict order -- not kept.)
+    // bf16: the packed layouts take 16 per slot too from 40 non-zeros per row on (products shape, d = 100 at a 128-element
+    // pitch: 4.47 ms per hop against 4.58 with 8 and 4.56 with 4, profiles/bf16_hop_dtype_unroll.json), 8 below.
+    const bool whole_wave = L.group == 64 && L.nch == 1;
+    L.ulevel = whole_wave ? 2 : 1;
+    if (L.nch == 1 && n_rows > 0) {
+        const double avg = (double)nnz / (double)n_rows;
+        if (whole_wave) {
+            if (avg < 12.0) L.ulevel = 0;
+            else if (avg < 40.0) L.ulevel = 1;
+        } else {
+            L.ulevel = bf16 ? (avg >= 40.0 ? 2 : 1) : 1;
+        }
+    }
+    const int64_t un = tuning("spmm_unroll", 0);
+    if (un == 1) L.ulevel = 0;
+    if (un == 2) L.ulevel = 2;
+    if (un == 3) L.ulevel = 1;
+    if (un == 4) L.ulevel = bf16 ? L.ulevel : 3;   // 32 gathers in flight (one-row-per-step layout only): fp32 alone compiles it
+    L.nt = bf16 ? false : tuning("spmm_nt", 0) != 0;   // the bf16 kernel has no non-temporal variant
+    L.waves = (int)tuning("spmm_waves", 0);
+    if (L.waves != 1 && L.waves != 2 && L.waves != 4) L.waves = 4;
+    return L;
 }
 
 // Issue order of the work items.  An item closes when it reaches item_nnz non-zeros, so one that ends in a heavy row holds up

@@ -1,5 +1,6 @@
-// The device CSR handle behind sgl_csr_t (include/sgl_hip.h), shared by the translation units that launch SpMM kernels on it
-// (sgl_spmm.hip: fp32 hops, sgl_spmm_bf16.hip: bfloat16 hops).  Not part of the ABI.
+// The device CSR handle behind sgl_csr_t (include/sgl_hip.h): made, changed and destroyed in sgl_csr.hip, used by the translation
+// units that launch SpMM kernels on it (sgl_spmm.hip: fp32 hops, sgl_spmm_bf16.hip: bfloat16 hops; what the two share is in
+// sgl_spmm_common.h).  Not part of the ABI.
 #pragma once
 #include "sgl_common.h"
 

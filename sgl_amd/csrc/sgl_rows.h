@@ -160,8 +160,6 @@ __device__ __forceinline__ void store_row(float *__restrict__ orow, const f4 (&a
     }
 }
 
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 int pick_lpr(int64_t d, int vec) {
     const int64_t lanes = (d + vec - 1) / vec;
     int lpr = 8;

@@ -18,7 +18,7 @@
 //   * U independent gathers are kept in flight per lane (memory-level parallelism), x up to 8 waves per SIMD;
 //   * block -> item mapping is XCD-aware: each of the 8 XCDs walks its own contiguous range of rows, so rows that
 //     share neighbours (and the CSR stream) stay in one XCD's L2.
-#include "sgl_csr.h"
+#include "sgl_spmm_common.h"
 
 namespace {
 
@@ -85,19 +85,6 @@ __device__ __forceinline__ void st_stream(T *p, const T &v) {
         *p = v;
 }
 
-// broadcast element `idx` (0..63) of a wave-distributed register to this lane
-template <int R>
-__device__ __forceinline__ int bcast_i(int v, int idx) {
-    if constexpr (R == 1)
-        return __builtin_amdgcn_readlane(v, idx);  // idx is wave-uniform -> SGPR result
-    else
-        return __builtin_amdgcn_ds_bpermute(idx << 2, v);
-}
-template <int R>
-__device__ __forceinline__ float bcast_f(float v, int idx) {
-    return __int_as_float(bcast_i<R>(__float_as_int(v), idx));
-}
-
 struct SpmmArgs {
     const int32_t *items;       // (row_begin,row_end) pairs
     const sgl::Piece *pieces;   // long-row pieces
@@ -109,7 +96,7 @@ struct SpmmArgs {
     float *partial;
     int64_t ldx, ldy, ldp;
     int32_t n_items, n_pieces, d, accumulate;
-    int32_t piece_blocks, item_blocks_per_xcd, xcd_remap, waves;
+    BlockMap map;
     // optional fused epilogue  Y = clamp(alpha * (A X) + res, lo, hi)   (label propagation / C&S step,
     // reference: sgl/tricks/utils.py:55-56); epi == 0 -> plain store
     const float *res;
@@ -136,26 +123,17 @@ struct MultiOut {
 };
 
 struct Epilogue {
-    const float *res;   // row pointer already applied by the caller (may be nullptr)
-    float alpha, lo, hi;
-    int on;
-    // running aggregate over hops, updated where the row is produced (Sum / Mean / SimpleWeighted MessageOps without a
-    // second pass over the hop matrices): acc_mode 1: ACC += Y, 2: ACC += w * Y (rounded product, then add: the order of
-    // hop_reduce_kernel), 3: ACC = max(ACC, Y) (+8: min), +4: ACC /= acc_div afterwards (Mean's one true division, on the
-    // last hop).  Y itself is stored unchanged: it is the next hop's input.
-    float *acc;         // row pointer already applied (nullptr = off)
-    int64_t ldacc;
-    float acc_w, acc_div;
-    int acc_mode;
+    const float *res = nullptr;   // row pointer already applied by the caller (may be nullptr)
+    float alpha = 1.f, lo = 0.f, hi = 0.f;
+    int on = 0;
+    // running aggregate over hops (acc_apply, sgl_spmm_common.h)
+    float *acc = nullptr;         // row pointer already applied (nullptr = off)
+    int64_t ldacc = 0;
+    float acc_w = 1.f, acc_div = 1.f;
+    int acc_mode = 0;
 };
 
-__device__ __forceinline__ float acc_apply(float a, float y, const Epilogue &e) {
-    if ((e.acc_mode & 3) == 3)   // running extremum with torch's NaN rule (a NaN in any hop wins), +8: min instead of max
-        return (e.acc_mode & 8) ? ((y < a || y != y) ? y : a) : ((y > a || y != y) ? y : a);
-    a = ((e.acc_mode & 3) == 2) ? __fadd_rn(a, __fmul_rn(y, e.acc_w)) : __fadd_rn(a, y);
-    if (e.acc_mode & 4) a = __fdiv_rn(a, e.acc_div);
-    return a;
-}
+__device__ __forceinline__ float acc_apply(float a, float y, const Epilogue &e) { return acc_apply(a, y, e.acc_mode, e.acc_w, e.acc_div); }
 
 __device__ __forceinline__ float epi_apply(float v, float r, const Epilogue &e, bool has_res) {
     float t = __fmul_rn(e.alpha, v);          // alpha * spmm(...)   (rounded product, then rounded add: torch order)
@@ -165,15 +143,7 @@ __device__ __forceinline__ float epi_apply(float v, float r, const Epilogue &e, 
 
 // One wavefront walks `nrows` consecutive rows whose non-zeros are colb/valb[0 .. tot) ; lane i of `my_rel`
 // holds the offset of row i's first non-zero (lane nrows holds tot).
-// Row map (sgl_csr_set_rowmap): the CSR's rows are stored in PROCESSING order (a locality ordering found at plan time), row i
-// of the storage is row my_map[i] of the product.  Only the output side is indirect -- Y, the residual and the running
-// aggregate are addressed with the mapped index from un-offset base pointers; the gathers use the original column ids, and a
-// row's terms are added in their original order, so the result is bit-identical to the unpermuted matrix's.
-struct RowMap {
-    int my_map = 0;      // lane i: output row of the item's row i
-    bool on = false;
-};
-
+// Under a row map (RowMap, sgl_spmm_common.h) `out`, the residual and the running aggregate are un-offset base pointers.
 template <int VEC, int GROUP, int NCH, int U, bool NT, bool MULTI>
 __device__ __forceinline__ void run_rows(const int32_t *__restrict__ colb, const float *__restrict__ valb,
                                          const int my_rel, const int nrows, const int tot,
@@ -331,41 +301,26 @@ __global__ __launch_bounds__(256) void spmm_kernel(const SpmmArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.x;
-    if (b < a.piece_blocks) {
-        const int p = b * a.waves + wave;
+    if (b < a.map.piece_blocks) {
+        const int p = b * a.map.waves + wave;
         if (p >= a.n_pieces) return;
         const sgl::Piece pc = a.pieces[p];
         const int my_rel = (lane == 0) ? 0 : pc.len;
-        Epilogue none;
-        none.res = nullptr;
-        none.alpha = 1.f;
-        none.lo = none.hi = 0.f;
-        none.on = 0;   // pieces hold partial sums: the epilogue runs in the fix-up kernel
-        none.acc = nullptr;
-        none.ldacc = 0;
-        none.acc_w = none.acc_div = 1.f;
-        none.acc_mode = 0;
+        const Epilogue none;   // pieces hold partial sums: the epilogue runs in the fix-up kernel
         MultiOut solo;
         solo.n = 0;
         solo.mask = nullptr;
         run_rows<VEC, GROUP, NCH, U, NT, false>(a.col + pc.begin, a.val + pc.begin, my_rel, 1, pc.len, a.x, a.ldx,
                                          a.partial + (int64_t)p * a.ldp, a.ldp, a.d, false, lane, none, 0, solo);
     } else {
-        int ib = b - a.piece_blocks;
-        if (a.xcd_remap) ib = (ib & 7) * a.item_blocks_per_xcd + (ib >> 3);
-        const int item = ib * a.waves + wave;
+        int ib = b - a.map.piece_blocks;
+        if (a.map.xcd_remap) ib = xcd_block(ib, a.map.item_blocks_per_xcd);
+        const int item = ib * a.map.waves + wave;
         if (item >= a.n_items) return;
         const int row_begin = a.items[2 * item], row_end = a.items[2 * item + 1];
         const int nrows = row_end - row_begin;
-        const int64_t rp = a.rowptr[(int64_t)row_begin + min(lane, nrows)];
-        const int lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)rp);
-        const int hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)rp >> 32));
-        const int64_t base = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-        const int my_rel = (int)(rp - base);
-        const int tot = __builtin_amdgcn_readlane(my_rel, nrows);
-        RowMap rm;
-        rm.on = a.rowmap != nullptr;            // then the output-side pointers stay un-offset: rows are addressed through the map
-        rm.my_map = rm.on ? a.rowmap[(int64_t)row_begin + max(min(lane, nrows - 1), 0)] : 0;
+        const ItemWindow w = item_window(a.rowptr, row_begin, nrows, lane);
+        const RowMap rm = item_rowmap(a.rowmap, row_begin, nrows, lane);
         const int64_t first = rm.on ? 0 : row_begin;
         Epilogue epi;
         epi.res = a.res ? a.res + first * a.ldres : nullptr;
@@ -383,7 +338,7 @@ __global__ __launch_bounds__(256) void spmm_kernel(const SpmmArgs a) {
         mo.mask = (MULTI && a.row_mask) ? a.row_mask + row_begin : nullptr;
 #pragma unroll
         for (int q = 0; q < 7; ++q) mo.p[q] = (MULTI && q < a.n_more) ? a.y_more[q] + (int64_t)row_begin * a.ldy : nullptr;
-        run_rows<VEC, GROUP, NCH, U, NT, MULTI>(a.col + base, a.val + base, my_rel, nrows, tot, a.x, a.ldx,
+        run_rows<VEC, GROUP, NCH, U, NT, MULTI>(a.col + w.base, a.val + w.base, w.my_rel, nrows, w.tot, a.x, a.ldx,
                                          a.y + first * a.ldy, a.ldy, a.d, a.accumulate != 0, lane, epi,
                                          a.ldres, mo, rm);
     }
@@ -420,9 +375,9 @@ __global__ __launch_bounds__(256) void spmm_fixup_kernel(const int32_t *__restri
 template <int VEC, int GROUP, int NCH, int U, bool NT>
 hipError_t launch_variant(const SpmmArgs &a, int grid, hipStream_t st) {
     if (a.n_more > 0)
-        hipLaunchKernelGGL((spmm_kernel<VEC, GROUP, NCH, U, NT, true>), dim3(grid), dim3(64 * a.waves), 0, st, a);
+        hipLaunchKernelGGL((spmm_kernel<VEC, GROUP, NCH, U, NT, true>), dim3(grid), dim3(64 * a.map.waves), 0, st, a);
     else
-        hipLaunchKernelGGL((spmm_kernel<VEC, GROUP, NCH, U, NT, false>), dim3(grid), dim3(64 * a.waves), 0, st, a);
+        hipLaunchKernelGGL((spmm_kernel<VEC, GROUP, NCH, U, NT, false>), dim3(grid), dim3(64 * a.map.waves), 0, st, a);
     return hipGetLastError();
 }
 
@@ -434,12 +389,11 @@ hipError_t launch_nt(const SpmmArgs &a, int grid, hipStream_t st, bool nt) {
 
 template <int VEC, int GROUP, int NCH>
 hipError_t launch_u(const SpmmArgs &a, int grid, hipStream_t st, bool nt, int ulevel) {
-    // gathers in flight per lane, scaled down with the number of column chunks to bound registers
-    constexpr int UH = (NCH == 1) ? 8 : (NCH == 2 ? 4 : 2);
-    constexpr int UL = UH / 2;
-    if (ulevel == 2) return launch_nt<VEC, GROUP, NCH, UH * 2 / (NCH == 1 ? 1 : 2)>(a, grid, st, nt);
-    if (ulevel == 3) return launch_nt<VEC, GROUP, NCH, (NCH == 1 && GROUP == 64) ? 32 : UH>(a, grid, st, nt);
-    return ulevel == 0 ? launch_nt<VEC, GROUP, NCH, UL>(a, grid, st, nt) : launch_nt<VEC, GROUP, NCH, UH>(a, grid, st, nt);
+    using sgl::unroll_of;
+    if (ulevel == 2) return launch_nt<VEC, GROUP, NCH, unroll_of(GROUP, NCH, 2)>(a, grid, st, nt);
+    if (ulevel == 3) return launch_nt<VEC, GROUP, NCH, unroll_of(GROUP, NCH, 3)>(a, grid, st, nt);
+    return ulevel == 0 ? launch_nt<VEC, GROUP, NCH, unroll_of(GROUP, NCH, 0)>(a, grid, st, nt)
+                       : launch_nt<VEC, GROUP, NCH, unroll_of(GROUP, NCH, 1)>(a, grid, st, nt);
 }
 
 template <int VEC>
@@ -461,231 +415,6 @@ hipError_t launch_group(const SpmmArgs &a, int grid, hipStream_t st, bool nt, in
 }
 
 }  // namespace
-
-// permutation check of a row map on the device: every entry in range, no output row named twice
-__global__ __launch_bounds__(256) void rowmap_check_kernel(const int32_t *__restrict__ map, const int64_t n, unsigned *__restrict__ seen,
-                                                           int *__restrict__ bad) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t m = map[i];
-    if (m < 0 || m >= n) {
-        atomicOr(bad, 1);
-        return;
-    }
-    const unsigned bit = 1u << (m & 31);
-    if (atomicOr(&seen[m >> 5], bit) & bit) atomicOr(bad, 2);
-}
-
-// The row pointers come to the host for the plan (sgl::build_plan).  Small ones in one copy; the 10^7 ... 10^8 rows of a
-// papers100M-sized block (up to 888 MB) through two page-locked 32 MB staging buffers, the copy of chunk c + 1 in flight while
-// chunk c is unpacked -- a pageable destination of that size is staged by the runtime at a fraction of the link rate -- and the
-// host waits on the chunks' EVENTS, not on the stream: work the caller queued behind this call on other streams is not held up.
-static int fetch_rowptr(std::vector<int64_t> &h, const int64_t *d, hipStream_t st) {
-    const size_t n = h.size();
-    constexpr size_t kChunk = (size_t)4 << 20;                        // elements: 32 MB
-    if (n <= 2 * kChunk) {
-        SGL_HIP_CHECK(hipMemcpyAsync(h.data(), d, n * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        SGL_HIP_CHECK(hipStreamSynchronize(st));
-        return SGL_OK;
-    }
-    int64_t *stage[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    int rc = SGL_OK;
-    auto cleanup = [&]() {
-        for (int i = 0; i < 2; ++i) {
-            if (stage[i]) (void)hipHostFree(stage[i]);
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    };
-    for (int i = 0; i < 2 && rc == SGL_OK; ++i) {
-        if (hipHostMalloc((void **)&stage[i], kChunk * sizeof(int64_t), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess)
-            rc = sgl::fail(SGL_ERR_ALLOC, "sgl_csr_create: no page-locked staging buffer for the row pointers");
-    }
-    const size_t n_chunks = (n + kChunk - 1) / kChunk;
-    auto issue = [&](size_t c) -> hipError_t {
-        const size_t off = c * kChunk, len = std::min(kChunk, n - off);
-        hipError_t e = hipMemcpyAsync(stage[c & 1], d + off, len * sizeof(int64_t), hipMemcpyDeviceToHost, st);
-        return e != hipSuccess ? e : hipEventRecord(ev[c & 1], st);
-    };
-    if (rc == SGL_OK && issue(0) != hipSuccess) rc = sgl::fail(SGL_ERR_INVALID, "sgl_csr_create: copying the row pointers failed");
-    for (size_t c = 0; c < n_chunks && rc == SGL_OK; ++c) {
-        if (hipEventSynchronize(ev[c & 1]) != hipSuccess) {
-            rc = sgl::fail(SGL_ERR_INVALID, "sgl_csr_create: copying the row pointers failed");
-            break;
-        }
-        const size_t off = c * kChunk, len = std::min(kChunk, n - off);
-        // chunk c sits in stage[c & 1]; chunk c + 1 goes to the other buffer, whose contents (chunk c - 1) were unpacked in the last round
-        if (c + 1 < n_chunks && issue(c + 1) != hipSuccess) {
-            rc = sgl::fail(SGL_ERR_INVALID, "sgl_csr_create: copying the row pointers failed");
-            break;
-        }
-        memcpy(h.data() + off, stage[c & 1], len * sizeof(int64_t));
-    }
-    if (rc != SGL_OK) (void)hipStreamSynchronize(st);                   // nothing may still write into the buffers we free
-    cleanup();
-    return rc;
-}
-
-SGL_EXPORT int sgl_csr_create(sgl_csr_t **out, int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *d_rowptr,
-                              const int32_t *d_col, const float *d_val, uint32_t flags, int32_t item_nnz,
-                              int32_t long_row_nnz, void *stream) {
-    if (!out) return sgl::fail(SGL_ERR_INVALID, "sgl_csr_create: NULL out");
-    *out = nullptr;
-    SGL_REQUIRE(n_rows >= 0 && n_cols >= 0 && nnz >= 0, "sgl_csr_create: negative size");
-    SGL_REQUIRE(n_rows < INT32_MAX && n_cols < INT32_MAX, "sgl_csr_create: n_rows/n_cols must be < 2^31 (int32 ids)");
-    SGL_REQUIRE(d_rowptr != nullptr, "sgl_csr_create: NULL row pointers");
-    SGL_REQUIRE(nnz == 0 || (d_col && d_val), "sgl_csr_create: NULL col/val with nnz > 0");
-    hipStream_t st = sgl::as_stream(stream);
-    std::vector<int64_t> h_rowptr((size_t)n_rows + 1);
-    {
-        const int rc_fetch = fetch_rowptr(h_rowptr, d_rowptr, st);
-        if (rc_fetch != SGL_OK) return rc_fetch;
-    }
-    SGL_REQUIRE(h_rowptr[0] == 0 && h_rowptr[n_rows] == nnz, "sgl_csr_create: rowptr[0]=%lld rowptr[n]=%lld but nnz=%lld",
-                (long long)h_rowptr[0], (long long)h_rowptr[n_rows], (long long)nnz);
-    if (item_nnz <= 0) {
-        // one wavefront per item: small matrices get smaller items so that the chip (256 CUs x 4 SIMDs x 8 waves) still
-        // sees enough wavefronts to hide memory latency; large ones use the 512-nnz default.  In between -- a launch of fewer
-        // than ~200 000 such items, e.g. a rank's block of a sharded job: a few "rounds" of the 8 192 resident wavefronts --
-        // 256-nnz items end the launch more evenly (profiles/r03_probe_small_launch.log: -3 % at an eighth of the
-        // products-sized graph, neutral on the whole of it).  Results do not depend on the item size.
-        const int64_t want_items = 256 * 4 * 8;
-        const int64_t cap = nnz >= sgl::kSmallLaunchNnz ? sgl::kDefaultItemNnz : sgl::kDefaultItemNnz / 2;
-        item_nnz = (int32_t)std::min<int64_t>(cap, std::max<int64_t>(16, nnz / want_items));
-    }
-    // Where a row is cut into pieces.  A row is ONE sequential chain of gathers in one wavefront; on a small matrix the whole
-    // launch is only a few such chains long, so its longest row IS the launch (Pubmed-sized S0: a 171-nnz hub row of 2 KB gathers
-    // took 62 us per hop whatever the item size; cut at 32 non-zeros the hop takes 44 us, 0.52 -> 0.73 of the roofline,
-    // profiles/r04_small_graph_sweep.log).  The threshold depends on the matrix (its nnz) only -- never on the plan -- so any two
-    // plans of one matrix still cut the same rows at the same places and agree bit for bit; strict order never cuts.
-    if (long_row_nnz == 0)
-        long_row_nnz = nnz < (1 << 18) ? 32 : nnz < (1 << 20) ? 128 : nnz < (1 << 22) ? 512 : sgl::kDefaultLongRowNnz;
-    if (flags & SGL_CSR_STRICT_ORDER) long_row_nnz = -1;
-    sgl::Plan plan;
-    int rc = sgl::build_plan(plan, h_rowptr.data(), n_rows, item_nnz, long_row_nnz);
-    if (rc != SGL_OK) return rc;
-
-    sgl_csr_t *h = new (std::nothrow) sgl_csr_t();
-    if (!h) return sgl::fail(SGL_ERR_ALLOC, "sgl_csr_create: out of memory");
-    h->n_rows = n_rows;
-    h->n_cols = n_cols;
-    h->nnz = nnz;
-    h->d_rowptr = d_rowptr;
-    h->d_col = d_col;
-    h->d_val = d_val;
-    h->flags = flags;
-    h->n_items = (int64_t)plan.items.size() / 2;
-    h->n_pieces = (int64_t)plan.pieces.size();
-    h->n_long = (int64_t)plan.long_row.size();
-    (void)hipGetDevice(&h->device);
-    auto upload = [&](void **dst, const void *src, size_t bytes) -> int {
-        if (bytes == 0) return SGL_OK;
-        SGL_HIP_CHECK(hipMalloc(dst, bytes));
-        SGL_HIP_CHECK(hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, st));
-        return SGL_OK;
-    };
-    rc = upload((void **)&h->d_items, plan.items.data(), plan.items.size() * sizeof(int32_t));
-    if (rc == SGL_OK) rc = upload((void **)&h->d_pieces, plan.pieces.data(), plan.pieces.size() * sizeof(sgl::Piece));
-    if (rc == SGL_OK) rc = upload((void **)&h->d_long_row, plan.long_row.data(), plan.long_row.size() * sizeof(int32_t));
-    if (rc == SGL_OK && h->n_long > 0)
-        rc = upload((void **)&h->d_long_first, plan.long_first.data(), plan.long_first.size() * sizeof(int32_t));
-    if (rc == SGL_OK) {
-        hipError_t e = hipStreamSynchronize(st);  // host vectors die at return
-        if (e != hipSuccess) rc = sgl::fail((int)e, "sgl_csr_create: sync failed: %s", hipGetErrorString(e));
-    }
-    if (rc != SGL_OK) {
-        sgl_csr_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return SGL_OK;
-}
-
-SGL_EXPORT int sgl_csr_destroy(sgl_csr_t *h) {
-    if (!h) return SGL_OK;
-    h->epoch->store(~0ull);                // a chain graph captured on this handle refuses to replay from now on
-    (void)hipFree(h->d_items);
-    (void)hipFree(h->d_pieces);
-    (void)hipFree(h->d_long_row);
-    (void)hipFree(h->d_long_first);
-    (void)hipFree(h->d_partial);
-    (void)hipFree(h->d_long_out);
-    for (float *p : h->retired) (void)hipFree(p);
-    delete h;
-    return SGL_OK;
-}
-
-// The handle's rows are stored in processing order: storage row i is row d_rowmap[i] of the product (a permutation of
-// 0..n_rows-1, e.g. sgl_reorder_community's order applied with sgl_csr_permute_rows).  Every product of this handle then writes
-// (and, for the epilogues, reads the residual / running aggregate of) output row d_rowmap[i]; X is gathered by the ORIGINAL
-// column ids and every row keeps the order of its terms, so results are bit-identical to the unpermuted matrix's.  NULL
-// removes the map.  The array must stay alive as long as the handle uses it.
-SGL_EXPORT int sgl_csr_set_rowmap(sgl_csr_t *h, const int32_t *d_rowmap, void *stream) {
-    if (!h) return sgl::fail(SGL_ERR_INVALID, "sgl_csr_set_rowmap: NULL handle");
-    h->d_rowmap = nullptr;
-    h->epoch->fetch_add(1);
-    if (!d_rowmap || h->n_rows == 0) return SGL_OK;
-    hipStream_t st = sgl::as_stream(stream);
-    {   // a map that is not a permutation would make every SpMM write rows out of bounds or leave rows unwritten: checked once
-        const size_t words = (size_t)(h->n_rows + 31) / 32;
-        unsigned *d_seen = nullptr;
-        SGL_HIP_CHECK(hipMalloc(&d_seen, (words + 1) * sizeof(unsigned)));
-        int *d_bad = reinterpret_cast<int *>(d_seen + words);
-        hipError_t e = hipMemsetAsync(d_seen, 0, (words + 1) * sizeof(unsigned), st);
-        int bad = 0;
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(rowmap_check_kernel, dim3((unsigned)((h->n_rows + 255) / 256)), dim3(256), 0, st, d_rowmap, h->n_rows, d_seen, d_bad);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(d_seen);
-        if (e != hipSuccess) return sgl::fail((int)e, "sgl_csr_set_rowmap: validation failed: %s", hipGetErrorString(e));
-        SGL_REQUIRE(!(bad & 1), "sgl_csr_set_rowmap: map entry outside [0, n_rows)");
-        SGL_REQUIRE(!(bad & 2), "sgl_csr_set_rowmap: the map names an output row twice (it must be a permutation)");
-    }
-    if (h->n_long > 0) {   // the split rows' fix-up writes whole output rows: give it their mapped ids
-        std::vector<int32_t> map((size_t)h->n_rows), rows((size_t)h->n_long);
-        SGL_HIP_CHECK(hipMemcpyAsync(map.data(), d_rowmap, map.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        SGL_HIP_CHECK(hipMemcpyAsync(rows.data(), h->d_long_row, rows.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        SGL_HIP_CHECK(hipStreamSynchronize(st));
-        for (auto &r : rows) {
-            SGL_REQUIRE(r >= 0 && r < h->n_rows && map[r] >= 0 && map[r] < h->n_rows, "sgl_csr_set_rowmap: map entry outside [0, n_rows)");
-            r = map[r];
-        }
-        if (!h->d_long_out) SGL_HIP_CHECK(hipMalloc(&h->d_long_out, rows.size() * sizeof(int32_t)));
-        SGL_HIP_CHECK(hipMemcpyAsync(h->d_long_out, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        SGL_HIP_CHECK(hipStreamSynchronize(st));
-    }
-    h->d_rowmap = d_rowmap;
-    return SGL_OK;
-}
-
-// Same structure, new values: the plan depends on the row pointers only, so re-weighting the matrix (another r of the
-// NAFS ensemble, another alpha of a PPR sweep: sgl/tasks/node_clustering.py:205-217) needs no new plan.
-SGL_EXPORT int sgl_csr_set_values(sgl_csr_t *h, const float *d_val) {
-    if (!h) return sgl::fail(SGL_ERR_INVALID, "sgl_csr_set_values: NULL handle");
-    SGL_REQUIRE(h->nnz == 0 || d_val, "sgl_csr_set_values: NULL values");
-    if (d_val != h->d_val) h->epoch->fetch_add(1);
-    h->d_val = d_val;
-    return SGL_OK;
-}
-
-SGL_EXPORT int sgl_csr_info(const sgl_csr_t *h, int64_t info[8]) {
-    if (!h || !info) return sgl::fail(SGL_ERR_INVALID, "sgl_csr_info: NULL");
-    info[0] = h->n_rows;
-    info[1] = h->n_cols;
-    info[2] = h->nnz;
-    info[3] = h->n_items;
-    info[4] = h->n_pieces;
-    info[5] = h->n_long;
-    info[6] = h->flags;
-    info[7] = (int64_t)(h->partial_cap * sizeof(float));
-    return SGL_OK;
-}
-
-static bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 static int pick_vec(const float *d_x, int64_t ldx, const float *d_y, int64_t ldy, int64_t d) {
     // vector width from alignment: every lane reads/writes VEC consecutive floats of a row
@@ -710,43 +439,12 @@ struct EpiHost {
 };
 
 static int spmm_slice(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, int64_t ldy, int d, int vec,
-                      int accumulate, hipStream_t st, const EpiHost &eh) {
-    const int lanes = d / vec;
-    const bool strict = (h->flags & SGL_CSR_STRICT_ORDER) != 0;
-    // Lane layout (measured on MI355X, profiles/r01_sweep*.log): rows wider than 64 floats are gathered one
-    // non-zero per step by the whole wavefront (R = 1): as fast as two half-wave slots and it keeps the reference's
-    // sequential fmaf order; narrower rows pack R = 64/GROUP non-zeros per step or the lanes would idle.
-    int group = 64, nch = 1;
-    if (lanes > 64) {
-        const int need = (lanes + 63) / 64;
-        nch = need <= 2 ? need : 4;
-    } else if (!strict && lanes <= 16) {
-        group = 8;
-        while (group < lanes) group <<= 1;
-    }
-    const int64_t forced = sgl::tuning("spmm_group", 0);   // strict order keeps its one chain per row whatever the key says
-    if (!strict && (forced == 8 || forced == 16 || forced == 32 || forced == 64)) {
-        if (nch == 1 && forced >= lanes) group = (int)forced;
-    }
-    // gathers in flight per lane: 16 for the one-row-per-step layout, 8 for the packed ones (0 = this default).  A row's
-    // remainder (nnz mod U) is gathered one dependent load at a time, so short rows want smaller batches: measured
-    // (profiles/r02_flat_*.log) 51 nnz/row: U=16 8.73 ms vs U=8 8.79; 30 nnz/row (papers100M-shaped shard): U=8 37.2 ms
-    // vs U=16 38.1; 6 nnz/row: U=4 11.27 vs U=8 11.36 vs U=16 13.9.  (A walk that batches across row ends was measured
-    // too: within 1 % of this one with the right U, 2-4 % slower for d = 147 and in strict order -- not kept.)
-    int ulevel = (group == 64 && nch == 1) ? 2 : 1;
-    if (group == 64 && nch == 1 && h->n_rows > 0) {
-        const double avg = (double)h->nnz / (double)h->n_rows;
-        if (avg < 12.0) ulevel = 0;
-        else if (avg < 40.0) ulevel = 1;
-    }
-    const int64_t un = sgl::tuning("spmm_unroll", 0);
-    if (un == 1) ulevel = 0;
-    if (un == 2) ulevel = 2;
-    if (un == 3) ulevel = 1;
-    if (un == 4) ulevel = 3;   // 32 gathers in flight (one-row-per-step layout only)
-    const bool nt = sgl::tuning("spmm_nt", 0) != 0;
-    int waves = (int)sgl::tuning("spmm_waves", 0);
-    if (waves != 1 && waves != 2 && waves != 4) waves = 4;
+                      int accumulate, hipStream_t st, const EpiHost &eh, const char *who) {
+    SpmmLaunch L;
+    int rc = spmm_launch(L, h, d / vec, d, false, who);
+    if (rc == SGL_OK) rc = grow_partial(h, L.ldp);
+    if (rc != SGL_OK) return rc;
+    if (L.grid == 0) return SGL_OK;
 
     SpmmArgs a;
     a.items = h->d_items;
@@ -758,12 +456,11 @@ static int spmm_slice(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, i
     a.y = d_y;
     a.ldx = ldx;
     a.ldy = ldy;
-    a.ldp = (d + 3) / 4 * 4;
+    a.ldp = L.ldp;
     a.n_items = (int32_t)h->n_items;
     a.n_pieces = (int32_t)h->n_pieces;
     a.d = d;
     a.accumulate = accumulate;
-    a.waves = waves;
     a.res = eh.res;
     a.ldres = eh.ldres;
     a.epi_alpha = eh.alpha;
@@ -779,40 +476,18 @@ static int spmm_slice(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, i
     a.row_mask = eh.row_mask;
     for (int q = 0; q < 7; ++q) a.y_more[q] = eh.y_more[q];
     a.rowmap = h->d_rowmap;
-    a.piece_blocks = (int32_t)((h->n_pieces + waves - 1) / waves);
-    const int64_t item_blocks = (h->n_items + waves - 1) / waves;
-    a.xcd_remap = (!(h->flags & SGL_CSR_NO_XCD_REMAP) && sgl::tuning("spmm_xcd_remap", 1) != 0) ? 1 : 0;
-    a.item_blocks_per_xcd = (int32_t)((item_blocks + 7) / 8);
-    const int64_t grid64 = a.piece_blocks + (a.xcd_remap ? (int64_t)a.item_blocks_per_xcd * 8 : item_blocks);
-    if (grid64 >= INT32_MAX) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_spmm_f32: grid too large");
-
-    if (h->n_pieces > 0) {
-        const size_t need = (size_t)h->n_pieces * (size_t)a.ldp;
-        if (need > h->partial_cap) {
-            // grow-only, and the outgrown buffer is kept until the handle dies: a ChainGraph captured earlier has its
-            // address baked in and may be replayed after a wider eager call on the same handle
-            if (h->d_partial) h->retired.push_back(h->d_partial);
-            h->d_partial = nullptr;
-            h->partial_cap = 0;
-            SGL_HIP_CHECK(hipMalloc((void **)&h->d_partial, need * sizeof(float)));
-            h->partial_cap = need;
-        }
-    }
+    a.map = L.map;
     a.partial = h->d_partial;
-    if (grid64 == 0) return SGL_OK;
     hipError_t e;
     if (vec == 4)
-        e = launch_group<4>(a, (int)grid64, st, nt, ulevel, group, nch);
+        e = launch_group<4>(a, L.grid, st, L.nt, L.ulevel, L.group, L.nch);
     else if (vec == 2)
-        e = launch_group<2>(a, (int)grid64, st, nt, ulevel, group, nch);
+        e = launch_group<2>(a, L.grid, st, L.nt, L.ulevel, L.group, L.nch);
     else
-        e = launch_group<1>(a, (int)grid64, st, nt, ulevel, group, nch);
-    if (e != hipSuccess) return sgl::fail((int)e, "sgl_spmm_f32: kernel launch failed: %s", hipGetErrorString(e));
-    if (h->n_long > 0) {
-        const int64_t fg = (int64_t)((d + 255) / 256) * h->n_long;
-        if (fg >= INT32_MAX) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_spmm_f32: fix-up grid too large");
-        Epilogue fe;
-        fe.res = nullptr;
+        e = launch_group<1>(a, L.grid, st, L.nt, L.ulevel, L.group, L.nch);
+    if (e != hipSuccess) return sgl::fail((int)e, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    if (L.fixup_grid > 0) {
+        Epilogue fe;   // (the fix-up takes the residual's base as an argument of its own)
         fe.alpha = eh.alpha;
         fe.lo = eh.lo;
         fe.hi = eh.hi;
@@ -826,11 +501,11 @@ static int spmm_slice(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, i
         fmo.n = eh.n_more;
         fmo.mask = eh.row_mask;
         for (int q = 0; q < 7; ++q) fmo.p[q] = eh.y_more[q];
-        hipLaunchKernelGGL(spmm_fixup_kernel, dim3((unsigned)fg), dim3(256), 0, st, h->d_rowmap ? h->d_long_out : h->d_long_row,
+        hipLaunchKernelGGL(spmm_fixup_kernel, dim3((unsigned)L.fixup_grid), dim3(256), 0, st, h->d_rowmap ? h->d_long_out : h->d_long_row,
                            h->d_long_first, h->d_partial, a.ldp,
                            d_y, ldy, d, accumulate, eh.res, eh.ldres, fe, fmo);
         e = hipGetLastError();
-        if (e != hipSuccess) return sgl::fail((int)e, "sgl_spmm_f32: fix-up launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return sgl::fail((int)e, "%s: fix-up launch failed: %s", who, hipGetErrorString(e));
     }
     return SGL_OK;
 }
@@ -872,7 +547,7 @@ static int spmm_impl(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, in
         if (es.res) es.res += c0;
         if (es.acc) es.acc += c0;
         for (int q = 0; q < es.n_more; ++q) es.y_more[q] += c0;
-        int rc = spmm_slice(h, d_x + c0, ldx, d_y + c0, ldy, dc, vec, accumulate, st, es);
+        int rc = spmm_slice(h, d_x + c0, ldx, d_y + c0, ldy, dc, vec, accumulate, st, es, who);
         if (rc != SGL_OK) return rc;
     }
     return SGL_OK;
@@ -983,16 +658,13 @@ SGL_EXPORT int sgl_chain_graph_destroy(sgl_graph_t *g) {
 // needs to be kept.
 SGL_EXPORT int sgl_spmm_acc_f32(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, int64_t ldy, int64_t d, float *d_acc,
                                 int64_t ldacc, float w, int mode, float divisor, void *stream) {
-    SGL_REQUIRE(d_acc != nullptr, "sgl_spmm_acc_f32: NULL accumulator");
-    SGL_REQUIRE(!(divisor == 0.f), "sgl_spmm_acc_f32: zero divisor");
-    SGL_REQUIRE(mode >= SGL_ACC_SUM && mode <= SGL_ACC_MIN, "sgl_spmm_acc_f32: unknown mode %d", mode);
-    SGL_REQUIRE(mode < SGL_ACC_MAX || divisor == 1.f, "sgl_spmm_acc_f32: max / min take no divisor");
     EpiHost eh;
+    const int rc = acc_mode_of("sgl_spmm_acc_f32", d_acc, mode, divisor, eh.acc_mode);
+    if (rc != SGL_OK) return rc;
     eh.acc = d_acc;
     eh.ldacc = ldacc;
     eh.acc_w = w;
     eh.acc_div = divisor;
-    eh.acc_mode = mode >= SGL_ACC_MAX ? (3 | (mode == SGL_ACC_MIN ? 8 : 0)) : ((mode == SGL_ACC_WSUM ? 2 : 1) | (divisor != 1.f ? 4 : 0));
     return spmm_impl(h, d_x, ldx, d_y, ldy, d, 0, stream, eh, "sgl_spmm_acc_f32");
 }
 

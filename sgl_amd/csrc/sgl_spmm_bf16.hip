@@ -11,7 +11,7 @@
 // sums stay fp32, and the finished sum is rounded ONCE to bf16, round-to-nearest-even (v_cvt_pk_bf16_f32: NaN stays NaN, +-inf
 // stays +-inf, overflow rounds to inf, subnormals are kept).  The running aggregate of sgl_spmm_acc_bf16 is fp32 and takes the
 // rounded value widened again, i.e. exactly what a later pass over the stored hop would read.
-#include "sgl_csr.h"
+#include "sgl_spmm_common.h"
 
 namespace {
 
@@ -132,35 +132,15 @@ __device__ __forceinline__ void vfma(float (&acc)[BV], float v, const typename R
     for (int e = 0; e < BV; ++e) acc[e] = __builtin_fmaf(v, xf[e], acc[e]);
 }
 
-// broadcast element `idx` (0..63) of a wave-distributed register to this lane
-template <int R>
-__device__ __forceinline__ int bcast_i(int v, int idx) {
-    if constexpr (R == 1)
-        return __builtin_amdgcn_readlane(v, idx);  // idx is wave-uniform -> SGPR result
-    else
-        return __builtin_amdgcn_ds_bpermute(idx << 2, v);
-}
-template <int R>
-__device__ __forceinline__ float bcast_f(float v, int idx) {
-    return __int_as_float(bcast_i<R>(__float_as_int(v), idx));
-}
-
-// running fp32 aggregate over hops (the modes and arithmetic of sgl_spmm_acc_f32, sgl_spmm.hip: acc_mode 1: ACC += Y, 2: ACC += w * Y
-// (rounded product, then add), 3: max (+8: min) with torch's NaN rule, +4: ACC /= acc_div afterwards)
+// running fp32 aggregate over hops: the modes and arithmetic of sgl_spmm_acc_f32 (acc_apply, sgl_spmm_common.h)
 struct AccEpi {
-    float *acc;   // nullptr = off
-    int64_t ldacc;
-    float acc_w, acc_div;
-    int acc_mode;
+    float *acc = nullptr;   // nullptr = off
+    int64_t ldacc = 0;
+    float acc_w = 1.f, acc_div = 1.f;
+    int acc_mode = 0;
 };
 
-__device__ __forceinline__ float acc_apply(float a, float y, const AccEpi &e) {
-    if ((e.acc_mode & 3) == 3)
-        return (e.acc_mode & 8) ? ((y < a || y != y) ? y : a) : ((y > a || y != y) ? y : a);
-    a = ((e.acc_mode & 3) == 2) ? __fadd_rn(a, __fmul_rn(y, e.acc_w)) : __fadd_rn(a, y);
-    if (e.acc_mode & 4) a = __fdiv_rn(a, e.acc_div);
-    return a;
-}
+__device__ __forceinline__ float acc_apply(float a, float y, const AccEpi &e) { return acc_apply(a, y, e.acc_mode, e.acc_w, e.acc_div); }
 
 struct Bf16Args {
     const int32_t *items;       // (row_begin,row_end) pairs
@@ -173,14 +153,9 @@ struct Bf16Args {
     float *partial;
     int64_t ldx, ldy, ldp;
     int32_t n_items, n_pieces, d;
-    int32_t piece_blocks, item_blocks_per_xcd, xcd_remap, waves;
+    BlockMap map;
     AccEpi epi;                 // epi.acc: matrix base
     const int32_t *rowmap;      // optional [n_rows]: storage row -> output row (sgl_csr_set_rowmap); NULL = identity
-};
-
-struct RowMap {
-    int my_map = 0;      // lane i: output row of the item's row i
-    bool on = false;
 };
 
 // One wavefront walks `nrows` consecutive rows whose non-zeros are colb/valb[0 .. tot); lane i of `my_rel` holds the offset of row
@@ -335,38 +310,27 @@ __global__ __launch_bounds__(256) void spmm_bf16_kernel(const Bf16Args a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.x;
-    if (b < a.piece_blocks) {
-        const int p = b * a.waves + wave;
+    if (b < a.map.piece_blocks) {
+        const int p = b * a.map.waves + wave;
         if (p >= a.n_pieces) return;
         const sgl::Piece pc = a.pieces[p];
         const int my_rel = (lane == 0) ? 0 : pc.len;
-        AccEpi none;     // pieces hold partial sums: rounding and the aggregate happen in the fix-up kernel
-        none.acc = nullptr;
-        none.ldacc = 0;
-        none.acc_w = none.acc_div = 1.f;
-        none.acc_mode = 0;
+        const AccEpi none;     // pieces hold partial sums: rounding and the aggregate happen in the fix-up kernel
         run_rows<BV, GROUP, NCH, U, true>(a.col + pc.begin, a.val + pc.begin, my_rel, 1, pc.len, a.x, a.ldx, nullptr,
                                           a.partial + (int64_t)p * a.ldp, a.ldp, a.d, lane, none);
     } else {
-        int ib = b - a.piece_blocks;
-        if (a.xcd_remap) ib = (ib & 7) * a.item_blocks_per_xcd + (ib >> 3);
-        const int item = ib * a.waves + wave;
+        int ib = b - a.map.piece_blocks;
+        if (a.map.xcd_remap) ib = xcd_block(ib, a.map.item_blocks_per_xcd);
+        const int item = ib * a.map.waves + wave;
         if (item >= a.n_items) return;
         const int row_begin = a.items[2 * item], row_end = a.items[2 * item + 1];
         const int nrows = row_end - row_begin;
-        const int64_t rp = a.rowptr[(int64_t)row_begin + min(lane, nrows)];
-        const int lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)rp);
-        const int hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)rp >> 32));
-        const int64_t base = (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-        const int my_rel = (int)(rp - base);
-        const int tot = __builtin_amdgcn_readlane(my_rel, nrows);
-        RowMap rm;
-        rm.on = a.rowmap != nullptr;            // then the output-side pointers stay un-offset: rows are addressed through the map
-        rm.my_map = rm.on ? a.rowmap[(int64_t)row_begin + max(min(lane, nrows - 1), 0)] : 0;
+        const ItemWindow w = item_window(a.rowptr, row_begin, nrows, lane);
+        const RowMap rm = item_rowmap(a.rowmap, row_begin, nrows, lane);
         const int64_t first = rm.on ? 0 : row_begin;
         AccEpi epi = a.epi;
         if (epi.acc) epi.acc += first * epi.ldacc;
-        run_rows<BV, GROUP, NCH, U, false>(a.col + base, a.val + base, my_rel, nrows, tot, a.x, a.ldx, a.y + first * a.ldy,
+        run_rows<BV, GROUP, NCH, U, false>(a.col + w.base, a.val + w.base, w.my_rel, nrows, w.tot, a.x, a.ldx, a.y + first * a.ldy,
                                            nullptr, a.ldy, a.d, lane, epi, rm);
     }
 }
@@ -394,17 +358,16 @@ __global__ __launch_bounds__(256) void spmm_bf16_fixup_kernel(const int32_t *__r
 
 template <int BV, int GROUP, int NCH, int U>
 hipError_t launch_variant(const Bf16Args &a, int grid, hipStream_t st) {
-    hipLaunchKernelGGL((spmm_bf16_kernel<BV, GROUP, NCH, U>), dim3(grid), dim3(64 * a.waves), 0, st, a);
+    hipLaunchKernelGGL((spmm_bf16_kernel<BV, GROUP, NCH, U>), dim3(grid), dim3(64 * a.map.waves), 0, st, a);
     return hipGetLastError();
 }
 
 template <int BV, int GROUP, int NCH>
 hipError_t launch_u(const Bf16Args &a, int grid, hipStream_t st, int ulevel) {
-    // gathers in flight per lane, scaled down with the number of column chunks to bound registers (the fp32 kernel's table)
-    constexpr int UH = (NCH == 1) ? 8 : (NCH == 2 ? 4 : 2);
-    constexpr int UL = UH / 2;
-    if (ulevel == 2) return launch_variant<BV, GROUP, NCH, UH * 2 / (NCH == 1 ? 1 : 2)>(a, grid, st);
-    return ulevel == 0 ? launch_variant<BV, GROUP, NCH, UL>(a, grid, st) : launch_variant<BV, GROUP, NCH, UH>(a, grid, st);
+    using sgl::unroll_of;
+    if (ulevel == 2) return launch_variant<BV, GROUP, NCH, unroll_of(GROUP, NCH, 2)>(a, grid, st);
+    return ulevel == 0 ? launch_variant<BV, GROUP, NCH, unroll_of(GROUP, NCH, 0)>(a, grid, st)
+                       : launch_variant<BV, GROUP, NCH, unroll_of(GROUP, NCH, 1)>(a, grid, st);
 }
 
 template <int BV>
@@ -425,8 +388,6 @@ hipError_t launch_group(const Bf16Args &a, int grid, hipStream_t st, int ulevel,
     return launch_u<BV, 64, 4>(a, grid, st, ulevel);
 }
 
-bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // lane width from alignment: every lane reads / writes BV consecutive bf16 of a row
 int pick_bv(const uint16_t *d_x, int64_t ldx, const uint16_t *d_y, int64_t ldy, int64_t d) {
     for (int bv = 8; bv > 1; bv >>= 1)
@@ -434,50 +395,13 @@ int pick_bv(const uint16_t *d_x, int64_t ldx, const uint16_t *d_y, int64_t ldy, 
     return 1;
 }
 
-struct AccHost {
-    float *acc = nullptr;
-    int64_t ldacc = 0;
-    float w = 1.f, div = 1.f;
-    int mode = 0;
-};
-
 int spmm_slice(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int d, int bv, hipStream_t st,
-               const AccHost &ah, const char *who) {
-    const int lanes = d / bv;
-    const bool strict = (h->flags & SGL_CSR_STRICT_ORDER) != 0;
-    // Lane layout, as in the fp32 kernel: rows wider than 64 lanes go in column chunks, rows of up to 16 lanes (d <= 128 with
-    // 16-byte lanes: the d = 100 hop is 13) pack R = 64 / GROUP non-zeros per step, strict order always walks one non-zero per step.
-    int group = 64, nch = 1;
-    if (lanes > 64) {
-        const int need = (lanes + 63) / 64;
-        nch = need <= 2 ? need : 4;
-    } else if (!strict && lanes <= 16) {
-        group = 8;
-        while (group < lanes) group <<= 1;
-    }
-    const int64_t forced = sgl::tuning("spmm_group", 0);
-    if (!strict && (forced == 8 || forced == 16 || forced == 32 || forced == 64)) {
-        if (nch == 1 && forced >= lanes) group = (int)forced;
-    }
-    // gathers in flight per lane: the fp32 kernel's rule for the one-row-per-step layout (16, fewer for short rows); the packed
-    // layouts take 16 per slot too from 40 non-zeros per row on (products shape, d = 100 at a 128-element pitch: 4.47 ms per hop
-    // against 4.58 with 8 and 4.56 with 4, profiles/bf16_hop_dtype_unroll.json), 8 below
-    int ulevel = (group == 64 && nch == 1) ? 2 : 1;
-    if (nch == 1 && h->n_rows > 0) {
-        const double avg = (double)h->nnz / (double)h->n_rows;
-        if (group == 64) {
-            if (avg < 12.0) ulevel = 0;
-            else if (avg < 40.0) ulevel = 1;
-        } else if (avg >= 40.0) {
-            ulevel = 2;
-        }
-    }
-    const int64_t un = sgl::tuning("spmm_unroll", 0);
-    if (un == 1) ulevel = 0;
-    if (un == 2) ulevel = 2;
-    if (un == 3) ulevel = 1;
-    int waves = (int)sgl::tuning("spmm_waves", 0);
-    if (waves != 1 && waves != 2 && waves != 4) waves = 4;
+               const AccEpi &ah, const char *who) {
+    SpmmLaunch L;
+    int rc = spmm_launch(L, h, d / bv, d, true, who);
+    if (rc == SGL_OK) rc = grow_partial(h, L.ldp);
+    if (rc != SGL_OK) return rc;
+    if (L.grid == 0) return SGL_OK;
 
     Bf16Args a;
     a.items = h->d_items;
@@ -489,52 +413,26 @@ int spmm_slice(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, in
     a.y = d_y;
     a.ldx = ldx;
     a.ldy = ldy;
-    a.ldp = (d + 7) / 8 * 8;
+    a.ldp = L.ldp;
     a.n_items = (int32_t)h->n_items;
     a.n_pieces = (int32_t)h->n_pieces;
     a.d = d;
-    a.waves = waves;
-    a.epi.acc = ah.acc;
-    a.epi.ldacc = ah.ldacc;
-    a.epi.acc_w = ah.w;
-    a.epi.acc_div = ah.div;
-    a.epi.acc_mode = ah.mode;
+    a.epi = ah;
     a.rowmap = h->d_rowmap;
-    a.piece_blocks = (int32_t)((h->n_pieces + waves - 1) / waves);
-    const int64_t item_blocks = (h->n_items + waves - 1) / waves;
-    a.xcd_remap = (!(h->flags & SGL_CSR_NO_XCD_REMAP) && sgl::tuning("spmm_xcd_remap", 1) != 0) ? 1 : 0;
-    a.item_blocks_per_xcd = (int32_t)((item_blocks + 7) / 8);
-    const int64_t grid64 = a.piece_blocks + (a.xcd_remap ? (int64_t)a.item_blocks_per_xcd * 8 : item_blocks);
-    if (grid64 >= INT32_MAX) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: grid too large", who);
-
-    if (h->n_pieces > 0) {
-        // the handle's one split-row workspace (fp32 partial sums), shared with the fp32 kernel: grow-only, outgrown buffers are
-        // kept until the handle dies (a captured fp32 chain graph may still replay into them)
-        const size_t need = (size_t)h->n_pieces * (size_t)a.ldp;
-        if (need > h->partial_cap) {
-            if (h->d_partial) h->retired.push_back(h->d_partial);
-            h->d_partial = nullptr;
-            h->partial_cap = 0;
-            SGL_HIP_CHECK(hipMalloc((void **)&h->d_partial, need * sizeof(float)));
-            h->partial_cap = need;
-        }
-    }
+    a.map = L.map;
     a.partial = h->d_partial;
-    if (grid64 == 0) return SGL_OK;
     hipError_t e;
     if (bv == 8)
-        e = launch_group<8>(a, (int)grid64, st, ulevel, group, nch);
+        e = launch_group<8>(a, L.grid, st, L.ulevel, L.group, L.nch);
     else if (bv == 4)
-        e = launch_group<4>(a, (int)grid64, st, ulevel, group, nch);
+        e = launch_group<4>(a, L.grid, st, L.ulevel, L.group, L.nch);
     else if (bv == 2)
-        e = launch_group<2>(a, (int)grid64, st, ulevel, group, nch);
+        e = launch_group<2>(a, L.grid, st, L.ulevel, L.group, L.nch);
     else
-        e = launch_group<1>(a, (int)grid64, st, ulevel, group, nch);
+        e = launch_group<1>(a, L.grid, st, L.ulevel, L.group, L.nch);
     if (e != hipSuccess) return sgl::fail((int)e, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
-    if (h->n_long > 0) {
-        const int64_t fg = (int64_t)((d + 255) / 256) * h->n_long;
-        if (fg >= INT32_MAX) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: fix-up grid too large", who);
-        hipLaunchKernelGGL(spmm_bf16_fixup_kernel, dim3((unsigned)fg), dim3(256), 0, st, h->d_rowmap ? h->d_long_out : h->d_long_row,
+    if (L.fixup_grid > 0) {
+        hipLaunchKernelGGL(spmm_bf16_fixup_kernel, dim3((unsigned)L.fixup_grid), dim3(256), 0, st, h->d_rowmap ? h->d_long_out : h->d_long_row,
                            h->d_long_first, h->d_partial, a.ldp, d_y, ldy, d, a.epi);
         e = hipGetLastError();
         if (e != hipSuccess) return sgl::fail((int)e, "%s: fix-up launch failed: %s", who, hipGetErrorString(e));
@@ -542,7 +440,7 @@ int spmm_slice(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, in
     return SGL_OK;
 }
 
-int spmm_impl(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int64_t d, void *stream, AccHost ah,
+int spmm_impl(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int64_t d, void *stream, AccEpi ah,
               const char *who) {
     if (!h) return sgl::fail(SGL_ERR_INVALID, "%s: NULL handle", who);
     SGL_REQUIRE(d >= 0 && d < INT32_MAX, "%s: bad d", who);
@@ -564,7 +462,7 @@ int spmm_impl(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int
     const int64_t max_cols = 64 * 4 * bv;
     for (int64_t c0 = 0; c0 < d; c0 += max_cols) {
         const int dc = (int)std::min<int64_t>(max_cols, d - c0);
-        AccHost as = ah;
+        AccEpi as = ah;
         if (as.acc) as.acc += c0;
         int rc = spmm_slice(h, d_x + c0, ldx, d_y + c0, ldy, dc, bv, st, as, who);
         if (rc != SGL_OK) return rc;
@@ -697,7 +595,7 @@ int gather_impl(const char *who, int n_hops, const uint16_t *const *h_x, const i
 }  // namespace
 
 SGL_EXPORT int sgl_spmm_bf16(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int64_t d, void *stream) {
-    return spmm_impl(h, d_x, ldx, d_y, ldy, d, stream, AccHost(), "sgl_spmm_bf16");
+    return spmm_impl(h, d_x, ldx, d_y, ldy, d, stream, AccEpi(), "sgl_spmm_bf16");
 }
 
 SGL_EXPORT int sgl_spmm_chain_bf16(sgl_csr_t *h, int n_hops, const uint16_t *d_x0, int64_t ldx0, uint16_t *const *h_y,
@@ -708,7 +606,7 @@ SGL_EXPORT int sgl_spmm_chain_bf16(sgl_csr_t *h, int n_hops, const uint16_t *d_x
     const uint16_t *cur = d_x0;
     int64_t ldc = ldx0;
     for (int k = 0; k < n_hops; ++k) {
-        int rc = spmm_impl(h, cur, ldc, h_y[k], h_ldy[k], d, stream, AccHost(), "sgl_spmm_chain_bf16");
+        int rc = spmm_impl(h, cur, ldc, h_y[k], h_ldy[k], d, stream, AccEpi(), "sgl_spmm_chain_bf16");
         if (rc != SGL_OK) return rc;
         cur = h_y[k];
         ldc = h_ldy[k];
@@ -718,16 +616,13 @@ SGL_EXPORT int sgl_spmm_chain_bf16(sgl_csr_t *h, int n_hops, const uint16_t *d_x
 
 SGL_EXPORT int sgl_spmm_acc_bf16(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int64_t ldy, int64_t d, float *d_acc,
                                  int64_t ldacc, float w, int mode, float divisor, void *stream) {
-    SGL_REQUIRE(d_acc != nullptr, "sgl_spmm_acc_bf16: NULL accumulator");
-    SGL_REQUIRE(!(divisor == 0.f), "sgl_spmm_acc_bf16: zero divisor");
-    SGL_REQUIRE(mode >= SGL_ACC_SUM && mode <= SGL_ACC_MIN, "sgl_spmm_acc_bf16: unknown mode %d", mode);
-    SGL_REQUIRE(mode < SGL_ACC_MAX || divisor == 1.f, "sgl_spmm_acc_bf16: max / min take no divisor");
-    AccHost ah;
+    AccEpi ah;
+    const int rc = acc_mode_of("sgl_spmm_acc_bf16", d_acc, mode, divisor, ah.acc_mode);
+    if (rc != SGL_OK) return rc;
     ah.acc = d_acc;
     ah.ldacc = ldacc;
-    ah.w = w;
-    ah.div = divisor;
-    ah.mode = mode >= SGL_ACC_MAX ? (3 | (mode == SGL_ACC_MIN ? 8 : 0)) : ((mode == SGL_ACC_WSUM ? 2 : 1) | (divisor != 1.f ? 4 : 0));
+    ah.acc_w = w;
+    ah.acc_div = divisor;
     return spmm_impl(h, d_x, ldx, d_y, ldy, d, stream, ah, "sgl_spmm_acc_bf16");
 }
 

@@ -245,7 +245,7 @@ def widen_hops(feats):
 
 
 def default_long_row_nnz(nnz):
-    """where sgl_csr_create cuts long rows when it is not told (csrc/sgl_spmm.hip: a function of the matrix's nnz only).  A row
+    """where sgl_csr_create cuts long rows when it is not told (sgl::default_long_row_nnz, csrc/sgl_core.cpp: a function of the matrix's nnz only).  A row
     block of a sharded matrix has fewer non-zeros than the whole and would fall into another bracket: the distributed paths pass
     default_long_row_nnz(GLOBAL nnz) explicitly, so that the same rows are cut at the same places whatever the world size and the
     default-order hops of a sharded run stay bit-identical to the single-GPU run."""

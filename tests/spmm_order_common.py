@@ -1,9 +1,11 @@
 """Shared by the SpMM summation-order tests (test_spmm_order_cpu.py, test_gpu_spmm_order.py); no GPU needed to import it.
 
 Three restatements, each made ONCE here, of things the library decides on its own:
-  * default_long_row_nnz   where sgl_csr_create cuts long rows when it is not told (csrc/sgl_spmm.hip, "if (long_row_nnz == 0)")
-  * dispatch               which kernel template spmm_impl / spmm_slice launch for a call (csrc/sgl_spmm.hip, sgl_spmm_bf16.hip)
+  * default_long_row_nnz   where sgl_csr_create cuts long rows when it is not told (sgl::default_long_row_nnz, csrc/sgl_core.cpp)
+  * dispatch               which kernel template spmm_impl / spmm_slice launch for a call: the lane width in csrc/sgl_spmm.hip and
+                           sgl_spmm_bf16.hip, the layout in sgl::spmm_layout (csrc/sgl_core.cpp)
   * compiled_variants      every template instance the launch tables of the two files can reach
+(the first two are compared with the library's own answers without a GPU in test_spmm_order_cpu.py)
 plus the parser of kernel names as a profiler reports them, and the test graphs."""
 import re
 
@@ -12,7 +14,7 @@ import scipy.sparse as sp
 
 
 def default_long_row_nnz(nnz):
-    """sgl_csr_create, csrc/sgl_spmm.hip: `long_row_nnz = nnz < (1 << 18) ? 32 : nnz < (1 << 20) ? 128 : nnz < (1 << 22) ? 512 : 2048`"""
+    """sgl::default_long_row_nnz, csrc/sgl_core.cpp: `nnz < (1 << 18) ? 32 : nnz < (1 << 20) ? 128 : nnz < (1 << 22) ? 512 : 2048`"""
     nnz = int(nnz)
     return 32 if nnz < (1 << 18) else 128 if nnz < (1 << 20) else 512 if nnz < (1 << 22) else 2048
 
@@ -102,7 +104,8 @@ LAYOUTS = ((8, 1), (16, 1), (32, 1), (64, 1), (64, 2), (64, 4))      # (GROUP, N
 
 
 def unroll_of(group, nch, ulevel):
-    """launch_u of both files (sgl_spmm.hip has level 3 in addition): gathers in flight per lane"""
+    """sgl::unroll_of (csrc/sgl_common.h), the template argument of launch_u in both files (sgl_spmm.hip has level 3 in addition):
+    gathers in flight per lane"""
     uh = 8 if nch == 1 else 4 if nch == 2 else 2
     if ulevel == 2:
         return uh * 2 if nch == 1 else uh
@@ -138,7 +141,7 @@ TUNING_VALUES = {"spmm_group": (0, 8, 16, 32, 64), "spmm_unroll": (0, 1, 2, 3, 4
 
 def dispatch(dtype, d, ldx, ldy, x_ptr, y_ptr, strict, avg_nnz, tuning=None, acc=None):
     """[(c0, dc, variant)] per column slice of one sgl_spmm_f32 / sgl_spmm_bf16 (/ _acc_) call: spmm_impl and spmm_slice of
-    csrc/sgl_spmm.hip and csrc/sgl_spmm_bf16.hip restated.  Pitches in elements, pointers in bytes, avg_nnz = nnz / n_rows,
+    csrc/sgl_spmm.hip and csrc/sgl_spmm_bf16.hip with sgl::spmm_layout of csrc/sgl_core.cpp restated.  Pitches in elements, pointers in bytes, avg_nnz = nnz / n_rows,
     acc = (ldacc, acc_ptr) of the fused aggregate, tuning = {key: value} (missing keys at their defaults).
     variant = (BV, GROUP, NCH, U) for "bf16", (VEC, GROUP, NCH, U, NT) for "f32"; R = 64 // GROUP."""
     t = dict(TUNING_DEFAULTS)

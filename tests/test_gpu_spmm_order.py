@@ -5,8 +5,8 @@ spmm_bf16_kernel (csrc/sgl_spmm_bf16.hip, header "Numerics" and run_rows) is det
 (oracle.oracle_spmm_slots, oracle/spmm_ref.c) and compared exactly: fp32 results as 32-bit patterns, bf16 results as 16-bit
 patterns, NaNs by position.  There is NO tolerance anywhere in this file.
 
-Which template instance runs is decided by spmm_impl / spmm_slice from widths, pitches, pointer alignment, the average row
-length and the tuning keys.  That rule is restated in spmm_order_common.dispatch, and every launch made here is checked against
+Which template instance runs is decided by spmm_impl / spmm_slice (the lane width) and sgl::spmm_layout (csrc/sgl_core.cpp: the
+lane layout) from widths, pitches, pointer alignment, the average row length and the tuning keys.  That rule is restated in spmm_order_common.dispatch, and every launch made here is checked against
 the name of the kernel that really ran, as the profiler reports it.  The model's R is 64 / GROUP of that kernel."""
 import contextlib
 

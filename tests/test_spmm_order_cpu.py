@@ -8,7 +8,7 @@ import torch
 
 import oracle
 from inputs import hash_matrix
-from spmm_order_common import (compiled_variants, cut_rule, default_long_row_nnz, dense_graph, dispatch, medium_graph,
+from spmm_order_common import (TUNING_VALUES, compiled_variants, cut_rule, default_long_row_nnz, dense_graph, dispatch, medium_graph,
                                parse_kernel_name)
 from test_gpu_bf16 import long_row_graph
 from test_host_cpu import build_plan
@@ -188,3 +188,60 @@ def test_restated_launch_tables_and_dispatch():
     assert dispatch("f32", 16, 16, 16, A, A, False, 51.5, {"spmm_group": 32, "spmm_unroll": 4}) == [(0, 16, (4, 32, 1, 8, 0))]
     assert dispatch("f32", 1028, 1028, 1028, A, A, False, 5.0) == [(0, 1024, (4, 64, 4, 2, 0)), (1024, 4, (4, 8, 1, 8, 0))]
     assert dispatch("f32", 100, 100, 100, A, A, False, 5.0, {"spmm_vec": 2}, acc=(101, A)) == [(0, 100, (1, 64, 2, 4, 0))]
+
+
+def test_library_launch_rule_and_default_thresholds_equal_the_restatements(tmp_path):
+    """sgl::spmm_layout / default_item_nnz / default_long_row_nnz (csrc/sgl_core.cpp: pure host code), built with g++ into
+    tests/native/spmm_layout_table.cpp and asked once: for both dtypes, every lane width and every width of the GPU test, strict
+    or not, average row lengths on both sides of and exactly at the two thresholds, a matrix without rows (its average is 0 / 0:
+    no threshold applies), and every value of the four launch keys one at a time, the library's (GROUP, NCH, U[, NT]) is
+    spmm_order_common.dispatch's for every column slice and is a compiled variant; and the default cut threshold is the one
+    restated in spmm_order_common and in sgl_amd.device at every step of the rule."""
+    import os
+    import shutil
+    import subprocess
+    from conftest import ROOT
+    from sgl_amd import device as dev
+    from test_gpu_spmm_order import WIDTHS
+    gxx = shutil.which("g++")
+    if gxx is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime.h"):
+        pytest.skip("needs g++ and the HIP headers")
+    exe = str(tmp_path / "spmm_layout_table")
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                        os.path.join(ROOT, "tests", "native", "spmm_layout_table.cpp"), os.path.join(ROOT, "sgl_amd", "csrc", "sgl_core.cpp"),
+                        "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-pthread", "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    keys = ("spmm_group", "spmm_unroll", "spmm_waves", "spmm_nt")
+    tunings = [{}] + [{k: v} for k in keys for v in TUNING_VALUES[k]]
+    rows = ((6000, 1000), (25000, 1000), (60000, 1000), (12000, 1000), (40000, 1000), (0, 0))        # (nnz, n_rows)
+    nnzs = ((1 << 18) - 1, 1 << 18, (1 << 20) - 1, 1 << 20, (1 << 22) - 1, 1 << 22, 10 ** 8 - 1, 10 ** 8)
+    A = 1 << 20                                                   # an aligned address
+    queries, want = [], []
+    for dtype in ("f32", "bf16"):
+        for W, widths in WIDTHS[dtype].items():
+            for d in widths:
+                for strict in (0, 1):
+                    for nnz, n_rows in rows:
+                        avg = nnz / n_rows if n_rows else float("nan")
+                        for t in tunings:
+                            for c0, dc, var in dispatch(dtype, d, d, d, A, A, bool(strict), avg, t):
+                                assert var[0] == W, (dtype, d, var)
+                                queries.append(f"{dtype} {dc // W} {strict} {nnz} {n_rows} " + " ".join(str(t.get(k, 0)) for k in keys))
+                                waves = t.get("spmm_waves", 0)
+                                want.append((dtype, var, waves if waves in (1, 2, 4) else 4))
+    r = subprocess.run([exe], input="\n".join(queries + [str(v) for v in nnzs]) + "\n", capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+    assert len(got) == len(queries) + len(nnzs) and len(queries) > 10000
+    seen = {"f32": set(), "bf16": set()}
+    for q, (dtype, var, waves), (group, nch, u, nt, wv) in zip(queries, want, got):
+        mine = (var[0], group, nch, u) + ((nt,) if dtype == "f32" else ())
+        assert mine == var and wv == waves and (dtype == "f32" or nt == 0), (q, var, (group, nch, u, nt, wv))
+        assert mine in compiled_variants(dtype), (q, mine)
+        seen[dtype].add(mine)
+    assert len(seen["f32"]) > 40 and len(seen["bf16"]) > 40                     # the queries reach the table, not one corner of it
+    for nnz, (item_nnz, long_nnz) in zip(nnzs, got[len(queries):]):
+        assert long_nnz == default_long_row_nnz(nnz) == dev.default_long_row_nnz(nnz), nnz
+        # 8 192 items (one per resident wavefront) of at least 16 non-zeros, at most 256 below 10^8 non-zeros and 512 from there on
+        assert item_nnz == min(512 if nnz >= 10 ** 8 else 256, max(16, nnz // 8192)), (nnz, item_nnz)
+    assert [g[1] for g in got[len(queries):]] == [32, 128, 128, 512, 512, 2048, 2048, 2048]
