@@ -1534,33 +1534,39 @@ bool vec4_rows(const H &hx, int n_hops) {   // every hop matrix has 16-byte alig
     return true;
 }
 
-int fill_hops(Hops &hx, int n_hops, const float *const *h_x, const int64_t *h_ldx, int64_t d, bool &vec4) {
-    if (n_hops < 1 || n_hops > SGL_MAX_HOPS) return sgl::fail(SGL_ERR_INVALID, "n_hops=%d outside [1,%d]", n_hops, SGL_MAX_HOPS);
-    if (!h_x) return sgl::fail(SGL_ERR_INVALID, "NULL hop pointer array");
-    for (int h = 0; h < n_hops; ++h) {
-        hx.p[h] = h_x[h];
-        hx.ld[h] = h_ldx ? h_ldx[h] : d;
-        if (!hx.p[h]) return sgl::fail(SGL_ERR_INVALID, "hop %d: NULL pointer", h);
-        if (hx.ld[h] < d) return sgl::fail(SGL_ERR_INVALID, "hop %d: leading dimension %lld < d", h, (long long)hx.ld[h]);
-        if (!aligned_to(hx.p[h], 4)) return sgl::fail(SGL_ERR_INVALID, "hop %d: pointer not 4-byte aligned", h);
-        if (hx.ld[h] % 4 != 0 || !aligned_to(hx.p[h], 16)) vec4 = false;
-    }
-    for (int h = n_hops; h < SGL_MAX_HOPS; ++h) {
-        hx.p[h] = nullptr;
-        hx.ld[h] = 0;
+// A HopsOut table from the caller's arrays: entries [0, n), the rest null.  required: a NULL entry is an error (else it stays null
+// and the kernels skip it).  Every entry given needs a pitch >= min_pitch (h_ld == NULL: the pitch is min_pitch) and `align`-byte
+// alignment (0: not checked; 16: whole vectors, so the pitch a multiple of 4 floats as well); `bad`: the error text, one %d for the
+// entry.  *vec4 (optional) is cleared where an entry's rows are not 16-byte vectors.
+int fill_outs(HopsOut &t, int n, float *const *h_p, const int64_t *h_ld, bool required, int64_t min_pitch, int align, const char *bad,
+              bool *vec4) {
+    for (int k = 0; k < SGL_MAX_HOPS; ++k) {
+        t.p[k] = k < n ? h_p[k] : nullptr;
+        t.ld[k] = k < n ? (h_ld ? h_ld[k] : min_pitch) : 0;
+        if (k >= n || (!t.p[k] && !required)) continue;
+        const bool rows16 = t.ld[k] % 4 == 0 && aligned_to(t.p[k], 16);
+        if (!t.p[k] || t.ld[k] < min_pitch || (align == 16 ? !rows16 : (align > 0 && !aligned_to(t.p[k], (size_t)align))))
+            return sgl::fail(SGL_ERR_INVALID, bad, k);
+        if (vec4 && !rows16) *vec4 = false;
     }
     return SGL_OK;
 }
 
-int stream_grid(int64_t total_threads) {
-    // memory-bound elementwise: one 16-byte element per thread.  Measured on MI355X (products shape, 5 streams): a
-    // 2048-block grid-stride launch reaches 5.3 TB/s, one element per thread 5.9 TB/s (torch's add: 6.0); the
-    // grid-stride loop only remains as the overflow path for > 2^22 blocks.
-    int64_t blocks = (total_threads + 255) / 256;
-    const int64_t cap = sgl::tuning("agg_blocks", 0) > 0 ? sgl::tuning("agg_blocks", 0) : ((int64_t)1 << 22);
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
+// Lanes per row of the copy kernels: the group size that leaves the fewest lane slots idle (a row of 40 vectors -- d = 147 on its
+// 160-float pitch -- on 64 lanes idles 24 of them in every instruction; on 8 lanes x 5 iterations none, and a wavefront then has
+// 8 rows = 8 independent sets of lines in flight); ties go to the wider group (fewer iterations per row).  nv = lane accesses per row.
+int copy_lpr(int64_t nv) {
+    int lpr = 64;
+    int64_t best = -1;
+    for (int cand : {64, 32, 16, 8}) {
+        const int64_t waste = (nv + cand - 1) / cand * cand - nv;
+        if (best < 0 || waste < best) {
+            best = waste;
+            lpr = cand;
+        }
+    }
+    if (sgl::tuning("gather_lpr", 0) > 0) lpr = (int)sgl::tuning("gather_lpr", 0);
+    return lpr;
 }
 
 }  // namespace
@@ -1572,26 +1578,18 @@ SGL_EXPORT int sgl_hop_reduce_f32(int op, int n_hops, const float *const *h_x, c
     SGL_REQUIRE(op != SGL_REDUCE_WSUM || d_w, "sgl_hop_reduce_f32: WSUM needs device weights");
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldo % 4 == 0) && aligned_to(d_out, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_out && ldo >= d, "sgl_hop_reduce_f32: bad output");
     hipStream_t st = sgl::as_stream(stream);
     const int vec = vec4 ? 4 : 1;
     const int grid = stream_grid(n * (d / vec));
-#define SGL_RED(OP)                                                                                               \
-    if (vec4)                                                                                                     \
-        hipLaunchKernelGGL((hop_reduce_kernel<OP, 4>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, d_out, ldo, n, (int)d); \
-    else                                                                                                          \
-        hipLaunchKernelGGL((hop_reduce_kernel<OP, 1>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, d_out, ldo, n, (int)d);
-    switch (op) {
-        case SGL_REDUCE_SUM: SGL_RED(SGL_REDUCE_SUM) break;
-        case SGL_REDUCE_MEAN: SGL_RED(SGL_REDUCE_MEAN) break;
-        case SGL_REDUCE_MAX: SGL_RED(SGL_REDUCE_MAX) break;
-        case SGL_REDUCE_MIN: SGL_RED(SGL_REDUCE_MIN) break;
-        default: SGL_RED(SGL_REDUCE_WSUM) break;
-    }
-#undef SGL_RED
+    with_one_of<SGL_REDUCE_SUM, SGL_REDUCE_MEAN, SGL_REDUCE_MAX, SGL_REDUCE_MIN, SGL_REDUCE_WSUM>(op, [&](auto OP) {
+        with_vec(vec4, [&](auto V) {
+            hipLaunchKernelGGL((hop_reduce_kernel<OP, V>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, d_out, ldo, n, (int)d);
+        });
+    });
     SGL_LAUNCH_CHECK("sgl_hop_reduce_f32");
     return SGL_OK;
 }
@@ -1601,21 +1599,18 @@ static int wsum2d_impl(bool fma, int n_hops, const float *const *h_x, const int6
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_wsum2d_f32: bad sizes");
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldo % 4 == 0) && aligned_to(d_out, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_w && ldw >= n_hops, "sgl_hop_wsum2d_f32: bad weights");
     SGL_REQUIRE(d_out && ldo >= d, "sgl_hop_wsum2d_f32: bad output");
     hipStream_t st = sgl::as_stream(stream);
     const int grid = stream_grid(n * (d / (vec4 ? 4 : 1)));
-    if (vec4 && fma)
-        hipLaunchKernelGGL((hop_wsum2d_kernel<4, true>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, ldw, d_out, ldo, n, (int)d);
-    else if (vec4)
-        hipLaunchKernelGGL((hop_wsum2d_kernel<4, false>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, ldw, d_out, ldo, n, (int)d);
-    else if (fma)
-        hipLaunchKernelGGL((hop_wsum2d_kernel<1, true>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, ldw, d_out, ldo, n, (int)d);
-    else
-        hipLaunchKernelGGL((hop_wsum2d_kernel<1, false>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, ldw, d_out, ldo, n, (int)d);
+    with_vec(vec4, [&](auto V) {
+        with_bool(fma, [&](auto FMA) {
+            hipLaunchKernelGGL((hop_wsum2d_kernel<V, FMA>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, ldw, d_out, ldo, n, (int)d);
+        });
+    });
     SGL_LAUNCH_CHECK("sgl_hop_wsum2d_f32");
     return SGL_OK;
 }
@@ -1625,42 +1620,28 @@ SGL_EXPORT int sgl_hop_wsum2d_f32(int n_hops, const float *const *h_x, const int
     return wsum2d_impl(true, n_hops, h_x, h_ldx, d_w, ldw, d_out, ldo, n, d, stream);
 }
 
+// dW / gate scores of `who`: the register-resident kernel where the row's H hop vectors fit, else the general row-dot
 template <int VEC>
-static void launch_rowdot(int lpr, int g_unaligned, hipStream_t st, const Hops &hx, int n_hops,
-                          const float *g, int64_t ldg, float *dw, int64_t lddw, int64_t n, int d) {
+static int launch_rowdot(const char *who, int lpr, bool g_unaligned, hipStream_t st, const Hops &hx, int n_hops, const float *g,
+                         int64_t ldg, float *dw, int64_t lddw, int64_t n, int d) {
     if constexpr (VEC == 4) {
         // the row's H hop vectors fit in registers: one load of dOut, all loads in flight, interleaved butterflies
-        const RowLayout lay = pick_row_layout(d, n_hops);
-        if (n_hops <= 16 && d <= lay.lpr * 4 * lay.ch) {
-            const unsigned grid = (unsigned)((n + (256 / lay.lpr) - 1) / (256 / lay.lpr));
-#define SGL_RR(L, C, HM)                                                                                                        \
-    do {                                                                                                                       \
-        if (g_unaligned)                                                                                                       \
-            hipLaunchKernelGGL((hop_rowdot_reg_kernel<L, C, HM, true>), dim3(grid), dim3(256), 0, st, hx, n_hops, g, ldg, dw, lddw, n, d); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((hop_rowdot_reg_kernel<L, C, HM, false>), dim3(grid), dim3(256), 0, st, hx, n_hops, g, ldg, dw, lddw, n, d); \
-    } while (0)
-#define SGL_RR_H(L, C) SGL_HOPS_UP_TO_16(SGL_RR, L, C)
-#define SGL_RR_H12(L, C) SGL_HOPS_UP_TO_12(SGL_RR, L, C)
-#define SGL_RR_H6(L, C) (void)0          /* 8 x 5 is never chosen for this kernel (pick_row_layout) */
-            SGL_ROWREG_DISPATCH(SGL_RR_H, SGL_RR_H12, SGL_RR_H6, lay);
-#undef SGL_RR_H6
-#undef SGL_RR_H12
-#undef SGL_RR_H
-#undef SGL_RR
-            return;
+        const sgl::RowInstance in = sgl::row_instance(d, n_hops);
+        if (n_hops <= 16 && d <= in.lpr * 4 * in.ch) {
+            const unsigned grid = (unsigned)((n + (256 / in.lpr) - 1) / (256 / in.lpr));
+            const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
+                with_bool(g_unaligned, [&](auto GU) {
+                    hipLaunchKernelGGL((hop_rowdot_reg_kernel<L, C, HM, GU>), dim3(grid), dim3(256), 0, st, hx, n_hops, g, ldg, dw, lddw, n, d);
+                });
+            });
+            return ok ? SGL_OK : no_row_instance(who, in.lpr, in.ch, n_hops);
         }
     }
-#define SGL_RD(L)                                                                                              \
-    hipLaunchKernelGGL((hop_rowdot_kernel<L, VEC>), dim3((unsigned)((n + (256 / L) - 1) / (256 / L))), dim3(256), 0, st, \
-                       hx, n_hops, g, ldg, dw, lddw, n, d)
-    switch (lpr) {
-        case 8: SGL_RD(8); break;
-        case 16: SGL_RD(16); break;
-        case 32: SGL_RD(32); break;
-        default: SGL_RD(64); break;
-    }
-#undef SGL_RD
+    with_lpr(lpr, [&](auto L) {
+        hipLaunchKernelGGL((hop_rowdot_kernel<L, VEC>), dim3((unsigned)((n + (256 / L) - 1) / (256 / L))), dim3(256), 0, st, hx, n_hops, g,
+                           ldg, dw, lddw, n, d);
+    });
+    return SGL_OK;
 }
 
 SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_w,
@@ -1669,7 +1650,7 @@ SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_wsum2d_bwd_f32: bad sizes");
     Hops hx;
     bool hops4 = true;                                         // 16-byte row accesses possible (any d, masked tail)
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, hops4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &hops4);
     if (rc != SGL_OK) return rc;
     const bool g4 = (lddo % 4 == 0) && aligned_to(d_dout, 16);
     // a dword-aligned dOut (autograd's dense gradient, d % 4 != 0) still takes the 16-byte path for the H hop reads when the
@@ -1682,33 +1663,25 @@ SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const
     hipStream_t st = sgl::as_stream(stream);
     if (d_dw) {
         SGL_REQUIRE(lddw >= n_hops, "sgl_hop_wsum2d_bwd_f32: lddw < n_hops");
-        const int lpr = pick_lpr(d, row4 ? 4 : 1);
+        const int lpr = sgl::pick_lpr(d, row4 ? 4 : 1);
         SGL_REQUIRE((n + (256 / lpr) - 1) / (256 / lpr) < INT32_MAX, "sgl_hop_wsum2d_bwd_f32: too many rows");
-        if (row4)
-            launch_rowdot<4>(lpr, g_unaligned ? 1 : 0, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d);
-        else
-            launch_rowdot<1>(lpr, 0, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d);
+        rc = row4 ? launch_rowdot<4>("sgl_hop_wsum2d_bwd_f32", lpr, g_unaligned, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d)
+                  : launch_rowdot<1>("sgl_hop_wsum2d_bwd_f32", lpr, false, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d);
+        if (rc != SGL_OK) return rc;
         SGL_LAUNCH_CHECK("sgl_hop_wsum2d_bwd_f32(dW)");
     }
     if (h_dx) {
         SGL_REQUIRE(d_w && ldw >= n_hops, "sgl_hop_wsum2d_bwd_f32: dX needs W");
         HopsOut dx;
         bool any = false, v4 = vec4;
-        for (int h = 0; h < SGL_MAX_HOPS; ++h) {
-            dx.p[h] = (h < n_hops) ? h_dx[h] : nullptr;
-            dx.ld[h] = (h < n_hops) ? (h_lddx ? h_lddx[h] : d) : 0;
-            if (dx.p[h]) {
-                any = true;
-                if (dx.ld[h] < d) return sgl::fail(SGL_ERR_INVALID, "sgl_hop_wsum2d_bwd_f32: dX ld < d");
-                if (dx.ld[h] % 4 != 0 || !aligned_to(dx.p[h], 16)) v4 = false;
-            }
-        }
+        rc = fill_outs(dx, n_hops, h_dx, h_lddx, false, d, 0, "sgl_hop_wsum2d_bwd_f32: dX ld < d", &v4);
+        if (rc != SGL_OK) return rc;
+        for (int h = 0; h < n_hops; ++h) any = any || dx.p[h];
         if (any) {
             const int grid = stream_grid(n * (d / (v4 ? 4 : 1)));
-            if (v4)
-                hipLaunchKernelGGL((hop_wsum2d_dx_kernel<4>), dim3(grid), dim3(256), 0, st, dx, n_hops, d_w, ldw, d_dout, lddo, n, (int)d);
-            else
-                hipLaunchKernelGGL((hop_wsum2d_dx_kernel<1>), dim3(grid), dim3(256), 0, st, dx, n_hops, d_w, ldw, d_dout, lddo, n, (int)d);
+            with_vec(v4, [&](auto V) {
+                hipLaunchKernelGGL((hop_wsum2d_dx_kernel<V>), dim3(grid), dim3(256), 0, st, dx, n_hops, d_w, ldw, d_dout, lddo, n, (int)d);
+            });
             SGL_LAUNCH_CHECK("sgl_hop_wsum2d_bwd_f32(dX)");
         }
     }
@@ -1723,7 +1696,7 @@ SGL_EXPORT int sgl_hop_rowdot_f32(int n_hops, const float *const *h_x, const int
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_rowdot_f32: bad sizes");
     Hops hx;
     bool row4 = aligned_to(d_vec, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, row4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &row4);
     if (rc != SGL_OK) return rc;
     if (n == 0) return SGL_OK;
     SGL_REQUIRE(d_vec && d_out && ldo >= n_hops, "sgl_hop_rowdot_f32: bad arguments");
@@ -1735,12 +1708,11 @@ SGL_EXPORT int sgl_hop_rowdot_f32(int n_hops, const float *const *h_x, const int
     }
     // the vector is read with the same 16-byte lanes as the rows: it must be readable up to round_up(d, 4) floats
     // (callers pass a zero-padded copy), the masked tail ignores what lies beyond d
-    const int lpr = pick_lpr(d, row4 ? 4 : 1);
+    const int lpr = sgl::pick_lpr(d, row4 ? 4 : 1);
     SGL_REQUIRE((n + (256 / lpr) - 1) / (256 / lpr) < INT32_MAX, "sgl_hop_rowdot_f32: too many rows");
-    if (row4)
-        launch_rowdot<4>(lpr, 0, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d);
-    else
-        launch_rowdot<1>(lpr, 0, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d);
+    rc = row4 ? launch_rowdot<4>("sgl_hop_rowdot_f32", lpr, false, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d)
+              : launch_rowdot<1>("sgl_hop_rowdot_f32", lpr, false, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d);
+    if (rc != SGL_OK) return rc;
     SGL_LAUNCH_CHECK("sgl_hop_rowdot_f32");
     return SGL_OK;
 }
@@ -1752,7 +1724,7 @@ SGL_EXPORT int sgl_hop_wsum1d_bwd_f32(int n_hops, const float *const *h_x, const
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_wsum1d_bwd_f32: bad sizes");
     Hops hx;
     bool vec4 = false;
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     SGL_REQUIRE(d_dw && d_scratch, "sgl_hop_wsum1d_bwd_f32: NULL output/scratch");
     hipStream_t st = sgl::as_stream(stream);
@@ -1768,20 +1740,12 @@ SGL_EXPORT int sgl_hop_wsum1d_bwd_f32(int n_hops, const float *const *h_x, const
         blocks = (int)std::min<int64_t>(kW1dBlocks, (total + 255) / 256);
         const int64_t per_block = ((total + blocks - 1) / blocks + 255) / 256 * 256;
         blocks = (int)((total + per_block - 1) / per_block);
-#define SGL_DP(HM)                                                                                                             \
-    do {                                                                                                                       \
-        if (g4)                                                                                                                \
-            hipLaunchKernelGGL((hop_dot_partial_vec_kernel<HM, false>), dim3(blocks), dim3(256), 0, st, hx, n_hops, d_dout, lddo, \
-                               d_scratch, n, (int)d, per_block);                                                              \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((hop_dot_partial_vec_kernel<HM, true>), dim3(blocks), dim3(256), 0, st, hx, n_hops, d_dout, lddo, \
-                               d_scratch, n, (int)d, per_block);                                                              \
-    } while (0)
-        if (n_hops <= 4) SGL_DP(4);
-        else if (n_hops <= 8) SGL_DP(8);
-        else if (n_hops <= 12) SGL_DP(12);
-        else SGL_DP(16);
-#undef SGL_DP
+        with_hop_capacity(n_hops, [&](auto HM) {
+            with_bool(!g4, [&](auto GU) {
+                hipLaunchKernelGGL((hop_dot_partial_vec_kernel<HM, GU>), dim3(blocks), dim3(256), 0, st, hx, n_hops, d_dout, lddo,
+                                   d_scratch, n, (int)d, per_block);
+            });
+        });
     } else {
         blocks = (int)std::min<int64_t>(kW1dBlocks, (n * d + 255) / 256);
         hipLaunchKernelGGL(hop_dot_partial_kernel, dim3(blocks), dim3(256), 0, st, hx, n_hops, d_dout, lddo, d_scratch, n, (int)d);
@@ -1798,29 +1762,21 @@ SGL_EXPORT int sgl_hop_select_bwd_f32(int op, int n_hops, const float *const *h_
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_select_bwd_f32: bad sizes");
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldg % 4 == 0) && aligned_to(d_gout, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     SGL_REQUIRE(h_dx && h_lddx, "sgl_hop_select_bwd_f32: NULL gradient arrays");
     HopsOut dx;
-    for (int h = 0; h < SGL_MAX_HOPS; ++h) {
-        dx.p[h] = h < n_hops ? h_dx[h] : nullptr;
-        dx.ld[h] = h < n_hops ? h_lddx[h] : 0;
-        if (dx.p[h]) {
-            SGL_REQUIRE(dx.ld[h] >= d && aligned_to(dx.p[h], 4), "sgl_hop_select_bwd_f32: bad gradient buffer %d", h);
-            if (dx.ld[h] % 4 != 0 || !aligned_to(dx.p[h], 16)) vec4 = false;
-        }
-    }
+    rc = fill_outs(dx, n_hops, h_dx, h_lddx, false, d, 4, "sgl_hop_select_bwd_f32: bad gradient buffer %d", &vec4);
+    if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_gout && ldg >= d, "sgl_hop_select_bwd_f32: bad incoming gradient");
     hipStream_t st = sgl::as_stream(stream);
     const int grid = stream_grid(n * (d / (vec4 ? 4 : 1)));
-    if (op == SGL_REDUCE_MAX) {
-        if (vec4) hipLaunchKernelGGL((hop_select_bwd_kernel<true, 4>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_gout, ldg, dx, n, (int)d);
-        else hipLaunchKernelGGL((hop_select_bwd_kernel<true, 1>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_gout, ldg, dx, n, (int)d);
-    } else {
-        if (vec4) hipLaunchKernelGGL((hop_select_bwd_kernel<false, 4>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_gout, ldg, dx, n, (int)d);
-        else hipLaunchKernelGGL((hop_select_bwd_kernel<false, 1>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_gout, ldg, dx, n, (int)d);
-    }
+    with_bool(op == SGL_REDUCE_MAX, [&](auto IS_MAX) {
+        with_vec(vec4, [&](auto V) {
+            hipLaunchKernelGGL((hop_select_bwd_kernel<IS_MAX, V>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_gout, ldg, dx, n, (int)d);
+        });
+    });
     SGL_LAUNCH_CHECK("sgl_hop_select_bwd_f32");
     return SGL_OK;
 }
@@ -1834,32 +1790,21 @@ SGL_EXPORT int sgl_hop_lincomb_f32(int n_in, const float *const *h_x, const int6
     SGL_REQUIRE(h_out && h_ldo, "sgl_hop_lincomb_f32: NULL output arrays");
     Hops hx;
     bool vec4 = (d % 4 == 0);
-    int rc = fill_hops(hx, n_in, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_in, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     HopsOut outs;
-    for (int k = 0; k < SGL_MAX_HOPS; ++k) {
-        outs.p[k] = k < n_out ? h_out[k] : nullptr;
-        outs.ld[k] = k < n_out ? h_ldo[k] : 0;
-        if (k < n_out) {
-            SGL_REQUIRE(outs.p[k] && outs.ld[k] >= d && aligned_to(outs.p[k], 4), "sgl_hop_lincomb_f32: bad output %d", k);
-            if (outs.ld[k] % 4 != 0 || !aligned_to(outs.p[k], 16)) vec4 = false;
-            for (int j = 0; j < n_in; ++j)
-                SGL_REQUIRE(outs.p[k] != hx.p[j], "sgl_hop_lincomb_f32: output %d aliases input %d", k, j);
-        }
-    }
+    rc = fill_outs(outs, n_out, h_out, h_ldo, true, d, 4, "sgl_hop_lincomb_f32: bad output %d", &vec4);
+    if (rc != SGL_OK) return rc;
+    for (int k = 0; k < n_out; ++k)
+        for (int j = 0; j < n_in; ++j) SGL_REQUIRE(outs.p[k] != hx.p[j], "sgl_hop_lincomb_f32: output %d aliases input %d", k, j);
     if (n == 0 || d == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
     const int grid = stream_grid(n * (d / (vec4 ? 4 : 1)));
-#define SGL_LC(NI)                                                                                                                 \
-    do {                                                                                                                           \
-        if (vec4) hipLaunchKernelGGL((hop_lincomb_kernel<NI, 4>), dim3(grid), dim3(256), 0, st, hx, n_in, outs, n_out, d_w, (int)ldw, n, (int)d); \
-        else hipLaunchKernelGGL((hop_lincomb_kernel<NI, 1>), dim3(grid), dim3(256), 0, st, hx, n_in, outs, n_out, d_w, (int)ldw, n, (int)d);      \
-    } while (0)
-    if (n_in <= 4) SGL_LC(4);
-    else if (n_in <= 8) SGL_LC(8);
-    else if (n_in <= 12) SGL_LC(12);
-    else SGL_LC(16);
-#undef SGL_LC
+    with_hop_capacity(n_in, [&](auto NI) {
+        with_vec(vec4, [&](auto V) {
+            hipLaunchKernelGGL((hop_lincomb_kernel<NI, V>), dim3(grid), dim3(256), 0, st, hx, n_in, outs, n_out, d_w, (int)ldw, n, (int)d);
+        });
+    });
     SGL_LAUNCH_CHECK("sgl_hop_lincomb_f32");
     return SGL_OK;
 }
@@ -1868,12 +1813,12 @@ SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, co
                                          int64_t pad_cols, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_concat_f32: bad sizes");
     {
-        const int prc = check_pad("sgl_hop_concat_padded_f32", d * (n_hops > 0 ? n_hops : 0), pad_cols, ldo);
+        const int prc = sgl::check_pad("sgl_hop_concat_padded_f32", d * (n_hops > 0 ? n_hops : 0), pad_cols, ldo);
         if (prc != SGL_OK) return prc;
     }
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldo % 4 == 0) && aligned_to(d_out, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_out && ldo >= d * n_hops, "sgl_hop_concat_f32: bad output");
@@ -1882,13 +1827,13 @@ SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, co
     if (vec4) {
         const int grid = stream_grid(n * (d / 4) * n_hops);
         hipLaunchKernelGGL((hop_concat_kernel<4>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d);
-    } else if (out16 && d >= 4 && vec4_rows(hx, n_hops) && d * n_hops >= 256 && out_cols(d * n_hops, pad_cols, INT32_MAX) <= kConcatRowCap &&
+    } else if (out16 && d >= 4 && vec4_rows(hx, n_hops) && d * n_hops >= 256 && sgl::out_cols(d * n_hops, pad_cols, INT32_MAX) <= kConcatRowCap &&
                (sgl::tuning("concat_lds", 1) == 3 ||
                 (sgl::tuning("concat_lds", 1) == 1 &&      // where the 1024-float tiles of the kernel below would be < 85 % full
-                 100 * (int64_t)out_cols(d * n_hops, pad_cols, INT32_MAX) <
-                     85 * (int64_t)kConcatTile * ((out_cols(d * n_hops, pad_cols, INT32_MAX) + kConcatTile - 1) / kConcatTile)))) {
+                 100 * (int64_t)sgl::out_cols(d * n_hops, pad_cols, INT32_MAX) <
+                     85 * (int64_t)kConcatTile * ((sgl::out_cols(d * n_hops, pad_cols, INT32_MAX) + kConcatTile - 1) / kConcatTile)))) {
         // any d, rows of 256 ... 4096 floats: whole rows assembled in LDS, the block's threads share the work flat
-        const int width_w = out_cols(d * n_hops, pad_cols, INT32_MAX);
+        const int width_w = sgl::out_cols(d * n_hops, pad_cols, INT32_MAX);
         const int W = (width_w + 3) / 4 * 4;
         const int R = kConcatLds / W;
         const int64_t blocks = (n + R - 1) / R;
@@ -1902,14 +1847,14 @@ SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, co
         }
         hipLaunchKernelGGL(hop_concat_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d, width_w, W, R, pitch_v);
     } else if (out16 && d >= 4 && vec4_rows(hx, n_hops) && d * n_hops >= 256 && sgl::tuning("concat_lds", 1) != 0 &&
-               sgl::launch_fits((n + kConcatRows - 1) / kConcatRows * ((out_cols(d * n_hops, pad_cols, INT32_MAX) + kConcatTile - 1) / kConcatTile), 256)) {
+               sgl::launch_fits((n + kConcatRows - 1) / kConcatRows * ((sgl::out_cols(d * n_hops, pad_cols, INT32_MAX) + kConcatTile - 1) / kConcatTile), 256)) {
         // any d, long rows: assembled in LDS, every source vector read once
-        const int width_w = out_cols(d * n_hops, pad_cols, INT32_MAX);
+        const int width_w = sgl::out_cols(d * n_hops, pad_cols, INT32_MAX);
         const int tiles = (int)((width_w + kConcatTile - 1) / kConcatTile);
         hipLaunchKernelGGL(hop_concat_lds_kernel, dim3((unsigned)((n + kConcatRows - 1) / kConcatRows * tiles)), dim3(256), 0, st, hx,
                            n_hops, d_out, ldo, n, (int)d, tiles, width_w);
     } else if (out16 && d >= 4 && vec4_rows(hx, n_hops)) {   // any d: aligned 16-byte stores, aligned 16-byte loads + select
-        const int width_w = out_cols(d * n_hops, pad_cols, INT32_MAX);
+        const int width_w = sgl::out_cols(d * n_hops, pad_cols, INT32_MAX);
         const int grid = stream_grid(n * (((int64_t)width_w + 3) / 4));
         hipLaunchKernelGGL(hop_concat_any_kernel, dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d, width_w);
     } else {
@@ -1929,56 +1874,36 @@ SGL_EXPORT int sgl_nafs_padded_f32(int n_hops, const float *const *h_x, const in
                                    int64_t pad_cols, float *d_w_out, int64_t ldw, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_nafs_f32: bad sizes");
     {
-        const int prc = check_pad("sgl_nafs_padded_f32", d, d_out ? pad_cols : 0, d_out ? ldo : d);
+        const int prc = sgl::check_pad("sgl_nafs_padded_f32", d, d_out ? pad_cols : 0, d_out ? ldo : d);
         if (prc != SGL_OK) return prc;
     }
     SGL_REQUIRE(d_w_out && ldw >= n_hops, "sgl_nafs_f32: the [n, n_hops] weight buffer is required");
     Hops hx;
     bool vec4 = true;   // 16-byte row accesses with a masked tail: needs only 4-float row pitches
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
-    const int lpr = pick_lpr(d, vec4 ? 4 : 1);
+    const int lpr = sgl::pick_lpr(d, vec4 ? 4 : 1);
     const int64_t blocks = (n + (256 / lpr) - 1) / (256 / lpr);
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "row-wise kernel: too many rows for one launch (shard the matrix)");
     SGL_REQUIRE(blocks < INT32_MAX, "sgl_nafs_f32: too many rows");
     // single-pass kernel: the H hop rows of a node fit in registers (H <= 16, d <= 512, 16-byte lanes)
     const bool out_vec4 = d_out && (ldo % 4 == 0) && aligned_to(d_out, 16);
     if (vec4 && out_vec4 && n_hops <= 16 && d <= 512 && sgl::tuning("nafs_fused", 1) != 0) {
-        const RowLayout lay = pick_row_layout(d, n_hops);
-        const int64_t nblocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
-#define SGL_NF(L, C, HM) \
-    hipLaunchKernelGGL((nafs_fused_kernel<L, C, HM>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n, (int)d, out_cols(d, pad_cols, (L) * (C) * 4))
-#define SGL_NF_H(L, C) SGL_HOPS_UP_TO_16(SGL_NF, L, C)
-#define SGL_NF_H12(L, C) SGL_HOPS_UP_TO_12(SGL_NF, L, C)
-#define SGL_NF_H6(L, C) (void)0          /* 8 x 5 is never chosen for this kernel (pick_row_layout) */
-        SGL_ROWREG_DISPATCH(SGL_NF_H, SGL_NF_H12, SGL_NF_H6, lay);
-#undef SGL_NF_H6
-#undef SGL_NF_H12
-#undef SGL_NF_H
-#undef SGL_NF
+        const sgl::RowInstance in = sgl::row_instance(d, n_hops);
+        const int64_t nblocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
+        const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
+            hipLaunchKernelGGL((nafs_fused_kernel<L, C, HM>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n,
+                               (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+        });
+        if (!ok) return no_row_instance("sgl_nafs_f32", in.lpr, in.ch, n_hops);
         SGL_LAUNCH_CHECK("sgl_nafs_f32(fused)");
         return SGL_OK;
     }
-#define SGL_NW(L, V) \
-    hipLaunchKernelGGL((nafs_weight_kernel<L, V>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_w_out, ldw, n, (int)d)
-    if (vec4) {
-        switch (lpr) {
-            case 8: SGL_NW(8, 4); break;
-            case 16: SGL_NW(16, 4); break;
-            case 32: SGL_NW(32, 4); break;
-            default: SGL_NW(64, 4); break;
-        }
-    } else {
-        switch (lpr) {
-            case 8: SGL_NW(8, 1); break;
-            case 16: SGL_NW(16, 1); break;
-            case 32: SGL_NW(32, 1); break;
-            default: SGL_NW(64, 1); break;
-        }
-    }
-#undef SGL_NW
+    with_lpr_vec(lpr, vec4, [&](auto L, auto V) {
+        hipLaunchKernelGGL((nafs_weight_kernel<L, V>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_w_out, ldw, n, (int)d);
+    });
     SGL_LAUNCH_CHECK("sgl_nafs_f32(weights)");
     if (!d_out) return SGL_OK;  // weights only
     // out = sum_h W[:,h] * X_h accumulated in hop order from 0 with rounded products (over_smooth_distance_op.py:27-31)
@@ -1998,34 +1923,27 @@ SGL_EXPORT int sgl_nafs_prefix_f32(int n_hops, const float *const *h_x, const in
     SGL_REQUIRE(combine != 2 || divisor != 0.f, "sgl_nafs_prefix_f32: zero divisor");
     Hops hx;
     bool vec4 = true;
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     SGL_REQUIRE(vec4, "sgl_nafs_prefix_f32: hop rows must be 16-byte aligned with pitches that are multiples of 4 floats");
     SGL_REQUIRE(emit_mask != 0 && (n_hops == 64 || (emit_mask >> n_hops) == 0), "sgl_nafs_prefix_f32: emit_mask must name hops below n_hops");
     SGL_REQUIRE(h_out && h_ldo, "sgl_nafs_prefix_f32: NULL output arrays");
     HopsOut outs;
     const int n_out = __builtin_popcountll(emit_mask);
-    for (int k = 0; k < SGL_MAX_HOPS; ++k) {
-        outs.p[k] = k < n_out ? h_out[k] : nullptr;
-        outs.ld[k] = k < n_out ? h_ldo[k] : 0;
-        if (k < n_out) {
-            SGL_REQUIRE(outs.p[k] && outs.ld[k] >= d && outs.ld[k] % 4 == 0 && aligned_to(outs.p[k], 16),
-                        "sgl_nafs_prefix_f32: output %d must be 16-byte aligned with a pitch >= d that is a multiple of 4 floats", k);
-            const int prc = check_pad("sgl_nafs_prefix_f32", d, pad_cols, outs.ld[k]);
-            if (prc != SGL_OK) return prc;
-        }
-    }
+    rc = fill_outs(outs, n_out, h_out, h_ldo, true, d, 16,
+                   "sgl_nafs_prefix_f32: output %d must be 16-byte aligned with a pitch >= d that is a multiple of 4 floats", nullptr);
+    for (int k = 0; k < n_out && rc == SGL_OK; ++k) rc = sgl::check_pad("sgl_nafs_prefix_f32", d, pad_cols, outs.ld[k]);
+    if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
-    const RowLayout lay = pick_row_layout(d, 1);
+    const sgl::RowLayout lay = sgl::row_layout(d, 1);
     const int64_t nblocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
     if (!sgl::launch_fits(nblocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "row-wise kernel: too many rows for one launch (shard the matrix)");
-#define SGL_NP(L, C) \
-    hipLaunchKernelGGL((nafs_prefix_kernel<L, C>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, emit_mask, outs, combine, divisor, n, (int)d, out_cols(d, pad_cols, (L) * (C) * 4))
-#define SGL_NP_NONE(L, C) (void)0
-    SGL_ROWREG_DISPATCH(SGL_NP, SGL_NP, SGL_NP_NONE, lay);
-#undef SGL_NP_NONE
-#undef SGL_NP
+    const bool ok = with_row_layout<false>(lay.lpr, lay.ch, [&](auto L, auto C) {
+        hipLaunchKernelGGL((nafs_prefix_kernel<L, C>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, emit_mask, outs, combine, divisor, n,
+                           (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    });
+    if (!ok) return no_row_instance("sgl_nafs_prefix_f32", lay.lpr, lay.ch, n_hops);
     SGL_LAUNCH_CHECK("sgl_nafs_prefix_f32");
     return SGL_OK;
 }
@@ -2040,22 +1958,7 @@ static int copy_rows(const char *who, const float *d_x, int64_t ldx, int64_t n_r
                 "%s: padded rows need 16-byte aligned rows, pitches that are multiples of 4 floats and d + pad_cols a multiple of 4", who);
     const bool vec4 = (d % 4 == 0) && (ldx % 4 == 0) && (ldo % 4 == 0) && aligned_to(d_x, 16) && aligned_to(d_out, 16);
     hipStream_t st = sgl::as_stream(stream);
-    // Lanes per row: the group size that leaves the fewest lane slots idle (a row of 40 vectors -- d = 147 on its 160-float pitch --
-    // on 64 lanes idles 24 of them in every instruction; on 8 lanes x 5 iterations none, and a wavefront then has 8 rows = 8
-    // independent sets of lines in flight); ties go to the wider group (fewer iterations per row).
-    int lpr = 64;
-    {
-        const int64_t nv = (d + (vec4 ? 3 : 0)) / (vec4 ? 4 : 1);
-        int64_t best = -1;
-        for (int cand : {64, 32, 16, 8}) {
-            const int64_t waste = (nv + cand - 1) / cand * cand - nv;
-            if (best < 0 || waste < best) {
-                best = waste;
-                lpr = cand;
-            }
-        }
-        if (sgl::tuning("gather_lpr", 0) > 0) lpr = (int)sgl::tuning("gather_lpr", 0);
-    }
+    const int lpr = copy_lpr((d + (vec4 ? 3 : 0)) / (vec4 ? 4 : 1));
     // Rows per thread: a copy is three dependent memory round trips (index, row, store); a launch that needs several ROUNDS of
     // resident workgroups pays them once per round, which is what a small batch is made of (200 000 rows: 46 us against 26 us
     // for a contiguous copy of the same bytes, profiles/r05_aggregators.log).  U rows per thread -- all index loads, then all row
@@ -2068,39 +1971,14 @@ static int copy_rows(const char *who, const float *d_x, int64_t ldx, int64_t n_r
     const int64_t blocks = (n_idx + (int64_t)rpb * u - 1) / ((int64_t)rpb * u);
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: too many indices for one launch", who);
     SGL_REQUIRE(blocks < INT32_MAX, "%s: too many rows", who);
-#define SGL_GRU(L, V, UU)                                                                                                         \
-    hipLaunchKernelGGL((gather_rows_kernel<L, V, UU>), dim3((unsigned)blocks), dim3(256), 0, st, d_x, ldx, n_rows, d_idx, d_dst, n_out, \
-                       n_idx, d_out, ldo, (int)d, (int)dz)
-#define SGL_GR(L, V)                                                                                                             \
-    do {                                                                                                                         \
-        switch (u) {                                                                                                             \
-            case 16: SGL_GRU(L, V, 16); break;                                                                                   \
-            case 8: SGL_GRU(L, V, 8); break;                                                                                     \
-            case 4: SGL_GRU(L, V, 4); break;                                                                                     \
-            case 2: SGL_GRU(L, V, 2); break;                                                                                     \
-            default: SGL_GRU(L, V, 1); break;                                                                                    \
-        }                                                                                                                        \
-    } while (0)
-    if (vec4) {
-        switch (lpr) {
-            case 8: SGL_GR(8, 4); break;
-            case 16: SGL_GR(16, 4); break;
-            case 32: SGL_GR(32, 4); break;
-            default: SGL_GR(64, 4); break;
-        }
-    } else {
-        switch (lpr) {
-            case 8: SGL_GR(8, 1); break;
-            case 16: SGL_GR(16, 1); break;
-            case 32: SGL_GR(32, 1); break;
-            default: SGL_GR(64, 1); break;
-        }
-    }
-#undef SGL_GR
-#undef SGL_GRU
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sgl::fail((int)e, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
-    return SGL_OK;
+    const bool ok = with_lpr_vec(lpr, vec4, [&](auto L, auto V) {
+        with_one_of<16, 8, 4, 2, 1>(u, [&](auto U) {
+            hipLaunchKernelGGL((gather_rows_kernel<L, V, U>), dim3((unsigned)blocks), dim3(256), 0, st, d_x, ldx, n_rows, d_idx, d_dst, n_out, n_idx,
+                               d_out, ldo, (int)d, (int)dz);
+        });
+    });
+    if (!ok) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: no kernel instance for groups of %d lanes (gather_lpr: 8, 16, 32 or 64)", who, lpr);
+    return launch_check(who);
 }
 
 SGL_EXPORT int sgl_gather_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t n_idx,
@@ -2125,33 +2003,16 @@ SGL_EXPORT int sgl_gather_hops_padded_f32(int n_hops, const float *const *h_x, c
     SGL_REQUIRE(d_idx && h_out && h_ldo, "sgl_gather_hops_padded_f32: NULL arguments");
     Hops hx;
     bool vec4 = true;
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     const int64_t dw = d + pad_cols;
     HopsOut ho;
-    for (int h = 0; h < SGL_MAX_HOPS; ++h) {
-        ho.p[h] = h < n_hops ? h_out[h] : nullptr;
-        ho.ld[h] = h < n_hops ? h_ldo[h] : 0;
-        if (h < n_hops) {
-            SGL_REQUIRE(ho.p[h] && ho.ld[h] >= dw, "sgl_gather_hops_padded_f32: output %d: NULL or pitch < d + pad_cols", h);
-            if (ho.ld[h] % 4 != 0 || !aligned_to(ho.p[h], 16)) vec4 = false;
-        }
-    }
+    rc = fill_outs(ho, n_hops, h_out, h_ldo, true, dw, 0, "sgl_gather_hops_padded_f32: output %d: NULL or pitch < d + pad_cols", &vec4);
+    if (rc != SGL_OK) return rc;
     if (!vec4 || dw % 4 != 0) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_gather_hops_padded_f32: rows are not 16-byte vectors (gather hop by hop)");
     hipStream_t st = sgl::as_stream(stream);
-    const int64_t nv = dw / 4;
-    int lpr = 64;
-    {
-        int64_t best = -1;
-        for (int cand : {64, 32, 16, 8}) {
-            const int64_t waste = (nv + cand - 1) / cand * cand - nv;
-            if (best < 0 || waste < best) {
-                best = waste;
-                lpr = cand;
-            }
-        }
-        if (sgl::tuning("gather_lpr", 0) > 0) lpr = (int)sgl::tuning("gather_lpr", 0);
-    }
+    const int lpr = copy_lpr(dw / 4);
+    const auto no_lpr = [&] { return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_gather_hops_padded_f32: no kernel instance for groups of %d lanes (gather_lpr: 8, 16, 32 or 64)", lpr); };
     const int rpb = 256 / lpr;
     if (sgl::tuning("gather_hops_grid", 1) != 0 && n_hops <= 65535) {
         // hop in blockIdx.y (gather_hops_y_kernel), the default.  Per launch with ten launches queued, 200 000 rows (profiles/
@@ -2162,25 +2023,13 @@ SGL_EXPORT int sgl_gather_hops_padded_f32(int n_hops, const float *const *h_x, c
         if (uy != 1 && uy != 2 && uy != 4 && uy != 8) uy = 4;
         const int64_t by = (n_idx + (int64_t)rpb * uy - 1) / ((int64_t)rpb * uy);
         if (!sgl::launch_fits(by * n_hops, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_gather_hops_padded_f32: too many indices for one launch");
-#define SGL_GY(L, UU) hipLaunchKernelGGL((gather_hops_y_kernel<L, UU>), dim3((unsigned)by, (unsigned)n_hops), dim3(256), 0, st, hx, ho, n_rows, d_idx, n_idx, (int)dw, (int)d)
-#define SGL_GYU(L)                     \
-    do {                               \
-        if (uy == 1) SGL_GY(L, 1);     \
-        else if (uy == 2) SGL_GY(L, 2); \
-        else if (uy == 8) SGL_GY(L, 8); \
-        else SGL_GY(L, 4);             \
-    } while (0)
-        switch (lpr) {
-            case 8: SGL_GYU(8); break;
-            case 16: SGL_GYU(16); break;
-            case 32: SGL_GYU(32); break;
-            default: SGL_GYU(64); break;
-        }
-#undef SGL_GYU
-#undef SGL_GY
-        hipError_t ey = hipGetLastError();
-        if (ey != hipSuccess) return sgl::fail((int)ey, "sgl_gather_hops_padded_f32: kernel launch failed: %s", hipGetErrorString(ey));
-        return SGL_OK;
+        const bool ok = with_lpr(lpr, [&](auto L) {
+            with_one_of<1, 2, 4, 8>(uy, [&](auto U) {
+                hipLaunchKernelGGL((gather_hops_y_kernel<L, U>), dim3((unsigned)by, (unsigned)n_hops), dim3(256), 0, st, hx, ho, n_rows, d_idx, n_idx,
+                                   (int)dw, (int)d);
+            });
+        });
+        return ok ? launch_check("sgl_gather_hops_padded_f32") : no_lpr();
     }
     // gather_hops_grid = 0: the first form, a hop loop inside the thread (3-8 % slower than the grid form above, kept for comparison).
     // one row per thread: with HB = 4 hops per batch a thread already keeps 4 independent row loads in flight, and the grid stays
@@ -2190,24 +2039,13 @@ SGL_EXPORT int sgl_gather_hops_padded_f32(int n_hops, const float *const *h_x, c
     if (u != 1 && u != 2 && u != 4) u = 1;
     const int64_t blocks = (n_idx + (int64_t)rpb * u - 1) / ((int64_t)rpb * u);
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_gather_hops_padded_f32: too many indices for one launch");
-#define SGL_GH(L, UU) hipLaunchKernelGGL((gather_hops_kernel<L, UU, 4>), dim3((unsigned)blocks), dim3(256), 0, st, hx, ho, n_hops, n_rows, d_idx, n_idx, (int)dw, (int)d)
-#define SGL_GHU(L)                   \
-    do {                             \
-        if (u == 1) SGL_GH(L, 1);    \
-        else if (u == 4) SGL_GH(L, 4); \
-        else SGL_GH(L, 2);           \
-    } while (0)
-    switch (lpr) {
-        case 8: SGL_GHU(8); break;
-        case 16: SGL_GHU(16); break;
-        case 32: SGL_GHU(32); break;
-        default: SGL_GHU(64); break;
-    }
-#undef SGL_GHU
-#undef SGL_GH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sgl::fail((int)e, "sgl_gather_hops_padded_f32: kernel launch failed: %s", hipGetErrorString(e));
-    return SGL_OK;
+    const bool ok = with_lpr(lpr, [&](auto L) {
+        with_one_of<1, 2, 4>(u, [&](auto U) {
+            hipLaunchKernelGGL((gather_hops_kernel<L, U, 4>), dim3((unsigned)blocks), dim3(256), 0, st, hx, ho, n_hops, n_rows, d_idx, n_idx, (int)dw,
+                               (int)d);
+        });
+    });
+    return ok ? launch_check("sgl_gather_hops_padded_f32") : no_lpr();
 }
 
 // out[dst[i], :] = X[src[i], :], i < n_idx (dst entries distinct; every index is range-checked in the kernel, which traps on a
@@ -2309,12 +2147,12 @@ static int hop_gate_impl(bool device_bias_sentinel, int n_hops, const float *con
                          int64_t ldg, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_gate_f32: bad sizes");
     {
-        const int prc = check_pad("sgl_hop_gate_padded_f32", d, pad_cols, ldo);
+        const int prc = sgl::check_pad("sgl_hop_gate_padded_f32", d, pad_cols, ldo);
         if (prc != SGL_OK) return prc;
     }
     Hops hx;
     bool vec4 = aligned_to(d_vec, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_vec && d_out && ldo >= d, "sgl_hop_gate_f32: bad arguments");
@@ -2322,24 +2160,19 @@ static int hop_gate_impl(bool device_bias_sentinel, int n_hops, const float *con
     if (!(vec4 && n_hops <= 16 && d <= 512 && ldo % 4 == 0 && aligned_to(d_out, 16)))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_gate_f32: needs <= 16 hops, d <= 512 and 16-byte aligned rows (use the two-pass route)");
     hipStream_t st = sgl::as_stream(stream);
-    const RowLayout lay = pick_row_layout(d, n_hops);
-    const int64_t blocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
+    const sgl::RowInstance in = sgl::row_instance(d, n_hops);
+    const int64_t blocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_gate_f32: too many rows for one launch (shard the matrix)");
     // bias = NaN: the bias is the float that follows the padded vector on the device (d_vec[round_up(d, 4)]) -- a caller whose
     // bias is a device tensor (a torch parameter) needs neither a device-to-host synchronisation nor a new value per launch
     // Only the *_padded entry point reads it that way: a caller of the un-suffixed sgl_hop_gate_f32 whose d_vec holds exactly
     // round_up(d, 4) floats and whose (diverged) bias is NaN gets NaN outputs, as the scalar semantics say, not a read past its vector.
     const float *bias_ptr = (device_bias_sentinel && bias != bias) ? d_vec + (d + 3) / 4 * 4 : nullptr;
-#define SGL_GF(L, C, HM) \
-    hipLaunchKernelGGL((gate_fused_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_vec, bias, bias_ptr, d_out, ldo, d_w_out, ldw, d_g_out, ldg, n, (int)d, out_cols(d, pad_cols, (L) * (C) * 4))
-#define SGL_GF_H(L, C) SGL_HOPS_UP_TO_16(SGL_GF, L, C)
-#define SGL_GF_H12(L, C) SGL_HOPS_UP_TO_12(SGL_GF, L, C)
-#define SGL_GF_H6(L, C) (void)0          /* 8 x 5 is never chosen for this kernel (pick_row_layout) */
-    SGL_ROWREG_DISPATCH(SGL_GF_H, SGL_GF_H12, SGL_GF_H6, lay);
-#undef SGL_GF_H6
-#undef SGL_GF_H12
-#undef SGL_GF_H
-#undef SGL_GF
+    const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((gate_fused_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_vec, bias, bias_ptr, d_out, ldo,
+                           d_w_out, ldw, d_g_out, ldg, n, (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    });
+    if (!ok) return no_row_instance("sgl_hop_gate_f32", in.lpr, in.ch, n_hops);
     SGL_LAUNCH_CHECK("sgl_hop_gate_f32");
     return SGL_OK;
 }
@@ -2364,12 +2197,12 @@ SGL_EXPORT int sgl_hop_recursive_f32(int n_hops, const float *const *h_x, const 
                                      int64_t lda, float *d_c_out, int64_t ldc, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_recursive_f32: bad sizes");
     {
-        const int prc = check_pad("sgl_hop_recursive_f32", d, pad_cols, ldo);
+        const int prc = sgl::check_pad("sgl_hop_recursive_f32", d, pad_cols, ldo);
         if (prc != SGL_OK) return prc;
     }
     Hops hx;
     bool vec4 = aligned_to(d_vec, 16);
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_vec && d_out && ldo >= d, "sgl_hop_recursive_f32: bad arguments");
@@ -2378,21 +2211,16 @@ SGL_EXPORT int sgl_hop_recursive_f32(int n_hops, const float *const *h_x, const 
     if (!(vec4 && n_hops <= 16 && d <= 512 && ldo % 4 == 0 && aligned_to(d_out, 16)))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_recursive_f32: needs <= 16 hops, d <= 512 and 16-byte aligned rows (use the step-by-step route)");
     hipStream_t st = sgl::as_stream(stream);
-    const RowLayout lay = pick_row_layout(d, n_hops);
-    const int64_t blocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
+    const sgl::RowInstance in = sgl::row_instance(d, n_hops);
+    const int64_t blocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_recursive_f32: too many rows for one launch (shard the matrix)");
     const int dv = (int)((d + 3) / 4 * 4);
     const float *bias_ptr = (bias != bias) ? d_vec + 2 * dv : nullptr;
-#define SGL_RF(L, C, HM) \
-    hipLaunchKernelGGL((recursive_fused_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_vec, dv, bias, bias_ptr, d_out, ldo, d_w_out, ldw, d_a_out, lda, d_c_out, ldc, n, (int)d, out_cols(d, pad_cols, (L) * (C) * 4))
-#define SGL_RF_H(L, C) SGL_HOPS_UP_TO_16(SGL_RF, L, C)
-#define SGL_RF_H12(L, C) SGL_HOPS_UP_TO_12(SGL_RF, L, C)
-#define SGL_RF_H6(L, C) (void)0          /* 8 x 5 is never chosen for this kernel (pick_row_layout) */
-    SGL_ROWREG_DISPATCH(SGL_RF_H, SGL_RF_H12, SGL_RF_H6, lay);
-#undef SGL_RF_H6
-#undef SGL_RF_H12
-#undef SGL_RF_H
-#undef SGL_RF
+    const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((recursive_fused_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_vec, dv, bias, bias_ptr, d_out,
+                           ldo, d_w_out, ldw, d_a_out, lda, d_c_out, ldc, n, (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    });
+    if (!ok) return no_row_instance("sgl_hop_recursive_f32", in.lpr, in.ch, n_hops);
     SGL_LAUNCH_CHECK("sgl_hop_recursive_f32");
     return SGL_OK;
 }
@@ -2411,13 +2239,10 @@ SGL_EXPORT int sgl_hop_recursive_bwd_f32(int n_hops, const float *d_a, int64_t l
     const int64_t blocks = (n + 255) / 256;
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_recursive_bwd_f32: too many rows for one launch");
     const float *bias_ptr = (bias != bias) ? d_bias : nullptr;
-#define SGL_RB(HM) \
-    hipLaunchKernelGGL((recursive_scalar_bwd_kernel<HM>), dim3((unsigned)blocks), dim3(256), 0, st, n_hops, d_a, lda, d_c, ldc, bias, bias_ptr, d_gw, ldg, d_da, ldda, d_dc, lddc, d_db, n)
-    if (n_hops <= 4) SGL_RB(4);
-    else if (n_hops <= 8) SGL_RB(8);
-    else if (n_hops <= 12) SGL_RB(12);
-    else SGL_RB(16);
-#undef SGL_RB
+    with_hop_capacity(n_hops, [&](auto HM) {
+        hipLaunchKernelGGL((recursive_scalar_bwd_kernel<HM>), dim3((unsigned)blocks), dim3(256), 0, st, n_hops, d_a, lda, d_c, ldc, bias, bias_ptr, d_gw,
+                           ldg, d_da, ldda, d_dc, lddc, d_db, n);
+    });
     SGL_LAUNCH_CHECK("sgl_hop_recursive_bwd_f32");
     return SGL_OK;
 }
@@ -2428,7 +2253,7 @@ SGL_EXPORT int sgl_hop_rowdot2_f32(int n_hops, const float *const *h_x, const in
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_rowdot2_f32: bad sizes");
     Hops hx;
     bool vec4 = aligned_to(d_vec, 16) && (!d_u || (aligned_to(d_u, 16) && ldu % 4 == 0));
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     SGL_REQUIRE(h0 >= 0 && h0 <= h1 && h1 <= n_hops, "sgl_hop_rowdot2_f32: bad hop range");
     if (n == 0) return SGL_OK;
@@ -2438,20 +2263,15 @@ SGL_EXPORT int sgl_hop_rowdot2_f32(int n_hops, const float *const *h_x, const in
     if (!(vec4 && n_hops <= 16 && d <= 512 && d > 0))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_rowdot2_f32: needs <= 16 hops, 0 < d <= 512 and 16-byte aligned rows");
     hipStream_t st = sgl::as_stream(stream);
-    const RowLayout lay = pick_row_layout(d, n_hops, true);
-    const int64_t blocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
+    const sgl::RowInstance in = sgl::row_instance(d, n_hops, true);
+    const int64_t blocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_rowdot2_f32: too many rows for one launch (shard the matrix)");
     float *a_out = u_mask ? d_a : nullptr;
-#define SGL_R2(L, C, HM) \
-    hipLaunchKernelGGL((hop_rowdot2_reg_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_u, ldu, (unsigned long long)u_mask, d_vec, h0, h1, d_p, ldp, a_out, n, (int)d)
-#define SGL_R2_H(L, C) SGL_HOPS_UP_TO_16(SGL_R2, L, C)
-#define SGL_R2_H12(L, C) SGL_HOPS_UP_TO_12(SGL_R2, L, C)
-#define SGL_R2_H6(L, C) SGL_HOPS_UP_TO_6(SGL_R2, L, C)
-    SGL_ROWREG_DISPATCH(SGL_R2_H, SGL_R2_H12, SGL_R2_H6, lay);
-#undef SGL_R2_H6
-#undef SGL_R2_H12
-#undef SGL_R2_H
-#undef SGL_R2
+    const bool ok = with_row_instance<true>(in, [&](auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((hop_rowdot2_reg_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_u, ldu,
+                           (unsigned long long)u_mask, d_vec, h0, h1, d_p, ldp, a_out, n, (int)d);
+    });
+    if (!ok) return no_row_instance("sgl_hop_rowdot2_f32", in.lpr, in.ch, n_hops);
     SGL_LAUNCH_CHECK("sgl_hop_rowdot2_f32");
     return SGL_OK;
 }
@@ -2478,7 +2298,7 @@ SGL_EXPORT int sgl_hop_colsum_f32(int n_hops, const float *const *h_x, const int
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_colsum_f32: bad sizes");
     Hops hx;
     bool vec4 = true;
-    int rc = fill_hops(hx, n_hops, h_x, h_ldx, d, vec4);
+    int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
     if (rc != SGL_OK) return rc;
     SGL_REQUIRE(d_out && ldo >= d, "sgl_hop_colsum_f32: bad output");
     SGL_REQUIRE(sw == 0 || sw == 1, "sgl_hop_colsum_f32: sw must be 0 (one weight per row) or 1 (one per row and hop)");
@@ -2495,12 +2315,9 @@ SGL_EXPORT int sgl_hop_colsum_f32(int n_hops, const float *const *h_x, const int
     const int slots = (int)((d + 3) / 4);
     const int64_t per = colsum_per_block(n, slots);
     const int blocks = (int)std::max<int64_t>(1, (n + per - 1) / per);
-#define SGL_CS(HM) hipLaunchKernelGGL((hop_colsum_partial_kernel<HM>), dim3(blocks), dim3(256), 0, st, hx, n_hops, d_w, ldw, sw, d_scratch, n, (int)d, slots, per)
-    if (n_hops <= 4) SGL_CS(4);
-    else if (n_hops <= 8) SGL_CS(8);
-    else if (n_hops <= 12) SGL_CS(12);
-    else SGL_CS(16);
-#undef SGL_CS
+    with_hop_capacity(n_hops, [&](auto HM) {
+        hipLaunchKernelGGL((hop_colsum_partial_kernel<HM>), dim3(blocks), dim3(256), 0, st, hx, n_hops, d_w, ldw, sw, d_scratch, n, (int)d, slots, per);
+    });
     SGL_LAUNCH_CHECK("sgl_hop_colsum_f32(partial)");
     hipLaunchKernelGGL(hop_colsum_final_kernel, dim3(n_hops * slots), dim3(64), 0, st, d_scratch, blocks, n_hops, slots, d_out, ldo, (int)d);
     SGL_LAUNCH_CHECK("sgl_hop_colsum_f32(final)");

@@ -360,20 +360,7 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fu
 // what every entry checks before anything touches a device; the hop table for the kernels
 int fill_hops_bf16(const char *who, HopsB &hx, int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, int64_t n, int64_t d) {
     if (n < 0 || d <= 0 || d >= INT32_MAX) return sgl::fail(SGL_ERR_INVALID, "%s: bad sizes (n=%lld, d=%lld)", who, (long long)n, (long long)d);
-    if (n_hops < 1 || n_hops > SGL_MAX_HOPS) return sgl::fail(SGL_ERR_INVALID, "%s: n_hops=%d outside [1,%d]", who, n_hops, SGL_MAX_HOPS);
-    if (!h_x) return sgl::fail(SGL_ERR_INVALID, "%s: NULL hop pointer array", who);
-    for (int h = 0; h < n_hops; ++h) {
-        hx.p[h] = h_x[h];
-        hx.ld[h] = h_ldx ? h_ldx[h] : d;
-        if (!hx.p[h]) return sgl::fail(SGL_ERR_INVALID, "%s: hop %d: NULL pointer", who, h);
-        if (hx.ld[h] < d) return sgl::fail(SGL_ERR_INVALID, "%s: hop %d: leading dimension %lld < d", who, h, (long long)hx.ld[h]);
-        if (!aligned_to(hx.p[h], 2)) return sgl::fail(SGL_ERR_INVALID, "%s: hop %d: pointer not 2-byte aligned", who, h);
-    }
-    for (int h = n_hops; h < SGL_MAX_HOPS; ++h) {
-        hx.p[h] = nullptr;
-        hx.ld[h] = 0;
-    }
-    return SGL_OK;
+    return fill_hops(who, hx, n_hops, h_x, h_ldx, d, 2, nullptr);
 }
 
 // every hop row starts on a multiple of `bytes` (2 * elems): pointers aligned, pitches multiples of elems
@@ -381,14 +368,6 @@ bool hop_rows_aligned(const HopsB &hx, int n_hops, int elems) {
     for (int h = 0; h < n_hops; ++h)
         if (hx.ld[h] % elems != 0 || !aligned_to(hx.p[h], 2 * (size_t)elems)) return false;
     return true;
-}
-
-int stream_blocks(int64_t total_threads) {      // one lane access per thread; the grid-stride loop is the overflow path (stream_grid)
-    int64_t blocks = (total_threads + 255) / 256;
-    const int64_t cap = sgl::tuning("agg_blocks", 0) > 0 ? sgl::tuning("agg_blocks", 0) : ((int64_t)1 << 22);
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
 }
 
 int concat_impl(const char *who, int ob, int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, void *d_out, int64_t ldo,
@@ -406,19 +385,13 @@ int concat_impl(const char *who, int ob, int n_hops, const uint16_t *const *h_x,
     const int64_t dw = width + pad_cols;
     const bool fast = hop_rows_aligned(hx, n_hops, 4) && ldo % 4 == 0 && aligned_to(d_out, 4 * (size_t)ob);
     hipStream_t st = sgl::as_stream(stream);
-    const int grid = stream_blocks(n * (fast ? (dw + 3) / 4 : dw));
-#define SGL_CC(OB, V) hipLaunchKernelGGL((hop_concat_bf16_kernel<OB, V>), dim3(grid), dim3(256), 0, st, hx, d_out, ldo, n, (int)d, (int)width, (int)dw)
-    if (ob == 2) {
-        if (fast) SGL_CC(2, 4);
-        else SGL_CC(2, 1);
-    } else {
-        if (fast) SGL_CC(4, 4);
-        else SGL_CC(4, 1);
-    }
-#undef SGL_CC
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sgl::fail((int)e, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
-    return SGL_OK;
+    const int grid = stream_grid(n * (fast ? (dw + 3) / 4 : dw));
+    with_one_of<2, 4>(ob, [&](auto OB) {
+        with_vec(fast, [&](auto V) {
+            hipLaunchKernelGGL((hop_concat_bf16_kernel<OB, V>), dim3(grid), dim3(256), 0, st, hx, d_out, ldo, n, (int)d, (int)width, (int)dw);
+        });
+    });
+    return launch_check(who);
 }
 
 }  // namespace
@@ -445,24 +418,12 @@ SGL_EXPORT int sgl_hop_reduce_bf16_f32(int op, int n_hops, const uint16_t *const
         }
     }
     hipStream_t st = sgl::as_stream(stream);
-    const int grid = stream_blocks(n * ((dw + bv - 1) / bv));
-#define SGL_RB(OP, B) hipLaunchKernelGGL((hop_reduce_bf16_kernel<OP, B>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, d_out, ldo, n, (int)d, (int)dw)
-#define SGL_RED(OP)                    \
-    do {                               \
-        if (bv == 8) SGL_RB(OP, 8);    \
-        else if (bv == 4) SGL_RB(OP, 4); \
-        else if (bv == 2) SGL_RB(OP, 2); \
-        else SGL_RB(OP, 1);            \
-    } while (0)
-    switch (op) {
-        case SGL_REDUCE_SUM: SGL_RED(SGL_REDUCE_SUM); break;
-        case SGL_REDUCE_MEAN: SGL_RED(SGL_REDUCE_MEAN); break;
-        case SGL_REDUCE_MAX: SGL_RED(SGL_REDUCE_MAX); break;
-        case SGL_REDUCE_MIN: SGL_RED(SGL_REDUCE_MIN); break;
-        default: SGL_RED(SGL_REDUCE_WSUM); break;
-    }
-#undef SGL_RED
-#undef SGL_RB
+    const int grid = stream_grid(n * ((dw + bv - 1) / bv));
+    with_one_of<SGL_REDUCE_SUM, SGL_REDUCE_MEAN, SGL_REDUCE_MAX, SGL_REDUCE_MIN, SGL_REDUCE_WSUM>(op, [&](auto OP) {
+        with_one_of<8, 4, 2, 1>(bv, [&](auto BV) {
+            hipLaunchKernelGGL((hop_reduce_bf16_kernel<OP, BV>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_w, d_out, ldo, n, (int)d, (int)dw);
+        });
+    });
     SGL_LAUNCH_CHECK("sgl_hop_reduce_bf16_f32");
     return SGL_OK;
 }
@@ -483,7 +444,7 @@ SGL_EXPORT int sgl_nafs_bf16_f32(int n_hops, const uint16_t *const *h_x, const i
     HopsB hx;
     int rc = fill_hops_bf16(who, hx, n_hops, h_x, h_ldx, n, d);
     if (rc != SGL_OK) return rc;
-    rc = check_pad(who, d, pad_cols, ldo);
+    rc = sgl::check_pad(who, d, pad_cols, ldo);
     if (rc != SGL_OK) return rc;
     SGL_REQUIRE(d_out && aligned_to(d_out, 4), "%s: bad output", who);
     SGL_REQUIRE(!d_w_out || ldw >= n_hops, "%s: the weight matrix needs a pitch of at least n_hops", who);
@@ -497,20 +458,15 @@ SGL_EXPORT int sgl_nafs_bf16_f32(int n_hops, const uint16_t *const *h_x, const i
         return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the output needs 16-byte aligned rows on a pitch that is a multiple of 4: widen the hops and use sgl_nafs_padded_f32", who);
     if (sgl::tuning("nafs_fused", 1) == 0)
         return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the fused kernel is switched off (nafs_fused = 0): widen the hops and use sgl_nafs_padded_f32", who);
-    const RowLayout lay = pick_row_layout(d, n_hops);
-    const int64_t nblocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
+    const sgl::RowInstance in = sgl::row_instance(d, n_hops);
+    const int64_t nblocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
     if (!sgl::launch_fits(nblocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: too many rows for one launch (shard the matrix)", who);
     hipStream_t st = sgl::as_stream(stream);
-#define SGL_NB(L, C, HM) \
-    hipLaunchKernelGGL((nafs_bf16_fused_kernel<L, C, HM>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n, (int)d, out_cols(d, pad_cols, (L) * (C) * 4))
-#define SGL_NB_H(L, C) SGL_HOPS_UP_TO_16(SGL_NB, L, C)
-#define SGL_NB_H12(L, C) SGL_HOPS_UP_TO_12(SGL_NB, L, C)
-#define SGL_NB_H6(L, C) (void)0          /* 8 x 5 is never chosen for this kernel (pick_row_layout) */
-    SGL_ROWREG_DISPATCH(SGL_NB_H, SGL_NB_H12, SGL_NB_H6, lay);
-#undef SGL_NB_H6
-#undef SGL_NB_H12
-#undef SGL_NB_H
-#undef SGL_NB
+    const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((nafs_bf16_fused_kernel<L, C, HM>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n,
+                           (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    });
+    if (!ok) return no_row_instance(who, in.lpr, in.ch, n_hops);
     SGL_LAUNCH_CHECK("sgl_nafs_bf16_f32");
     return SGL_OK;
 }

@@ -88,6 +88,19 @@ constexpr int unroll_of(int group, int nch, int ulevel) {
     return ulevel == 2 ? uh * 2 / (nch == 1 ? 1 : 2) : ulevel == 3 ? ((nch == 1 && group == 64) ? 32 : uh) : ulevel == 0 ? uh / 2 : uh;
 }
 
+// ---- row rule (host, sgl_core.cpp): lanes x chunks of the register-resident row kernels, one rule for float32 and bfloat16 hops ----
+struct RowLayout {
+    int lpr, ch;         // lanes per row x 16-byte chunks per lane
+};
+struct RowInstance {
+    int lpr, ch, hmax;   // hmax: the even hop capacity of the compiled instance; 0 = the layout has none for this hop count
+};
+int pick_lpr(int64_t d, int vec);                                    // the smallest of 8 / 16 / 32 / 64 lanes that covers ceil(d / vec)
+RowLayout row_layout(int64_t d, int n_hops, bool allow_8x5 = false);  // reads the tuning keys row_lpr32x2, row_narrow_groups
+RowInstance row_instance(int64_t d, int n_hops, bool allow_8x5 = false);
+int out_cols(int64_t d, int64_t pad, int64_t room);                  // columns a row kernel writes; reads row_whole_lines
+int check_pad(const char *who, int64_t width, int64_t pad, int64_t ldo);
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // A HIP launch carries at most 2^32 - 1 threads per grid dimension; beyond that the launch is silently truncated on this

@@ -1,4 +1,5 @@
-// Host-only part of libsgl_hip.so: error text, tuning knobs, the SpMM launch rule and the SpMM execution-plan builder.
+// Host-only part of libsgl_hip.so: error text, tuning knobs, the SpMM launch rule, the row rule of the register-resident
+// aggregator kernels and the SpMM execution-plan builder.
 // No device code here, so these entry points work (and are unit-tested) on a machine without a GPU.
 #include <algorithm>
 #include <atomic>
@@ -121,6 +122,80 @@ SpmmLayout spmm_layout(int lanes, bool strict, int64_t nnz, int64_t n_rows, bool
     L.waves = (int)tuning("spmm_waves", 0);
     if (L.waves != 1 && L.waves != 2 && L.waves != 4) L.waves = 4;
     return L;
+}
+
+// ---- row rule: lanes x chunks of a register-resident row kernel (sgl_rows.h dispatches on what these return) -----------------
+int pick_lpr(int64_t d, int vec) {
+    const int64_t lanes = (d + vec - 1) / vec;
+    int lpr = 8;
+    while (lpr < lanes && lpr < 64) lpr <<= 1;
+    return lpr;
+}
+
+// A row of d floats is ceil(d / 4) 16-byte slots; LPR lanes take CH slots each (slot (c * LPR + l) of the row for lane l, chunk c),
+// 64 / LPR rows per wavefront.  Power-of-two groups leave slots idle when the row is not a power of two wide, and idle slots still
+// cost their share of every load and VALU instruction: d = 147 (BASELINE config 3: 100 features + 47 label columns = 37 slots) on
+// 32 lanes x 2 chunks idles 27 of 64.  Narrow groups with more chunks per lane fit such rows far better -- 8 lanes x 5 chunks
+// (40 slots, 8 rows per wavefront, every load instruction of a lane group is one whole 128-byte line) or 16 x 3 (48 slots) -- at
+// the price of CH x HMAX hop vectors in registers, so they are instantiated for few hops only (<= 6 / <= 12) and chosen when they
+// at least halve the idle slots.  Measured at d = 147 (profiles/r04_aggregators_layouts.log): 16 x 3 is as fast as 32 x 2 at 6 hops
+// and 12-15 % faster at 11 (row-dot 0.597 -> 0.661 of peak, gate 0.539 -> 0.613, NAFS 0.536 -> 0.612); 8 x 5 (151 VGPRs, 3 waves
+// per SIMD) pays only in the jk-score kernel (0.585 -> 0.657 at 6 hops) and is instantiated for that kernel alone (allow_8x5).  At
+// 6 hops the gate / NAFS kernels are NOT issue-bound -- halving their VALU instructions and quartering their wavefronts changed
+// nothing (profiles/r04_agg_pmc.md) -- what they lost against the plain sum was the partly written last line of the output row
+// (store_row of sgl_rows.h, out_cols below).
+static const int kNarrow[2][3] = {{16, 3, 12}, {8, 5, 6}};       // lanes, chunks, most hops instantiated
+
+RowLayout row_layout(int64_t d, int n_hops, bool allow_8x5) {
+    RowLayout r;
+    r.lpr = pick_lpr(d, 4);
+    r.ch = (d > r.lpr * 4) ? 2 : 1;
+    if (r.lpr == 64 && r.ch == 1 && d > 128 && tuning("row_lpr32x2", 1) != 0) {   // 2 rows per wavefront
+        r.lpr = 32;
+        r.ch = 2;
+    }
+    if (tuning("row_narrow_groups", 1) != 0 && d <= r.lpr * 4 * r.ch) {
+        const int slots = (int)((d + 3) / 4);
+        const int64_t mode = tuning("row_narrow_groups", 1);       // 1: both candidates, 2: 16 x 3 only, 3: 8 x 5 only (measurements)
+        for (const auto &c : kNarrow) {
+            const int idle = c[0] * c[1] - slots;
+            if (((mode == 2 || !allow_8x5) && c[0] == 8) || (mode == 3 && c[0] == 16)) continue;
+            if (idle >= 0 && n_hops <= c[2] && 2 * idle <= r.lpr * r.ch - slots) {
+                r.lpr = c[0];
+                r.ch = c[1];
+            }
+        }
+    }
+    return r;
+}
+
+// the compiled instance that serves n_hops in the layout: every even hop capacity up to 16 for the wide layouts, up to 12 / 6 for
+// the narrow groups (CH x HMAX hop vectors live in registers)
+RowInstance row_instance(int64_t d, int n_hops, bool allow_8x5) {
+    const RowLayout r = row_layout(d, n_hops, allow_8x5);
+    int most = 16;
+    for (const auto &c : kNarrow)
+        if (r.lpr == c[0] && r.ch == c[1]) most = c[2];
+    const int hmax = (n_hops < 1 || n_hops > most) ? 0 : std::max(2, (n_hops + 1) / 2 * 2);
+    return RowInstance{r.lpr, r.ch, hmax};
+}
+
+// Columns a row-producing kernel writes: the d data columns plus the `pad` columns after them that the CALLER declared to be the
+// row's own padding (the *_padded_f32 entry points; sgl_amd.device passes the tail of the pitch of the outputs it allocates) --
+// written as zeros, so that every line of the row is written whole.  The kernels never guess: with pad = 0 nothing beyond column
+// d is touched.  `room` = the columns the lane layout reaches.
+int out_cols(int64_t d, int64_t pad, int64_t room) {
+    int64_t dw = tuning("row_whole_lines", 1) != 0 ? d + pad : d;
+    if (dw > room) dw = room > d ? room / 4 * 4 : d;
+    if (dw > d && dw % 4 != 0) dw = d;              // (validated by the entry points: d + pad is a whole number of vectors)
+    return (int)dw;
+}
+
+int check_pad(const char *who, int64_t width, int64_t pad, int64_t ldo) {
+    if (pad < 0 || width + pad > ldo) return fail(SGL_ERR_INVALID, "%s: pad_cols=%lld does not fit the output pitch", who, (long long)pad);
+    if (pad > 0 && ((width + pad) % 4 != 0 || ldo % 4 != 0))
+        return fail(SGL_ERR_INVALID, "%s: padded rows must be whole 16-byte vectors (width + pad_cols and ldo multiples of 4)", who);
+    return SGL_OK;
 }
 
 // Issue order of the work items.  An item closes when it reaches item_nnz non-zeros, so one that ends in a heavy row holds up

@@ -4,7 +4,7 @@
 // like the SpMM and the row gathers: E x (2 d x 4 + 16 + 4) bytes, no reuse the kernel could arrange (what reuse there is -- a node
 // with many edges -- is the caches').
 //
-// Layout.  LPR lanes (8 / 16 / 32 / 64: pick_lpr of sgl_rows.h) own one edge, 256 / LPR edge groups per workgroup, U edges per group:
+// Layout.  LPR lanes (8 / 16 / 32 / 64: sgl::pick_lpr) own one edge, 256 / LPR edge groups per workgroup, U edges per group:
 // a group first loads its U index pairs, then for every chunk of LPR vectors issues the 2 U row loads before any arithmetic (the
 // U-unroll of gather_rows_kernel: 2 U independent 16-byte loads per lane in flight), accumulates per lane with fmaf, elements 0..3
 // of a vector in order, chunk after chunk, and finally sums the group's lanes with group_sum<LPR> (DPP / permlane: no LDS).
@@ -140,30 +140,15 @@ SGL_EXPORT int sgl_edge_dot_f32(const float *d_a, int64_t lda, int64_t n_a, cons
         return SGL_OK;
     }
     const bool vec4 = lda % 4 == 0 && ldb % 4 == 0 && aligned_to(d_a, 16) && aligned_to(d_b, 16);
-    const int lpr = pick_lpr(d, vec4 ? 4 : 1);
+    const int lpr = sgl::pick_lpr(d, vec4 ? 4 : 1);
     const int64_t per_block = (int64_t)(256 / lpr) * kEdgesPerGroup;
     const int64_t blocks = (n_edges + per_block - 1) / per_block;
     if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_edge_dot_f32: too many edges for one launch (split the list)");
     const int e16 = aligned_to(d_edges, 16) ? 1 : 0;
-#define SGL_ED(L, V)                                                                                                            \
-    hipLaunchKernelGGL((edge_dot_kernel<L, V, kEdgesPerGroup>), dim3((unsigned)blocks), dim3(256), 0, st, d_a, lda, n_a, d_b, ldb, \
-                       n_b, d_edges, e16, n_edges, (int)d, d_out)
-    if (vec4) {
-        switch (lpr) {
-            case 8: SGL_ED(8, 4); break;
-            case 16: SGL_ED(16, 4); break;
-            case 32: SGL_ED(32, 4); break;
-            default: SGL_ED(64, 4); break;
-        }
-    } else {
-        switch (lpr) {
-            case 8: SGL_ED(8, 1); break;
-            case 16: SGL_ED(16, 1); break;
-            case 32: SGL_ED(32, 1); break;
-            default: SGL_ED(64, 1); break;
-        }
-    }
-#undef SGL_ED
+    with_lpr_vec(lpr, vec4, [&](auto L, auto V) {
+        hipLaunchKernelGGL((edge_dot_kernel<L, V, kEdgesPerGroup>), dim3((unsigned)blocks), dim3(256), 0, st, d_a, lda, n_a, d_b, ldb, n_b, d_edges,
+                           e16, n_edges, (int)d, d_out);
+    });
     SGL_LAUNCH_CHECK("sgl_edge_dot_f32");
     return SGL_OK;
 }

@@ -1,7 +1,10 @@
-// Lanes, layouts and launch tables of the register-resident row kernels, shared by sgl_aggregate.hip (float32 hops) and
-// sgl_aggregate_bf16.hip (bfloat16 hops): both files must pick the same lane layout and sum in the same lane order for their
-// results to be bit-identical, so the rule and the in-wavefront reductions exist once, here.  Not part of the ABI.
+// Device helpers and typed launch dispatch of the row kernels, shared by sgl_aggregate.hip (float32 hops), sgl_aggregate_bf16.hip
+// (bfloat16 hops) and sgl_edge.hip: both aggregator files must pick the same lane layout and sum in the same lane order for their
+// results to be bit-identical, so the in-wavefront reductions exist once, here, and the layout rule once in sgl_core.cpp
+// (sgl::row_layout / sgl::row_instance: pure host arithmetic, checked on the CPU).  Not part of the ABI.
 #pragma once
+#include <type_traits>
+
 #include "sgl_common.h"
 
 namespace {
@@ -77,23 +80,6 @@ __device__ __forceinline__ float group_sum(float v) {
 // (v_permlane32_swap exchanges; 8 waves, but 0.57 / 0.48 vs 0.67 / 0.62) -- profiles/r03_aggregators_{online_gate,hop_split}_experiment.log.
 #define ROWREG_MIN_BLOCKS(HMAX, CH) (((HMAX) * (CH) <= 8) ? 8 : (((HMAX) * (CH) <= 16) ? 4 : 2))
 
-// ---- lanes x chunks of a register-resident row kernel ------------------------------------------------------------------------
-// A row of d floats is ceil(d / 4) 16-byte slots; LPR lanes take CH slots each (slot (c * LPR + l) of the row for lane l, chunk c),
-// 64 / LPR rows per wavefront.  Power-of-two groups leave slots idle when the row is not a power of two wide, and idle slots still
-// cost their share of every load and VALU instruction: d = 147 (BASELINE config 3: 100 features + 47 label columns = 37 slots) on
-// 32 lanes x 2 chunks idles 27 of 64.  Narrow groups with more chunks per lane fit such rows far better -- 8 lanes x 5 chunks
-// (40 slots, 8 rows per wavefront, every load instruction of a lane group is one whole 128-byte line) or 16 x 3 (48 slots) -- at
-// the price of CH x HMAX hop vectors in registers, so they are instantiated for few hops only (<= 6 / <= 12) and chosen when they
-// at least halve the idle slots.  Measured at d = 147 (profiles/r04_aggregators_layouts.log): 16 x 3 is as fast as 32 x 2 at 6 hops
-// and 12-15 % faster at 11 (row-dot 0.597 -> 0.661 of peak, gate 0.539 -> 0.613, NAFS 0.536 -> 0.612); 8 x 5 (151 VGPRs, 3 waves
-// per SIMD) pays only in the jk-score kernel (0.585 -> 0.657 at 6 hops) and is instantiated for that kernel alone.  At 6 hops the
-// gate / NAFS kernels are NOT issue-bound -- halving their VALU instructions and quartering their wavefronts changed nothing
-// (profiles/r04_agg_pmc.md) -- what they lost against the plain sum was the partly written last line of the output row
-// (store_row below).
-struct RowLayout {
-    int lpr, ch;
-};
-
 // ---- per-row scalars, one hop per lane -------------------------------------------------------------------------------------
 // After the row reductions every lane of a row's group holds all H per-hop scalars.  Evaluating sigmoid / softmax / the IEEE
 // divisions hop after hop costs H instruction sequences per WAVEFRONT (every lane repeats them): ~1 050 VALU instructions at
@@ -129,7 +115,7 @@ __device__ __forceinline__ float group_max(float v) {
 }
 
 // Output row of a register-resident row kernel.  dw = the columns the kernel writes: exactly d, or -- when the caller declared the
-// tail of the row's pitch to be padding (out_cols() below) -- d + pad, the pad columns as zeros.  Why: a row of d = 147 floats on a
+// tail of the row's pitch to be padding (sgl::out_cols) -- d + pad, the pad columns as zeros.  Why: a row of d = 147 floats on a
 // 160-float pitch ends 52 bytes short of its last 128-byte line, and a line that is only partly written costs a read-modify-write in
 // the ECC-protected HBM: the output write of the gate / NAFS kernels ran at 2.7 TB/s at d = 147 against 5.8 TB/s at d = 160
 // (profiles/r04_aggregators.log; the element-wise kernels always streamed whole pitches).
@@ -160,98 +146,109 @@ __device__ __forceinline__ void store_row(float *__restrict__ orow, const f4 (&a
     }
 }
 
-int pick_lpr(int64_t d, int vec) {
-    const int64_t lanes = (d + vec - 1) / vec;
-    int lpr = 8;
-    while (lpr < lanes && lpr < 64) lpr <<= 1;
-    return lpr;
+// ---- host side: run-time values as compile-time arguments of a generic lambda ----------------------------------------------------
+// Each helper calls f with std::integral_constant arguments (usable as template arguments inside the lambda) and returns whether it
+// called it: a value with no compiled instance launches nothing and the entry point reports it.
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+template <int... Vs, typename F>
+bool with_one_of(int v, F &&f) {   // f(Int<V>) for the V of the list that equals v
+    return ((v == Vs ? (f(Int<Vs>{}), true) : false) || ...);
+}
+template <typename F>
+bool with_lpr(int lpr, F &&f) {   // lanes per row
+    return with_one_of<8, 16, 32, 64>(lpr, f);
+}
+template <typename F>
+bool with_lpr_vec(int lpr, bool vec4, F &&f) {   // f(lanes per row, floats per lane access)
+    return vec4 ? with_lpr(lpr, [&](auto L) { f(L, Int<4>{}); }) : with_lpr(lpr, [&](auto L) { f(L, Int<1>{}); });
+}
+template <typename F>
+bool with_bool(bool b, F &&f) {
+    b ? f(std::true_type{}) : f(std::false_type{});
+    return true;
+}
+template <typename F>
+bool with_vec(bool vec4, F &&f) {   // floats per lane access
+    vec4 ? f(Int<4>{}) : f(Int<1>{});
+    return true;
+}
+template <typename F>
+bool with_hop_capacity(int n, F &&f) {   // kernels that keep per-hop values of up to 4 / 8 / 12 / 16 hops in registers
+    return with_one_of<4, 8, 12, 16>(n <= 4 ? 4 : (n + 3) / 4 * 4, f);
 }
 
-// Columns a row-producing kernel writes: the d data columns plus the `pad` columns after them that the CALLER declared to be the
-// row's own padding (the *_padded_f32 entry points; sgl_amd.device passes the tail of the pitch of the outputs it allocates) --
-// written as zeros, so that every line of the row is written whole.  The kernels never guess: with pad = 0 nothing beyond column
-// d is touched.  `room` = the columns the lane layout reaches.
-int out_cols(int64_t d, int64_t pad, int64_t room) {
-    int64_t dw = sgl::tuning("row_whole_lines", 1) != 0 ? d + pad : d;
-    if (dw > room) dw = room > d ? room / 4 * 4 : d;
-    if (dw > d && dw % 4 != 0) dw = d;              // (validated by the entry points: d + pad is a whole number of vectors)
-    return (int)dw;
+// f(LPR, CH) for a layout of sgl::row_layout.  HAS_8X5: the kernel family has 8 x 5 instances (hop_rowdot2_reg_kernel alone).
+template <bool HAS_8X5, typename F>
+bool with_row_layout(int lpr, int ch, F &&f) {
+    if (ch == 5) {
+        if constexpr (HAS_8X5) return with_one_of<8>(lpr, [&](auto L) { f(L, Int<5>{}); });
+        return false;
+    }
+    if (ch == 3) return with_one_of<16>(lpr, [&](auto L) { f(L, Int<3>{}); });
+    if (ch == 2) return with_one_of<32, 64>(lpr, [&](auto L) { f(L, Int<2>{}); });
+    return ch == 1 && with_lpr(lpr, [&](auto L) { f(L, Int<1>{}); });
+}
+// f(LPR, CH, HMAX) for an instance of sgl::row_instance: every even capacity up to 16, 12 (16 x 3) or 6 (8 x 5) hop vectors
+template <bool HAS_8X5, typename F>
+bool with_row_instance(const sgl::RowInstance &in, F &&f) {
+    bool called = false;
+    with_row_layout<HAS_8X5>(in.lpr, in.ch, [&](auto L, auto C) {
+        if constexpr (C == 5) called = with_one_of<2, 4, 6>(in.hmax, [&](auto HM) { f(L, C, HM); });
+        else if constexpr (C == 3) called = with_one_of<2, 4, 6, 8, 10, 12>(in.hmax, [&](auto HM) { f(L, C, HM); });
+        else called = with_one_of<2, 4, 6, 8, 10, 12, 14, 16>(in.hmax, [&](auto HM) { f(L, C, HM); });
+    });
+    return called;
+}
+// what an entry point answers when one of the two did not call its lambda
+inline int no_row_instance(const char *who, int lpr, int ch, int n_hops) {
+    return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: no kernel instance is compiled for the %d x %d lane layout with %d hops", who, lpr, ch, n_hops);
 }
 
-int check_pad(const char *who, int64_t width, int64_t pad, int64_t ldo) {
-    if (pad < 0 || width + pad > ldo) return sgl::fail(SGL_ERR_INVALID, "%s: pad_cols=%lld does not fit the output pitch", who, (long long)pad);
-    if (pad > 0 && ((width + pad) % 4 != 0 || ldo % 4 != 0))
-        return sgl::fail(SGL_ERR_INVALID, "%s: padded rows must be whole 16-byte vectors (width + pad_cols and ldo multiples of 4)", who);
+// The hop table of a kernel (Hops, HopsB: p[], ld[]) from the caller's arrays.  who: prefix of the error texts (NULL: none);
+// align: bytes of one element; *vec4 (optional) is cleared where the rows of a float hop are not 16-byte vectors.
+template <typename Table, typename T>
+int fill_hops(const char *who, Table &hx, int n_hops, const T *const *h_x, const int64_t *h_ldx, int64_t d, int align, bool *vec4) {
+    const char *sep = who ? ": " : "";
+    if (!who) who = "";
+    if (n_hops < 1 || n_hops > SGL_MAX_HOPS) return sgl::fail(SGL_ERR_INVALID, "%s%sn_hops=%d outside [1,%d]", who, sep, n_hops, SGL_MAX_HOPS);
+    if (!h_x) return sgl::fail(SGL_ERR_INVALID, "%s%sNULL hop pointer array", who, sep);
+    for (int h = 0; h < n_hops; ++h) {
+        hx.p[h] = h_x[h];
+        hx.ld[h] = h_ldx ? h_ldx[h] : d;
+        if (!hx.p[h]) return sgl::fail(SGL_ERR_INVALID, "%s%shop %d: NULL pointer", who, sep, h);
+        if (hx.ld[h] < d) return sgl::fail(SGL_ERR_INVALID, "%s%shop %d: leading dimension %lld < d", who, sep, h, (long long)hx.ld[h]);
+        if (!aligned_to(hx.p[h], (size_t)align)) return sgl::fail(SGL_ERR_INVALID, "%s%shop %d: pointer not %d-byte aligned", who, sep, h, align);
+        if (vec4 && (hx.ld[h] % 4 != 0 || !aligned_to(hx.p[h], 16))) *vec4 = false;
+    }
+    for (int h = n_hops; h < SGL_MAX_HOPS; ++h) {
+        hx.p[h] = nullptr;
+        hx.ld[h] = 0;
+    }
     return SGL_OK;
 }
 
-RowLayout pick_row_layout(int64_t d, int n_hops, bool allow_8x5 = false) {
-    RowLayout r;
-    r.lpr = pick_lpr(d, 4);
-    r.ch = (d > r.lpr * 4) ? 2 : 1;
-    if (r.lpr == 64 && r.ch == 1 && d > 128 && sgl::tuning("row_lpr32x2", 1) != 0) {   // 2 rows per wavefront
-        r.lpr = 32;
-        r.ch = 2;
-    }
-    if (sgl::tuning("row_narrow_groups", 1) != 0 && d <= r.lpr * 4 * r.ch) {
-        const int slots = (int)((d + 3) / 4);
-        static const int cand[2][3] = {{16, 3, 12}, {8, 5, 6}};       // lanes, chunks, most hops instantiated
-        const int64_t mode = sgl::tuning("row_narrow_groups", 1);       // 1: both candidates, 2: 16 x 3 only, 3: 8 x 5 only (measurements)
-        for (const auto &c : cand) {
-            const int idle = c[0] * c[1] - slots;
-            if (((mode == 2 || !allow_8x5) && c[0] == 8) || (mode == 3 && c[0] == 16)) continue;
-            if (idle >= 0 && n_hops <= c[2] && 2 * idle <= r.lpr * r.ch - slots) {
-                r.lpr = c[0];
-                r.ch = c[1];
-            }
-        }
-    }
-    return r;
+inline int stream_grid(int64_t total_threads) {
+    // memory-bound elementwise: one 16-byte element per thread.  Measured on MI355X (products shape, 5 streams): a
+    // 2048-block grid-stride launch reaches 5.3 TB/s, one element per thread 5.9 TB/s (torch's add: 6.0); the
+    // grid-stride loop only remains as the overflow path for > 2^22 blocks.
+    int64_t blocks = (total_threads + 255) / 256;
+    const int64_t cap = sgl::tuning("agg_blocks", 0) > 0 ? sgl::tuning("agg_blocks", 0) : ((int64_t)1 << 22);
+    if (blocks > cap) blocks = cap;
+    if (blocks < 1) blocks = 1;
+    return (int)blocks;
 }
 
-// KH(L, C): all even hop counts up to 16; KH12 / KH6: the narrow-group layouts, instantiated up to 12 / 6 hop vectors
-#define SGL_ROWREG_DISPATCH(KH, KH12, KH6, lay)                        \
-    do {                                                               \
-        if ((lay).lpr == 8 && (lay).ch == 5) KH6(8, 5);                \
-        else if ((lay).lpr == 16 && (lay).ch == 3) KH12(16, 3);        \
-        else if ((lay).lpr == 32 && (lay).ch == 2) KH(32, 2);          \
-        else if ((lay).ch == 2) KH(64, 2);                             \
-        else if ((lay).lpr == 8) KH(8, 1);                             \
-        else if ((lay).lpr == 16) KH(16, 1);                           \
-        else if ((lay).lpr == 32) KH(32, 1);                           \
-        else KH(64, 1);                                                \
-    } while (0)
-#define SGL_HOPS_UP_TO_16(K, L, C)                 \
-    do {                                           \
-        if (n_hops <= 2) K(L, C, 2);               \
-        else if (n_hops <= 4) K(L, C, 4);          \
-        else if (n_hops <= 6) K(L, C, 6);          \
-        else if (n_hops <= 8) K(L, C, 8);          \
-        else if (n_hops <= 10) K(L, C, 10);        \
-        else if (n_hops <= 12) K(L, C, 12);        \
-        else if (n_hops <= 14) K(L, C, 14);        \
-        else K(L, C, 16);                          \
-    } while (0)
-#define SGL_HOPS_UP_TO_12(K, L, C)                 \
-    do {                                           \
-        if (n_hops <= 2) K(L, C, 2);               \
-        else if (n_hops <= 4) K(L, C, 4);          \
-        else if (n_hops <= 6) K(L, C, 6);          \
-        else if (n_hops <= 8) K(L, C, 8);          \
-        else if (n_hops <= 10) K(L, C, 10);        \
-        else K(L, C, 12);                          \
-    } while (0)
-#define SGL_HOPS_UP_TO_6(K, L, C)                  \
-    do {                                           \
-        if (n_hops <= 2) K(L, C, 2);               \
-        else if (n_hops <= 4) K(L, C, 4);          \
-        else K(L, C, 6);                           \
-    } while (0)
-
-#define SGL_LAUNCH_CHECK(what)                                                                                  \
-    do {                                                                                                        \
-        hipError_t _e = hipGetLastError();                                                                      \
-        if (_e != hipSuccess) return sgl::fail((int)_e, what ": kernel launch failed: %s", hipGetErrorString(_e)); \
+inline int launch_check(const char *who) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return sgl::fail((int)e, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    return SGL_OK;
+}
+#define SGL_LAUNCH_CHECK(who)               \
+    do {                                    \
+        const int _rc = launch_check(who);  \
+        if (_rc != SGL_OK) return _rc;      \
     } while (0)
 
 }  // namespace

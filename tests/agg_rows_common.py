@@ -1,10 +1,11 @@
 """Shared by the row-register aggregator tests (test_agg_rows_cpu.py, test_gpu_agg_variants.py); no GPU and no torch needed to
 import it.
 
-Restatements, each made ONCE here, of what csrc/sgl_aggregate.hip decides on its own for the kernels that keep the hop rows of
-a node in registers:
+Restatements, each made ONCE here, of what the library (csrc/sgl_core.cpp) decides on its own for the kernels that keep the hop
+rows of a node in registers:
   * pick_lpr / pick_row_layout   the lane layout (lanes per row, 16-byte chunks per lane) for a row width and hop count
-  * hmax_of                      the hop capacity an instance is compiled for (SGL_HOPS_UP_TO_16 / _12 / _6)
+                                 (sgl::pick_lpr / sgl::row_layout)
+  * hmax_of                      the hop capacity an instance is compiled for (sgl::row_instance)
   * expected_kernel              the template instance an entry point launches, or None where it takes its general path
   * compiled_variants            every template instance the launch tables can reach
 plus the parser of these kernels' names as a profiler reports them, and the tuning keys that enter the rule."""
@@ -29,9 +30,9 @@ TUNING_VALUES = {"row_lpr32x2": (0, 1), "row_narrow_groups": (0, 1, 2, 3), "row_
 MAX_REG_HOPS = 16                 # "H <= 16, d <= 512": the entry points' test for the register-resident kernels
 MAX_REG_WIDTH = 512
 
-WIDE_LAYOUTS = ((8, 1), (16, 1), (32, 1), (64, 1), (32, 2), (64, 2))      # SGL_ROWREG_DISPATCH: KH, hop counts up to 16
-NARROW_16X3 = (16, 3)                                                       # KH12: up to 12
-NARROW_8X5 = (8, 5)                                                         # KH6: up to 6, hop_rowdot2_reg_kernel only
+WIDE_LAYOUTS = ((8, 1), (16, 1), (32, 1), (64, 1), (32, 2), (64, 2))      # with_row_instance of csrc/sgl_rows.h: hop counts up to 16
+NARROW_16X3 = (16, 3)                                                       # up to 12
+NARROW_8X5 = (8, 5)                                                         # up to 6, hop_rowdot2_reg_kernel only
 
 
 def pick_lpr(d, vec):
@@ -68,7 +69,7 @@ def _row_layout(d, n_hops, allow_8x5, lpr32x2, mode):
 
 
 def hmax_of(layout, n_hops):
-    """SGL_HOPS_UP_TO_16 / _12 / _6: the even hop capacity of the instance that serves n_hops in this layout; None where the
+    """sgl::row_instance: the even hop capacity of the instance that serves n_hops in this layout; None where the
     table of the layout has no such row (pick_row_layout never sends such a hop count there)"""
     most = 6 if layout == NARROW_8X5 else 12 if layout == NARROW_16X3 else 16
     if n_hops < 1 or n_hops > most:

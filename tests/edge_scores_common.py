@@ -17,7 +17,7 @@ _NAME = re.compile(KERNEL)
 
 
 def pick_lpr(d, vec):
-    """pick_lpr of sgl_rows.h: the smallest of 8 / 16 / 32 / 64 lanes that covers ceil(d / vec) lane accesses (64 when none does)"""
+    """sgl::pick_lpr (csrc/sgl_core.cpp): the smallest of 8 / 16 / 32 / 64 lanes that covers ceil(d / vec) lane accesses (64 when none does)"""
     lanes = (d + vec - 1) // vec
     lpr = 8
     while lpr < lanes and lpr < 64:

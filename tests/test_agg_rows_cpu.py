@@ -1,8 +1,11 @@
 """The restated dispatch rule of the row-register aggregator kernels (agg_rows_common.py), pinned without a GPU: the layout cells
-as csrc/sgl_aggregate.hip documents them, that the rule only ever names compiled instances, that every compiled instance is
-reachable from some (d, H, tuning) -- so the case list of test_gpu_agg_variants.py can reach all of them -- and the parser of
-the kernel names a profiler reports."""
+as csrc/sgl_core.cpp documents them, that the rule only ever names compiled instances, that every compiled instance is
+reachable from some (d, H, tuning) -- so the case list of test_gpu_agg_variants.py can reach all of them -- that the library's own
+rule (sgl::row_instance, host code built with g++) equals the restatement, and the parser of the kernel names a profiler reports."""
 import itertools
+import os
+import shutil
+import subprocess
 
 import pytest
 
@@ -117,6 +120,50 @@ def test_general_path_boundaries(family):
         assert expected_kernel(family, 147, 40) == ("prefix", (16, 3))      # any hop count, the layout of one hop
     else:
         assert expected_kernel(family, 100, 17) is None
+
+
+def test_library_row_rule_equals_the_restatement(tmp_path):
+    """sgl::row_instance / sgl::out_cols (csrc/sgl_core.cpp: pure host code), built with g++ into tests/native/agg_rows_table.cpp
+    and asked once for every d in 1 .. 520, every hop count in 1 .. 17, 8 x 5 allowed or not, and every value of the three tuning
+    keys one key at a time: (lpr, ch) is pick_row_layout's, hmax is hmax_of's with 0 exactly where that is None, and every answer
+    with hmax > 0 is a compiled instance of the family that may (rowdot2) or may not (nafs) use 8 x 5.  out_cols, for 0 / 3 / 13
+    declared pad columns and the room of the layout: the d data columns, plus the pad when row_whole_lines is set, as far as the
+    layout's lanes reach, and then only as whole 16-byte vectors."""
+    from conftest import ROOT
+    gxx = shutil.which("g++")
+    if gxx is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime.h"):
+        pytest.skip("needs g++ and the HIP headers")
+    exe = str(tmp_path / "agg_rows_table")
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                        os.path.join(ROOT, "tests", "native", "agg_rows_table.cpp"), os.path.join(ROOT, "sgl_amd", "csrc", "sgl_core.cpp"),
+                        "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath,/opt/rocm/lib", "-pthread", "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    keys = ("row_lpr32x2", "row_narrow_groups", "row_whole_lines")
+    tunings = [{}] + [{k: v} for k in keys for v in TUNING_VALUES[k]]
+    cases = [(d, H, allow, pad, t) for t in tunings for allow in (0, 1) for d in range(1, 521) for H in range(1, 18) for pad in (0, 3, 13)]
+    queries = [f"{d} {H} {allow} {pad} " + " ".join(str(t.get(k, TUNING_DEFAULTS[k])) for k in keys) for d, H, allow, pad, t in cases]
+    r = subprocess.run([exe], input="\n".join(queries) + "\n", capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = [tuple(int(v) for v in line.split()) for line in r.stdout.splitlines()]
+    assert len(got) == len(cases) == 9 * 2 * 520 * 17 * 3
+    compiled = {0: compiled_variants("nafs"), 1: compiled_variants("rowdot2")}
+    seen, none_seen = {0: set(), 1: set()}, 0
+    for (d, H, allow, pad, t), (lpr, ch, hmax, cols) in zip(cases, got):
+        lay = pick_row_layout(d, H, bool(allow), t)
+        want = hmax_of(lay, H)
+        assert (lpr, ch) == lay and hmax == (0 if want is None else want), ((d, H, allow, t), (lpr, ch, hmax), lay, want)
+        none_seen += want is None
+        if hmax > 0:
+            assert (lpr, ch, hmax) in compiled[allow], ((d, H, allow, t), (lpr, ch, hmax))
+            seen[allow].add((lpr, ch, hmax))
+        room, dw = lpr * ch * 4, d + pad if t.get("row_whole_lines", 1) else d
+        if dw > room:
+            dw = room // 4 * 4 if room > d else d
+        if dw > d and dw % 4:
+            dw = d
+        assert cols == dw, ((d, H, allow, pad, t), cols, dw)
+    assert seen == compiled                                   # the queries reach every instance of both tables
+    assert none_seen == 9 * 2 * 520 * 3                       # 17 hops: no layout has an instance, whatever the keys say
 
 
 def test_kernel_name_parser():

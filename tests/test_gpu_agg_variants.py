@@ -3,7 +3,7 @@ MI355X: run with `-m gpu`.
 
 hop_rowdot_reg_kernel (the dW of hop_wsum2d), nafs_fused_kernel, gate_fused_kernel, recursive_fused_kernel, hop_rowdot2_reg_kernel
 and nafs_prefix_kernel keep the hop rows of a node in registers and are compiled per lane layout (LPR lanes x CH chunks per row)
-and hop capacity HMAX.  Which instance an entry point launches is decided by pick_row_layout and the SGL_HOPS_UP_TO_* tables from
+and hop capacity HMAX.  Which instance an entry point launches is decided by sgl::row_instance (csrc/sgl_core.cpp) from
 the width, the hop count and three tuning keys; that rule is restated in agg_rows_common.expected_kernel, and every launch made
 here is checked against the name of the kernel that really ran, as the profiler reports it (Trace).  Each family's test ends with
 "the instances seen are exactly the compiled ones".
