@@ -238,12 +238,26 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def hop_arrays(tensors):
+def leading_dim(t, one_row=None):
+    """The leading dimension (in elements) to pass for a [n, d] row-major matrix: its row stride.  A matrix of at most one row has no
+    pitch the kernels ever step by, and torch reports whatever the view was cut from; for it `one_row` is passed, by default the
+    row length d (at least 1).  Two callers pass another value there and keep it: hop_arrays the larger of d and the reported stride
+    (a one-row view of a padded buffer keeps its pitch in the hop table), device.column_signature round_up(d, 4) (the width its
+    kernel reads).  The three differ for a one-row view of a padded buffer, so they cannot be one rule without changing an argument
+    that reaches the library."""
+    if t.shape[0] > 1:
+        return t.stride(0)
+    return max(t.shape[1], 1) if one_row is None else one_row
+
+
+def hop_arrays(tensors, one_row_pitch=True):
     """(host array of device pointers, host array of leading dimensions in elements) for a list of 2-D row-major
-    CUDA tensors (column stride 1)."""
+    CUDA tensors (column stride 1).  A None entry (an optional output nobody asked for) gives a null pointer and a leading dimension
+    of 0.  one_row_pitch=False: a one-row matrix gets leading_dim's default (its row length) instead of the pitch it was cut from --
+    what the gradient buffers of the backward kernels have always been passed with."""
     n = len(tensors)
-    ptrs = (c_void_p * n)(*[t.data_ptr() for t in tensors])
-    lds = (c_int64 * n)(*[t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)) for t in tensors])
+    ptrs = (c_void_p * n)(*[None if t is None else t.data_ptr() for t in tensors])
+    lds = (c_int64 * n)(*[0 if t is None else leading_dim(t, max(t.shape[1], t.stride(0)) if one_row_pitch else None) for t in tensors])
     return ptrs, lds
 
 

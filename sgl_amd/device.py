@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import check, current_stream_ptr, lib, ptr
+from ._lib import leading_dim as _ld
 
 __all__ = [
     "DeviceCSR", "default_long_row_nnz", "ChainGraph", "round_up", "row_pitch", "expected_lines", "alloc_rows", "upload_rows", "normalize_adj",
@@ -27,6 +28,9 @@ def round_up(x, m):
 
 
 HOP_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
+# hop aggregate kind -> (SGL_REDUCE_* code of the aggregator kernels, accumulate mode of the SpMM epilogue or None where it has none)
+HOP_KINDS = {"sum": (_lib.SGL_REDUCE_SUM, 0), "mean": (_lib.SGL_REDUCE_MEAN, None), "wsum": (_lib.SGL_REDUCE_WSUM, 1),
+             "max": (_lib.SGL_REDUCE_MAX, 2), "min": (_lib.SGL_REDUCE_MIN, 3)}
 
 
 def hop_torch_dtype(dtype):
@@ -42,6 +46,62 @@ def hop_torch_dtype(dtype):
 
 def _esize(dtype):
     return 2 if dtype == torch.bfloat16 else 4
+
+
+# entry points whose last argument is not a stream
+_NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
+                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch"})
+
+
+def _call(device, name, *args, raw=False):
+    """One call of the library entry point `name` on `device` (None: whichever is current): the symbol is looked up on lib() when the
+    call is made, the current stream of that device is appended for the entry points that take one, and the return code is checked
+    under the same name.  raw=True hands the return value back unchecked (the scratch sizes; the two callers that branch on
+    SGL_ERR_UNSUPPORTED).  Nothing here synchronises, allocates or touches a tensor: callers run under hipGraph capture."""
+    with torch.cuda.device(device):
+        if name not in _NO_STREAM:
+            args += (current_stream_ptr(),)
+        rc = getattr(lib(), name)(*args)
+    if raw:
+        return rc
+    check(rc, name)
+
+
+def _opt_ptr(t):
+    return ptr(t) if t is not None else None
+
+
+# ---- row layout: the three questions every launch asks about a [n, d] matrix.  Pure functions of shape, strides, storage offset,
+# element size, base address and storage size (no is_cuda, no dtype test: those stay with the caller, like the column stride)
+def pitch_vectored(t):
+    """is the row stride, as torch reports it (for a single row too), a whole number of 16-byte vectors?"""
+    return t.stride(0) % (16 // t.element_size()) == 0
+
+
+def rows_vectored(t, single_row=False, width=None, room=False):
+    """Are the rows of t 16-byte vectors -- base address and row pitch multiples of 16 bytes?  single_row: does a matrix of at most
+    one row pass (its pitch is never stepped by)?  width: the columns the pitch has to cover (None: not asked; callers pass
+    round_up(d, 4) when the kernel reads or writes the vector that straddles column d).  room: the storage must hold `width` columns
+    of the LAST row too (that vector is read there as well)."""
+    n = t.shape[0]
+    if t.data_ptr() % 16:
+        return False
+    if n > 1:
+        if not pitch_vectored(t) or (width is not None and t.stride(0) < width):
+            return False
+    elif not single_row:
+        return False
+    if room:
+        have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        return have >= (n - 1) * t.stride(0) * (n > 1) + width
+    return True
+
+
+def own_out_pad(ld, d):
+    """The pad_cols of a float32 output WE allocated on a pitch of ld (alloc_rows) and hand to a gather kernel: the whole tail of the
+    pitch while that is under 32 columns (every line of a row is then written whole), else up to the next 16-byte vector.  What
+    lies beyond is zeroed by the caller."""
+    return ld - d if ld - d < 32 else round_up(d, 4) - d
 
 
 def expected_lines(ld, d, elem_size=4):
@@ -98,11 +158,8 @@ def alloc_rows(n, d, device, zero_pad=True, dtype=torch.float32):
 def own_pad(t):
     """pad columns of an output WE allocated with alloc_rows (the tail of its pitch): what the *_padded_f32 entry points may write
     as zeros so that every line of a row is written whole; 0 for anything that is not a padded [n, d] view with 16-byte rows"""
-    n, d = t.shape
-    if n <= 1:
-        return 0
-    ld = t.stride(0)
-    return ld - d if (ld > d and (ld * t.element_size()) % 16 == 0 and t.stride(1) == 1 and t.data_ptr() % 16 == 0) else 0
+    d, ld = t.shape[1], t.stride(0)
+    return ld - d if (rows_vectored(t) and ld > d and t.stride(1) == 1) else 0
 
 
 def padded_parent(t):
@@ -173,9 +230,7 @@ def permute_rows(rowptr, col, val, perm):
     out_ptr = torch.empty(n + 1, dtype=torch.int64, device=rowptr.device)
     out_col = torch.empty_like(col)
     out_val = torch.empty_like(val)
-    with torch.cuda.device(rowptr.device):
-        check(lib().sgl_csr_permute_rows(ptr(rowptr), ptr(col), ptr(val), n, ptr(perm), ptr(out_ptr), ptr(out_col), ptr(out_val),
-                                         current_stream_ptr()), "sgl_csr_permute_rows")
+    _call(rowptr.device, "sgl_csr_permute_rows", ptr(rowptr), ptr(col), ptr(val), n, ptr(perm), ptr(out_ptr), ptr(out_col), ptr(out_val))
     return out_ptr, out_col, out_val
 
 
@@ -186,8 +241,7 @@ def download_rows(t):
     if src.numel() * 4 < _STAGED_MIN_BYTES:
         host.copy_(src)
         return host
-    with torch.cuda.device(src.device):
-        check(lib().sgl_download(host.data_ptr(), ptr(src), src.numel() * 4, current_stream_ptr()), "sgl_download")
+    _call(src.device, "sgl_download", host.data_ptr(), ptr(src), src.numel() * 4)
     return host
 
 
@@ -208,10 +262,6 @@ def _check_mat(t, name, bf16=False):
         raise ValueError(f"{name} must be row-major (column stride 1)")
     if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
         raise ValueError(f"{name}: row stride smaller than the row length")
-
-
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1)
 
 
 def _same_hop_dtype(who, *tensors):
@@ -270,10 +320,8 @@ class DeviceCSR:
         self.strict = bool(strict)
         flags = (_lib.SGL_CSR_STRICT_ORDER if strict else 0) | (0 if xcd_remap else _lib.SGL_CSR_NO_XCD_REMAP)
         h = c_void_p()
-        with torch.cuda.device(self.device):
-            check(lib().sgl_csr_create(ctypes.byref(h), self.shape[0], self.shape[1], self.nnz, ptr(rowptr), ptr(col),
-                                       ptr(val), flags, int(item_nnz), int(long_row_nnz), current_stream_ptr()),
-                  "sgl_csr_create")
+        _call(self.device, "sgl_csr_create", ctypes.byref(h), self.shape[0], self.shape[1], self.nnz, ptr(rowptr), ptr(col), ptr(val),
+              flags, int(item_nnz), int(long_row_nnz))
         self._h = h
 
     @classmethod
@@ -292,7 +340,7 @@ class DeviceCSR:
         """same sparsity structure, new values (another normalisation of the same graph): the execution plan is kept"""
         if not (val.is_cuda and val.dtype == torch.float32 and val.dim() == 1 and val.is_contiguous() and val.numel() == self.nnz):
             raise TypeError("val must be a contiguous float32 CUDA tensor with one entry per non-zero")
-        check(lib().sgl_csr_set_values(self._h, ptr(val)), "sgl_csr_set_values")
+        _call(None, "sgl_csr_set_values", self._h, ptr(val))
         self.val = val
         return self
 
@@ -304,15 +352,13 @@ class DeviceCSR:
         if rowmap is not None and not (rowmap.is_cuda and rowmap.dtype == torch.int32 and rowmap.dim() == 1
                                        and rowmap.is_contiguous() and rowmap.numel() == self.shape[0]):
             raise TypeError("rowmap must be a contiguous int32 CUDA tensor with one entry per row")
-        with torch.cuda.device(self.device):
-            check(lib().sgl_csr_set_rowmap(self._h, ptr(rowmap) if rowmap is not None else None, current_stream_ptr()),
-                  "sgl_csr_set_rowmap")
+        _call(self.device, "sgl_csr_set_rowmap", self._h, _opt_ptr(rowmap))
         self.rowmap = rowmap
         return self
 
     def info(self):
         a = (c_int64 * 8)()
-        check(lib().sgl_csr_info(self._h, a), "sgl_csr_info")
+        _call(None, "sgl_csr_info", self._h, a)
         keys = ("n_rows", "n_cols", "nnz", "n_items", "n_pieces", "n_long_rows", "flags", "workspace_bytes")
         return dict(zip(keys, list(a)))
 
@@ -334,17 +380,13 @@ class DeviceCSR:
         if _same_hop_dtype("spmm", x, out) == torch.bfloat16:
             if accumulate:
                 raise ValueError("spmm: bfloat16 hops have no accumulate form")
-            with torch.cuda.device(self.device):
-                check(lib().sgl_spmm_bf16(self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, current_stream_ptr()), "sgl_spmm_bf16")
-            _wrote(out)
-            return out
-        with torch.cuda.device(self.device):
-            check(lib().sgl_spmm_f32(self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, int(bool(accumulate)),
-                                     current_stream_ptr()), "sgl_spmm_f32")
+            _call(self.device, "sgl_spmm_bf16", self._h, ptr(x), _ld(x), ptr(out), _ld(out), d)
+        else:
+            _call(self.device, "sgl_spmm_f32", self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, int(bool(accumulate)))
         _wrote(out)
         return out
 
-    ACC_MODES = {"sum": 0, "wsum": 1, "max": 2, "min": 3}
+    ACC_MODES = {kind: acc for kind, (_, acc) in HOP_KINDS.items() if acc is not None}
 
     def spmm_acc(self, x, out, acc, w=1.0, weighted=False, divisor=1.0, mode=None):
         """out = A @ x and, in the same kernel, acc <- acc + out (weighted: acc + w * out), then acc / divisor if
@@ -356,11 +398,9 @@ class DeviceCSR:
         _check_mat(acc, "acc")
         if x.shape[0] != self.shape[1] or out.shape != (self.shape[0], x.shape[1]) or acc.shape != out.shape:
             raise ValueError("Dimension mismatch detected for the adjacency and the feature matrix!")
-        fn, name = ((lib().sgl_spmm_acc_bf16, "sgl_spmm_acc_bf16") if _same_hop_dtype("spmm_acc", x, out) == torch.bfloat16
-                    else (lib().sgl_spmm_acc_f32, "sgl_spmm_acc_f32"))     # bf16 hops: acc stays float32 and takes the ROUNDED out
-        with torch.cuda.device(self.device):
-            check(fn(self._h, ptr(x), _ld(x), ptr(out), _ld(out), x.shape[1], ptr(acc), _ld(acc),
-                                         float(w), mode, float(divisor), current_stream_ptr()), name)
+        bf16 = _same_hop_dtype("spmm_acc", x, out) == torch.bfloat16        # bf16 hops: acc stays float32 and takes the ROUNDED out
+        _call(self.device, "sgl_spmm_acc_bf16" if bf16 else "sgl_spmm_acc_f32", self._h, ptr(x), _ld(x), ptr(out), _ld(out), x.shape[1],
+              ptr(acc), _ld(acc), float(w), mode, float(divisor))
         _wrote(out, acc)
         return out
 
@@ -376,13 +416,10 @@ class DeviceCSR:
         if not 1 <= n_out <= 8:
             raise ValueError("between 1 and 8 output replicas are supported")
         arr = (c_void_p * n_out)(*[int(p) for p in out_ptrs])
-        with torch.cuda.device(self.device):
-            if row_mask is not None and not (row_mask.is_cuda and row_mask.dtype == torch.uint8 and row_mask.is_contiguous()
-                                             and row_mask.numel() == self.shape[0]):
-                raise ValueError("row_mask must be a contiguous uint8 CUDA tensor with one entry per row")
-            check(lib().sgl_spmm_multi_f32(self._h, ptr(x), _ld(x), n_out, arr, int(ld), x.shape[1],
-                                           ptr(row_mask) if row_mask is not None else None, current_stream_ptr()),
-                  "sgl_spmm_multi_f32")
+        if row_mask is not None and not (row_mask.is_cuda and row_mask.dtype == torch.uint8 and row_mask.is_contiguous()
+                                         and row_mask.numel() == self.shape[0]):
+            raise ValueError("row_mask must be a contiguous uint8 CUDA tensor with one entry per row")
+        _call(self.device, "sgl_spmm_multi_f32", self._h, ptr(x), _ld(x), n_out, arr, int(ld), x.shape[1], _opt_ptr(row_mask))
 
     def spmm_chain(self, x, n_hops, outs=None):
         """[A x, A^2 x, ..., A^k x] with ONE library call (the hop loop runs in C).  x: [n, d] row-major CUDA; the
@@ -403,11 +440,8 @@ class DeviceCSR:
                     raise ValueError("an output matrix has the wrong shape")
         if n_hops:
             bf16 = _same_hop_dtype("spmm_chain", x, *outs) == torch.bfloat16
-            fn, name = (lib().sgl_spmm_chain_bf16, "sgl_spmm_chain_bf16") if bf16 else (lib().sgl_spmm_chain_f32, "sgl_spmm_chain_f32")
-            ptrs = (c_void_p * n_hops)(*[o.data_ptr() for o in outs])
-            lds = (c_int64 * n_hops)(*[_ld(o) for o in outs])
-            with torch.cuda.device(self.device):
-                check(fn(self._h, n_hops, ptr(x), _ld(x), ptrs, lds, d, current_stream_ptr()), name)
+            ptrs, lds = _lib.hop_arrays(outs, one_row_pitch=False)
+            _call(self.device, "sgl_spmm_chain_bf16" if bf16 else "sgl_spmm_chain_f32", self._h, n_hops, ptr(x), _ld(x), ptrs, lds, d)
             _wrote(*outs)
         return outs
 
@@ -420,14 +454,10 @@ class DeviceCSR:
             _check_mat(o, "outs[*]")
             if o.shape != (self.shape[0], x.shape[1]):
                 raise ValueError("an output matrix has the wrong shape")
-        n_hops = len(outs)
-        ptrs = (c_void_p * n_hops)(*[o.data_ptr() for o in outs])
-        lds = (c_int64 * n_hops)(*[_ld(o) for o in outs])
+        ptrs, lds = _lib.hop_arrays(outs, one_row_pitch=False)
         g = c_void_p()
         torch.cuda.synchronize(self.device)
-        with torch.cuda.device(self.device):
-            check(lib().sgl_chain_graph_create(ctypes.byref(g), self._h, n_hops, ptr(x), _ld(x), ptrs, lds, x.shape[1]),
-                  "sgl_chain_graph_create")
+        _call(self.device, "sgl_chain_graph_create", ctypes.byref(g), self._h, len(outs), ptr(x), _ld(x), ptrs, lds, x.shape[1])
         return ChainGraph(g, self, x, list(outs))
 
     def spmm_axpb_clamp(self, x, alpha, res=None, lo=float("-inf"), hi=float("inf"), out=None):
@@ -445,17 +475,15 @@ class DeviceCSR:
             _check_mat(res, "res")
             if res.shape != (self.shape[0], d):
                 raise ValueError("res has the wrong shape")
-        with torch.cuda.device(self.device):
-            check(lib().sgl_spmm_axpb_clamp_f32(self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, float(alpha),
-                                                ptr(res) if res is not None else None, _ld(res) if res is not None else 0,
-                                                float(lo), float(hi), current_stream_ptr()), "sgl_spmm_axpb_clamp_f32")
+        _call(self.device, "sgl_spmm_axpb_clamp_f32", self._h, ptr(x), _ld(x), ptr(out), _ld(out), d, float(alpha), _opt_ptr(res),
+              _ld(res) if res is not None else 0, float(lo), float(hi))
         _wrote(out)
         return out
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
-            lib().sgl_csr_destroy(h)
+            _call(None, "sgl_csr_destroy", h, raw=True)
 
     def __del__(self):
         try:
@@ -471,15 +499,14 @@ class ChainGraph:
         self._g, self.csr, self.x, self.outs = handle, csr, x, outs
 
     def replay(self):
-        with torch.cuda.device(self.csr.device):
-            check(lib().sgl_chain_graph_launch(self._g, current_stream_ptr()), "sgl_chain_graph_launch")
+        _call(self.csr.device, "sgl_chain_graph_launch", self._g)
         _wrote(*self.outs)
         return self.outs
 
     def close(self):
         g, self._g = getattr(self, "_g", None), None
         if g:
-            lib().sgl_chain_graph_destroy(g)
+            _call(None, "sgl_chain_graph_destroy", g, raw=True)
 
     def __del__(self):
         try:
@@ -550,9 +577,7 @@ def degree_powers(deg, r, host_pow=True):
         host_pow = few
     if deg.is_cuda and not host_pow:
         left, right = torch.empty_like(deg), torch.empty_like(deg)
-        with torch.cuda.device(deg.device):
-            check(lib().sgl_norm_degree_powers(deg.numel(), ptr(deg), r, ptr(left), ptr(right), current_stream_ptr()),
-                  "sgl_norm_degree_powers")
+        _call(deg.device, "sgl_norm_degree_powers", deg.numel(), ptr(deg), r, ptr(left), ptr(right))
         pow_stats["device"] += 1
     elif deg.is_cuda and deg.numel() > 4096 and (few if few is not None else _few_distinct(deg)):
         uniq, inv = torch.unique(deg, return_inverse=True)
@@ -630,17 +655,15 @@ class PreparedAdjacency:
         self.n, self.src = int(n), (rowptr, col, val)
         nnz_out = c_int64(0)
         with torch.cuda.device(dev):
-            check(lib().sgl_norm_block_prepare(n, 0, nnz, ptr(rowptr), ptr(col), ctypes.byref(nnz_out), current_stream_ptr()),
-                  "sgl_norm_block_prepare")
+            _call(dev, "sgl_norm_block_prepare", n, 0, nnz, ptr(rowptr), ptr(col), ctypes.byref(nnz_out))
             m = nnz_out.value
             self.rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
             self.col = torch.empty(m, dtype=torch.int32, device=dev)
             self.t64 = torch.empty(m, dtype=torch.float64, device=dev)
             self.deg = torch.empty(n, dtype=torch.float64, device=dev)
             fp = torch.zeros(1, dtype=torch.int64, device=dev)
-            check(lib().sgl_norm_build_symcheck(n, nnz, ptr(rowptr), ptr(col), ptr(val), m, ptr(self.rowptr), ptr(self.col),
-                                                ptr(self.t64), ptr(self.deg), ptr(fp), current_stream_ptr()),
-                  "sgl_norm_build_symcheck")
+            _call(dev, "sgl_norm_build_symcheck", n, nnz, ptr(rowptr), ptr(col), ptr(val), m, ptr(self.rowptr), ptr(self.col),
+                  ptr(self.t64), ptr(self.deg), ptr(fp))
             # one read-back for both answers: is A symmetric, and can an entry of A_hat be exactly 0 (see _all_positive)
             ok = val.min() > 0 if nnz else torch.ones((), dtype=torch.bool, device=dev)
             asym, ok = torch.stack([fp[0] != 0, ok]).tolist()
@@ -719,9 +742,8 @@ def _scaled_values(owner, n_loc, row0, rowptr, col, t64, deg, r, alpha, return_f
         if alpha is None or not keep:
             if keep:                                 # Laplacian asked for, values to be kept: the fp64 output IS the cache entry
                 o_v64 = o_v64 if o_v64 is not None else torch.empty(m, dtype=torch.float64, device=dev)
-            check(lib().sgl_norm_block_scale(n_loc, row0, ptr(rowptr), ptr(col), ptr(t64), ptr(left_loc), ptr(right),
-                                             int(alpha is not None), float(alpha if alpha is not None else 0.0), ptr(o_val),
-                                             ptr(o_v64) if o_v64 is not None else None, current_stream_ptr()), "sgl_norm_block_scale")
+            _call(dev, "sgl_norm_block_scale", n_loc, row0, ptr(rowptr), ptr(col), ptr(t64), ptr(left_loc), ptr(right),
+                  int(alpha is not None), float(alpha if alpha is not None else 0.0), ptr(o_val), _opt_ptr(o_v64))
             if keep:
                 owner._hat64 = (key, o_v64)
                 if return_fp64:
@@ -729,8 +751,8 @@ def _scaled_values(owner, n_loc, row0, rowptr, col, t64, deg, r, alpha, return_f
             return (o_val, o_v64) if return_fp64 else (o_val,)
         # PPR with the cache empty: the Laplacian in fp64 first (o_val is scratch for its fp32 rounding), then the mix below
         hat64 = torch.empty(m, dtype=torch.float64, device=dev)
-        check(lib().sgl_norm_block_scale(n_loc, row0, ptr(rowptr), ptr(col), ptr(t64), ptr(left_loc), ptr(right), 0, 0.0,
-                                         ptr(o_val), ptr(hat64), current_stream_ptr()), "sgl_norm_block_scale")
+        _call(dev, "sgl_norm_block_scale", n_loc, row0, ptr(rowptr), ptr(col), ptr(t64), ptr(left_loc), ptr(right), 0, 0.0, ptr(o_val),
+              ptr(hat64))
         owner._hat64 = (key, hat64)
     if alpha is None:
         # Laplacian again at a cached r: alpha = 0 would multiply by 1.0 and add 0.0 to the diagonal -- exact, but a plain rounding
@@ -740,11 +762,9 @@ def _scaled_values(owner, n_loc, row0, rowptr, col, t64, deg, r, alpha, return_f
     diag = getattr(owner, "_diag", None)
     if diag is None:                                  # where each row's diagonal entry sits: once per prepared block
         diag = torch.empty(n_loc, dtype=torch.int64, device=dev)
-        check(lib().sgl_norm_block_diag_positions(n_loc, row0, ptr(rowptr), ptr(col), ptr(diag), current_stream_ptr()),
-              "sgl_norm_block_diag_positions")
+        _call(dev, "sgl_norm_block_diag_positions", n_loc, row0, ptr(rowptr), ptr(col), ptr(diag))
         owner._diag = diag
-    check(lib().sgl_norm_block_mix_at(m, n_loc, ptr(hat64), ptr(diag), float(alpha), ptr(o_val), ptr(o_v64) if return_fp64 else None,
-                                      current_stream_ptr()), "sgl_norm_block_mix_at")
+    _call(dev, "sgl_norm_block_mix_at", m, n_loc, ptr(hat64), ptr(diag), float(alpha), ptr(o_val), ptr(o_v64) if return_fp64 else None)
     return (o_val, o_v64) if return_fp64 else (o_val,)
 
 
@@ -764,17 +784,15 @@ def normalize_adj(rowptr, col, val, n, r, alpha=None, return_fp64=False, host_po
     dev = rowptr.device
     nnz_out = c_int64(0)
     with torch.cuda.device(dev):
-        check(lib().sgl_norm_prepare(n, nnz, ptr(rowptr), ptr(col), ctypes.byref(nnz_out), current_stream_ptr()),
-              "sgl_norm_prepare")
+        _call(dev, "sgl_norm_prepare", n, nnz, ptr(rowptr), ptr(col), ctypes.byref(nnz_out))
         m = nnz_out.value
         o_ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
         o_col = torch.empty(m, dtype=torch.int32, device=dev)
         o_val = torch.empty(m, dtype=torch.float32, device=dev)
         prune = not _all_positive(val) or alpha == 1.0
         o_v64 = torch.empty(m, dtype=torch.float64, device=dev) if (return_fp64 or prune) else None
-        check(lib().sgl_norm_execute(n, nnz, ptr(rowptr), ptr(col), ptr(val), float(r), int(alpha is not None),
-                                     float(alpha if alpha is not None else 0.0), m, ptr(o_ptr), ptr(o_col), ptr(o_val),
-                                     ptr(o_v64) if o_v64 is not None else None, current_stream_ptr()), "sgl_norm_execute")
+        _call(dev, "sgl_norm_execute", n, nnz, ptr(rowptr), ptr(col), ptr(val), float(r), int(alpha is not None),
+              float(alpha if alpha is not None else 0.0), m, ptr(o_ptr), ptr(o_col), ptr(o_val), _opt_ptr(o_v64))
         # the C entry point keeps the union pattern of A and I; the reference's pattern is this layer's business
         return _reference_pattern(prune, return_fp64, o_ptr, o_col, (o_val, o_v64) if o_v64 is not None else (o_val,))
 
@@ -798,15 +816,14 @@ class PreparedBlock:
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
         self.n_local, self.row0, self.n_cols, self.symmetric = n_loc, int(row0), int(n_cols), bool(symmetric)
         with torch.cuda.device(dev):
-            check(lib().sgl_norm_block_prepare(n_loc, row0, nnz, ptr(rowptr), ptr(col), ctypes.byref(nnz_out),
-                                               current_stream_ptr()), "sgl_norm_block_prepare")
+            _call(dev, "sgl_norm_block_prepare", n_loc, row0, nnz, ptr(rowptr), ptr(col), ctypes.byref(nnz_out))
             m = nnz_out.value
             self.rowptr = torch.empty(n_loc + 1, dtype=torch.int64, device=dev)
             self.col = torch.empty(m, dtype=torch.int32, device=dev)
             self.t64 = torch.empty(m, dtype=torch.float64, device=dev)
             rowsum = torch.empty(n_loc, dtype=torch.float64, device=dev)
-            check(lib().sgl_norm_block_build(n_loc, row0, nnz, ptr(rowptr), ptr(col), ptr(val), m, ptr(self.rowptr), ptr(self.col),
-                                             ptr(self.t64), ptr(rowsum), current_stream_ptr()), "sgl_norm_block_build")
+            _call(dev, "sgl_norm_block_build", n_loc, row0, nnz, ptr(rowptr), ptr(col), ptr(val), m, ptr(self.rowptr), ptr(self.col),
+                  ptr(self.t64), ptr(rowsum))
             if deg is not None:
                 if deg.numel() != n_cols:
                     raise ValueError("deg must hold one entry per column")
@@ -822,8 +839,7 @@ class PreparedBlock:
                     deg = rowsum
             else:
                 deg = torch.zeros(n_cols, dtype=torch.float64, device=dev)
-                check(lib().sgl_norm_block_colsum(n_cols, m, ptr(self.col), ptr(self.t64), ptr(deg), current_stream_ptr()),
-                      "sgl_norm_block_colsum")
+                _call(dev, "sgl_norm_block_colsum", n_cols, m, ptr(self.col), ptr(self.t64), ptr(deg))
                 if multi:
                     dist.all_reduce(deg, group=group)
             self.may_hold_zero = not _all_positive(val, deg)
@@ -876,14 +892,13 @@ def _widened(feats, out):
     only read, the output's pad columns belong to us."""
     n, d = out.shape
     strides = {t.stride(0) for t in list(feats) + [out]} if n > 1 else set()
-    if len(strides) == 1 and next(iter(strides)) % 4 == 0 and next(iter(strides)) > d:
-        dp = next(iter(strides))      # every buffer has the same pitch: stream whole rows, pad included (contiguous)
+    if len(strides) == 1 and pitch_vectored(out) and out.stride(0) > d:
+        dp = out.stride(0)            # every buffer has the same pitch: stream whole rows, pad included (contiguous)
     else:
         dp = round_up(d, 4)
     if d == dp or n <= 1:
         return feats, out, d
-    ok = all(f.stride(0) % 4 == 0 and f.stride(0) >= dp and f.data_ptr() % 16 == 0 for f in list(feats) + [out])
-    if not ok:
+    if not all(rows_vectored(f, width=dp) for f in list(feats) + [out]):
         return feats, out, d
     wide = [torch.as_strided(f, (n, dp), (f.stride(0), 1), f.storage_offset()) for f in feats]
     return wide, torch.as_strided(out, (n, dp), (out.stride(0), 1), out.storage_offset()), dp
@@ -906,69 +921,65 @@ def _alloc_out(n, d, device, dtype=torch.float32):
     return out, pad
 
 
+def _grad_rows(gout, n, d):
+    """the incoming gradient of a [n, d] result as a detached float32 row-major matrix (copied only when it is not one)"""
+    g = gout.detach().to(torch.float32)
+    if g.stride(1) != 1 or (n > 1 and g.stride(0) < d):
+        g = g.contiguous()
+    return g
+
+
 def hop_reduce(op, feats, weights=None):
     """sum / mean / max / min / 1-D weighted sum over the hop list -> new [n, d] float32 tensor.  A list of bfloat16 hops is read in
     place (sgl_hop_reduce_bf16_f32: every element widened exactly, the float32 kernel's operations in its order -- the same bits
-    as over widened copies, without the copies); a list that mixes dtypes widens its bfloat16 members first (widen_hops)."""
-    if _all_bf16(feats):
-        _check_hops(feats, bf16=True)
-        n, d = feats[0].shape
-        w = None
-        if op == _lib.SGL_REDUCE_WSUM:
-            w = weights.detach().to(device=feats[0].device, dtype=torch.float32).contiguous()
-            if w.numel() != len(feats):
-                raise ValueError("The feature list and the weight list have different lengths!")
-        result, pad = _alloc_out(n, d, feats[0].device)
-        ptrs, lds = _lib.hop_arrays(feats)
-        with torch.cuda.device(feats[0].device):
-            check(lib().sgl_hop_reduce_bf16_f32(op, len(feats), ptrs, lds, ptr(w) if w is not None else None, ptr(result), _ld(result),
-                                                pad, n, d, current_stream_ptr()), "sgl_hop_reduce_bf16_f32")
-        return result
-    feats = widen_hops(feats)
-    _check_hops(feats)
+    as over widened copies, without the copies); a list that mixes dtypes widens its bfloat16 members first (widen_hops) and runs
+    sgl_hop_reduce_f32."""
+    direct = _all_bf16(feats)
+    if not direct:
+        feats = widen_hops(feats)
+    _check_hops(feats, bf16=direct)
     n, d = feats[0].shape
-    result = alloc_rows(n, d, feats[0].device)
-    feats, out, d = _widened(feats, result)
-    ptrs, lds = _lib.hop_arrays(feats)
+    device = feats[0].device
     w = None
     if op == _lib.SGL_REDUCE_WSUM:
-        w = weights.detach().to(device=feats[0].device, dtype=torch.float32).contiguous()
+        w = weights.detach().to(device=device, dtype=torch.float32).contiguous()
         if w.numel() != len(feats):
             raise ValueError("The feature list and the weight list have different lengths!")
-    with torch.cuda.device(feats[0].device):
-        check(lib().sgl_hop_reduce_f32(op, len(feats), ptrs, lds, ptr(w) if w is not None else None, ptr(out), _ld(out),
-                                       n, d, current_stream_ptr()), "sgl_hop_reduce_f32")
+    if direct:                     # the kernel writes the pad columns it is told about, as zeros
+        result, pad = _alloc_out(n, d, device)
+        name, out, pad = "sgl_hop_reduce_bf16_f32", result, (pad,)
+    else:                          # element-wise over the padded width where every matrix has one (pad columns: zeros in, zeros out)
+        result = alloc_rows(n, d, device)
+        feats, out, d = _widened(feats, result)
+        name, pad = "sgl_hop_reduce_f32", ()
+    ptrs, lds = _lib.hop_arrays(feats)
+    _call(device, name, op, len(feats), ptrs, lds, _opt_ptr(w), ptr(out), _ld(out), *pad, n, d)
     return result
 
 
 def hop_concat(feats, out_dtype=None):
-    """the hops side by side -> [n, H d] float32.  A list of bfloat16 hops is read in place (sgl_hop_concat_bf16_f32: an exact
-    widening), and with out_dtype=torch.bfloat16 stays bfloat16 (sgl_hop_concat_bf16: a copy of bit patterns into an
-    alloc_rows(..., dtype=torch.bfloat16) matrix); a list that mixes dtypes widens its bfloat16 members first (widen_hops)."""
+    """the hops side by side -> [n, H d] float32 (sgl_hop_concat_padded_f32).  A list of bfloat16 hops is read in place
+    (sgl_hop_concat_bf16_f32: an exact widening), and with out_dtype=torch.bfloat16 stays bfloat16 (sgl_hop_concat_bf16: a copy of bit
+    patterns into an alloc_rows(..., dtype=torch.bfloat16) matrix); a list that mixes dtypes widens its bfloat16 members first
+    (widen_hops)."""
     if out_dtype not in (None, torch.float32, torch.bfloat16):
         raise ValueError(f"hop_concat: out_dtype is float32 or bfloat16, not {out_dtype}")
-    if _all_bf16(feats):
-        _check_hops(feats, bf16=True)
-        n, d = feats[0].shape
-        H = len(feats)
-        out, pad = _alloc_out(n, H * d, feats[0].device, dtype=out_dtype or torch.float32)
-        fn, name = ((lib().sgl_hop_concat_bf16, "sgl_hop_concat_bf16") if out_dtype == torch.bfloat16
-                    else (lib().sgl_hop_concat_bf16_f32, "sgl_hop_concat_bf16_f32"))
-        ptrs, lds = _lib.hop_arrays(feats)
-        with torch.cuda.device(feats[0].device):
-            check(fn(H, ptrs, lds, ptr(out), _ld(out), pad, n, d, current_stream_ptr()), name)
-        return out
-    if out_dtype == torch.bfloat16:
-        raise TypeError("hop_concat: a bfloat16 result is a copy of bfloat16 hop matrices (every member of the list), nothing is rounded here")
-    feats = widen_hops(feats)
-    _check_hops(feats)
+    direct = _all_bf16(feats)
+    if not direct:
+        if out_dtype == torch.bfloat16:
+            raise TypeError("hop_concat: a bfloat16 result is a copy of bfloat16 hop matrices (every member of the list), nothing is rounded here")
+        feats = widen_hops(feats)
+    _check_hops(feats, bf16=direct)
     n, d = feats[0].shape
     H = len(feats)
-    out = alloc_rows(n, H * d, feats[0].device)
+    if direct:
+        out, pad = _alloc_out(n, H * d, feats[0].device, dtype=out_dtype or torch.float32)
+        name = "sgl_hop_concat_bf16" if out_dtype == torch.bfloat16 else "sgl_hop_concat_bf16_f32"
+    else:
+        out = alloc_rows(n, H * d, feats[0].device)
+        name, pad = "sgl_hop_concat_padded_f32", own_pad(out)
     ptrs, lds = _lib.hop_arrays(feats)
-    with torch.cuda.device(feats[0].device):
-        check(lib().sgl_hop_concat_padded_f32(H, ptrs, lds, ptr(out), _ld(out), own_pad(out), n, d, current_stream_ptr()),
-              "sgl_hop_concat_padded_f32")
+    _call(feats[0].device, name, H, ptrs, lds, ptr(out), _ld(out), pad, n, d)
     return out
 
 
@@ -999,9 +1010,7 @@ def hop_lincomb(feats, weights, outs=None):
         f_w, o_w = list(feats), list(outs)
     ptrs, lds = _lib.hop_arrays(f_w)
     optrs, olds = _lib.hop_arrays(o_w)
-    with torch.cuda.device(feats[0].device):
-        check(lib().sgl_hop_lincomb_f32(len(feats), ptrs, lds, n_out, optrs, olds, ptr(w), int(w.stride(0)), n, dw, current_stream_ptr()),
-              "sgl_hop_lincomb_f32")
+    _call(feats[0].device, "sgl_hop_lincomb_f32", len(feats), ptrs, lds, n_out, optrs, olds, ptr(w), int(w.stride(0)), n, dw)
     _wrote(*outs)
     return outs
 
@@ -1039,16 +1048,11 @@ class _ReduceGrad(torch.autograd.Function):
             return (None, None, *[g if nd else None for nd in need])
         feats = list(ctx.saved_tensors)
         n, d = feats[0].shape
-        g = gout.detach().to(torch.float32)
-        if g.stride(1) != 1 or (n > 1 and g.stride(0) < d):
-            g = g.contiguous()
+        g = _grad_rows(gout, n, d)
         dxs = [alloc_rows(n, d, g.device) if nd else None for nd in need]
         ptrs, lds = _lib.hop_arrays(feats)
-        dx_ptrs = (c_void_p * H)(*[(t.data_ptr() if t is not None else None) for t in dxs])
-        dx_lds = (c_int64 * H)(*[(_ld(t) if t is not None else 0) for t in dxs])
-        with torch.cuda.device(g.device):
-            check(lib().sgl_hop_select_bwd_f32(ctx.op, H, ptrs, lds, ptr(g), _ld(g), dx_ptrs, dx_lds, n, d, current_stream_ptr()),
-                  "sgl_hop_select_bwd_f32")
+        dx_ptrs, dx_lds = _lib.hop_arrays(dxs, one_row_pitch=False)
+        _call(g.device, "sgl_hop_select_bwd_f32", ctx.op, H, ptrs, lds, ptr(g), _ld(g), dx_ptrs, dx_lds, n, d)
         return (None, None, *dxs)
 
 
@@ -1060,7 +1064,7 @@ def hop_reduce_grad(op, feats, divisor=None):
 
 class _ConcatGrad(torch.autograd.Function):
     """hstack of the hop list WITH gradients (concat_message_op.py:12; the tail of ProjectedConcatMessageOp._combine,
-    projected_concat_message_op.py:28): forward = sgl_hop_concat_f32, backward = the column slices of the incoming gradient (views)."""
+    projected_concat_message_op.py:28): forward = hop_concat (sgl_hop_concat_padded_f32), backward = the column slices of the incoming gradient (views)."""
 
     @staticmethod
     def forward(ctx, *feats):
@@ -1092,9 +1096,7 @@ class _WSum2D(torch.autograd.Function):
         result = alloc_rows(n, d, feats_d[0].device)
         wide, out, dw_ = _widened(feats_d, result)
         ptrs, lds = _lib.hop_arrays(wide)
-        with torch.cuda.device(out.device):
-            check(lib().sgl_hop_wsum2d_f32(len(feats_d), ptrs, lds, ptr(wd), _ld(wd), ptr(out), _ld(out), n, dw_,
-                                           current_stream_ptr()), "sgl_hop_wsum2d_f32")
+        _call(out.device, "sgl_hop_wsum2d_f32", len(feats_d), ptrs, lds, ptr(wd), _ld(wd), ptr(out), _ld(out), n, dw_)
         ctx.save_for_backward(wd, *feats_d)
         return result
 
@@ -1110,10 +1112,8 @@ def _wsum2d_backward(wd, feats, gout, need_w, need_x):
     """gradients of out = sum_h W[:, h] X_h: dW[n, h] = <dOut[n], X_h[n]> (register row-dot kernel) and dX_h = W[:, h] dOut"""
     n, d = feats[0].shape
     H = len(feats)
-    g = gout.detach().to(torch.float32)
-    if g.stride(1) != 1 or (n > 1 and g.stride(0) < d):
-        g = g.contiguous()
-    if n > 1 and d > 4 and (g.stride(0) % 4 != 0 or g.data_ptr() % 16 != 0) and (any(need_x) or H > 16 or d > 512):
+    g = _grad_rows(gout, n, d)
+    if n > 1 and d > 4 and not rows_vectored(g) and (any(need_x) or H > 16 or d > 512):
         # autograd hands over a dense [n, d] gradient: for d % 4 != 0 its rows are not 16-byte aligned.  The dW row-dot
         # reads such a gradient directly (dword-aligned vector loads, sgl_hop_wsum2d_bwd_f32); the element-wise dX
         # kernel and the wide / many-hop fallback would drop to 4-byte lanes (0.36 of peak at d = 147), so for those
@@ -1124,14 +1124,8 @@ def _wsum2d_backward(wd, feats, gout, need_w, need_x):
     dw = torch.empty((n, H), dtype=torch.float32, device=g.device) if need_w else None
     dxs = [alloc_rows(n, d, g.device) if need_x[h] else None for h in range(H)]
     ptrs, lds = _lib.hop_arrays(feats)
-    dx_ptrs = dx_lds = None
-    if any(need_x):
-        dx_ptrs = (c_void_p * H)(*[(t.data_ptr() if t is not None else None) for t in dxs])
-        dx_lds = (c_int64 * H)(*[(_ld(t) if t is not None else 0) for t in dxs])
-    with torch.cuda.device(g.device):
-        check(lib().sgl_hop_wsum2d_bwd_f32(H, ptrs, lds, ptr(wd), _ld(wd), ptr(g), _ld(g),
-                                           ptr(dw) if need_w else None, H, dx_ptrs, dx_lds, n, d,
-                                           current_stream_ptr()), "sgl_hop_wsum2d_bwd_f32")
+    dx_ptrs, dx_lds = _lib.hop_arrays(dxs, one_row_pitch=False) if any(need_x) else (None, None)
+    _call(g.device, "sgl_hop_wsum2d_bwd_f32", H, ptrs, lds, ptr(wd), _ld(wd), ptr(g), _ld(g), _opt_ptr(dw), H, dx_ptrs, dx_lds, n, d)
     return dw, dxs
 
 
@@ -1154,17 +1148,13 @@ class _WSum1D(torch.autograd.Function):
         wd, *feats = ctx.saved_tensors
         n, d = feats[0].shape
         H = len(feats)
-        g = gout.detach().to(torch.float32)
-        if g.stride(1) != 1 or (n > 1 and g.stride(0) < d):
-            g = g.contiguous()
+        g = _grad_rows(gout, n, d)
         dw = None
         if ctx.needs_input_grad[0]:
             dw = torch.empty(H, dtype=torch.float32, device=g.device)
-            scratch = torch.empty(int(lib().sgl_hop_wsum1d_bwd_scratch(H)), dtype=torch.float32, device=g.device)
+            scratch = torch.empty(int(_call(None, "sgl_hop_wsum1d_bwd_scratch", H, raw=True)), dtype=torch.float32, device=g.device)
             ptrs, lds = _lib.hop_arrays(feats)
-            with torch.cuda.device(g.device):
-                check(lib().sgl_hop_wsum1d_bwd_f32(H, ptrs, lds, ptr(g), _ld(g), ptr(dw), ptr(scratch), n, d,
-                                                   current_stream_ptr()), "sgl_hop_wsum1d_bwd_f32")
+            _call(g.device, "sgl_hop_wsum1d_bwd_f32", H, ptrs, lds, ptr(g), _ld(g), ptr(dw), ptr(scratch), n, d)
         dxs = []
         for h in range(H):
             dxs.append(g * wd[h] if ctx.needs_input_grad[1 + h] else None)  # rarely needed: features carry no grad
@@ -1184,15 +1174,13 @@ def hop_colsum(feats, w, shared=False):
     H = len(feats)
     n, d = feats[0].shape
     w = w.detach().to(torch.float32)
-    if (H <= 16 and 0 < d <= 1024 and n > 0 and all(f.is_cuda and f.dtype == torch.float32 and f.stride(1) == 1 and f.data_ptr() % 16 == 0
-                                                    and (n == 1 or f.stride(0) % 4 == 0) for f in feats)):
+    if (H <= 16 and 0 < d <= 1024 and n > 0 and all(f.is_cuda and f.dtype == torch.float32 and f.stride(1) == 1
+                                                    and rows_vectored(f, single_row=True) for f in feats)):
         w = w.contiguous()
         out = torch.empty((H, d), dtype=torch.float32, device=feats[0].device)
-        scratch = torch.empty(int(lib().sgl_hop_colsum_scratch(H, n, d)), dtype=torch.float32, device=out.device)
+        scratch = torch.empty(int(_call(None, "sgl_hop_colsum_scratch", H, n, d, raw=True)), dtype=torch.float32, device=out.device)
         ptrs, lds = _lib.hop_arrays(feats)
-        with torch.cuda.device(out.device):
-            check(lib().sgl_hop_colsum_f32(H, ptrs, lds, ptr(w), 1 if shared else H, 0 if shared else 1, ptr(out), d, ptr(scratch),
-                                           n, d, current_stream_ptr()), "sgl_hop_colsum_f32")
+        _call(out.device, "sgl_hop_colsum_f32", H, ptrs, lds, ptr(w), 1 if shared else H, 0 if shared else 1, ptr(out), d, ptr(scratch), n, d)
         return out
     if shared:
         return torch.stack([f.t() @ w.view(-1) for f in feats])
@@ -1209,12 +1197,10 @@ class _HopScores(torch.autograd.Function):
         _check_hops(feats_d)
         n, d = feats_d[0].shape
         H = len(feats_d)
-        vp = torch.zeros(round_up(d, 4), dtype=torch.float32, device=feats_d[0].device)
-        vp[:d] = v.detach().to(torch.float32).view(-1)
+        vp = _padded_vec(v, d, feats_d[0].device)
         out = torch.empty((n, H), dtype=torch.float32, device=vp.device)
         ptrs, lds = _lib.hop_arrays(feats_d)
-        with torch.cuda.device(vp.device):
-            check(lib().sgl_hop_rowdot_f32(H, ptrs, lds, ptr(vp), ptr(out), H, n, d, current_stream_ptr()), "sgl_hop_rowdot_f32")
+        _call(vp.device, "sgl_hop_rowdot_f32", H, ptrs, lds, ptr(vp), ptr(out), H, n, d)
         ctx.save_for_backward(v.detach(), *feats_d)
         return out
 
@@ -1254,15 +1240,13 @@ def _gate_launch(v, b, feats_d, outputs):
     result = alloc_rows(n, d, dev_)
     w, g = ((torch.empty((n, H), dtype=torch.float32, device=dev_) for _ in range(2)) if outputs else (None, None))
     ptrs, lds = _lib.hop_arrays(feats_d)
-    with torch.cuda.device(dev_):
-        check(lib().sgl_hop_gate_padded_f32(H, ptrs, lds, ptr(vp), float("nan"), ptr(result), _ld(result), own_pad(result),
-                                            ptr(w) if outputs else None, H, ptr(g) if outputs else None, H, n, d,
-                                            current_stream_ptr()), "sgl_hop_gate_padded_f32")
+    _call(dev_, "sgl_hop_gate_padded_f32", H, ptrs, lds, ptr(vp), float("nan"), ptr(result), _ld(result), own_pad(result),
+          _opt_ptr(w), H, _opt_ptr(g), H, n, d)
     return result, w, g
 
 
 class _GateFused(torch.autograd.Function):
-    """out = sum_h softmax_h(sigmoid(<X_h, v> + b)) X_h in ONE pass over the hops (sgl_hop_gate_f32); the backward re-uses the
+    """out = sum_h softmax_h(sigmoid(<X_h, v> + b)) X_h in ONE pass over the hops (sgl_hop_gate_padded_f32); the backward re-uses the
     dW row-dot kernel and finishes the [n, H]-sized softmax / sigmoid chain in torch."""
 
     @staticmethod
@@ -1294,15 +1278,16 @@ class _GateFused(torch.autograd.Function):
 
 
 def gate_fusable(feats):
-    """can sgl_hop_gate_f32 / sgl_hop_rowdot2_f32 take these hops? (register-resident rows: <= 16 hops, d <= 512, 16-byte rows)"""
+    """can sgl_hop_gate_padded_f32 / sgl_hop_recursive_f32 / sgl_hop_rowdot2_f32 take these hops? (register-resident rows: <= 16
+    float32 hops, d <= 512, 16-byte rows)"""
     f0 = feats[0]
-    return (len(feats) <= 16 and f0.is_cuda and f0.dtype == torch.float32 and 0 < f0.shape[1] <= 512 and f0.shape[0] > 0 and
-            all(f.stride(1) == 1 and f.data_ptr() % 16 == 0 and (f.shape[0] == 1 or f.stride(0) % 4 == 0) for f in feats))
+    return (len(feats) <= 16 and f0.is_cuda and 0 < f0.shape[1] <= 512 and f0.shape[0] > 0 and
+            all(f.dtype == torch.float32 and f.stride(1) == 1 and rows_vectored(f, single_row=True) for f in feats))
 
 
 def hop_gate(feats, v, b, return_weights=False):
     """LearnableWeightedMessageOp 'gate': (out, W) with W = softmax_h(sigmoid(Linear(X_h))) [n, H].  One pass over the hops
-    (sgl_hop_gate_f32) when their rows fit the register-resident kernel (gate_fusable); otherwise the two-pass route -- one
+    (sgl_hop_gate_padded_f32) when their rows fit the register-resident kernel (gate_fusable); otherwise the two-pass route -- one
     row-dot pass for the scores, the [n, H] sigmoid / softmax in torch, one weighted-sum pass."""
     if gate_fusable(feats):
         if torch.is_grad_enabled() and any(t.requires_grad for t in (v, b, *feats)):
@@ -1337,22 +1322,16 @@ def _recursive_launch(weight, b, feats_d, outputs):
     n, d = feats_d[0].shape
     H = len(feats_d)
     dev_ = feats_d[0].device
-    dp = round_up(d, 4)
     wt = weight.detach().to(device=dev_, dtype=torch.float32).reshape(-1)
     if wt.numel() != 2 * d:
         raise ValueError(f"the recursive gate's Linear has {wt.numel()} weights, the hops need 2 * {d}")
-    vp = torch.zeros(2 * dp + 4, dtype=torch.float32, device=dev_)          # [w_x | pad | w_acc | pad | bias]
-    vp[:d] = wt[:d]
-    vp[dp:dp + d] = wt[d:]
-    vp[2 * dp:2 * dp + 1] = b.detach().to(device=dev_, dtype=torch.float32).reshape(-1)[:1]
+    vp = torch.cat([_padded_vec(wt[:d], d, dev_), _padded_vec(wt[d:], d, dev_, tail=b)])          # [w_x | pad | w_acc | pad | bias]
     result = alloc_rows(n, d, dev_)
     w, a, c = ((torch.empty((n, H), dtype=torch.float32, device=dev_) for _ in range(3)) if outputs else (None, None, None))
     ptrs, lds = _lib.hop_arrays(feats_d)
-    with torch.cuda.device(dev_):
-        # bias = NaN: "read it from the device, after the two padded vectors" (no host synchronisation on a parameter)
-        check(lib().sgl_hop_recursive_f32(H, ptrs, lds, ptr(vp), float("nan"), ptr(result), _ld(result), own_pad(result),
-                                          ptr(w) if outputs else None, H, ptr(a) if outputs else None, H,
-                                          ptr(c) if outputs else None, H, n, d, current_stream_ptr()), "sgl_hop_recursive_f32")
+    # bias = NaN: "read it from the device, after the two padded vectors" (no host synchronisation on a parameter)
+    _call(dev_, "sgl_hop_recursive_f32", H, ptrs, lds, ptr(vp), float("nan"), ptr(result), _ld(result), own_pad(result),
+          _opt_ptr(w), H, _opt_ptr(a), H, _opt_ptr(c), H, n, d)
     return result, vp, w, a, c
 
 
@@ -1381,9 +1360,8 @@ class _RecursiveFused(torch.autograd.Function):
         dwt = dwt.contiguous()
         da, dc = torch.empty_like(a), torch.empty_like(c)
         dbr = torch.empty(n, dtype=torch.float32, device=a.device)
-        with torch.cuda.device(a.device):
-            check(lib().sgl_hop_recursive_bwd_f32(H, ptr(a), H, ptr(c), H, float("nan"), ptr(vp[2 * dp:]), ptr(dwt), H, ptr(da), H,
-                                                  ptr(dc), H, ptr(dbr), n, current_stream_ptr()), "sgl_hop_recursive_bwd_f32")
+        _call(a.device, "sgl_hop_recursive_bwd_f32", H, ptr(a), H, ptr(c), H, float("nan"), ptr(vp[2 * dp:]), ptr(dwt), H, ptr(da), H,
+              ptr(dc), H, ptr(dbr), n)
         dweight = dbias = None
         if ctx.needs_input_grad[0]:
             dweight = torch.cat([hop_colsum(feats, da).sum(0), hop_colsum(feats, dc).sum(0)]).reshape(ctx.shapes[0])
@@ -1431,9 +1409,7 @@ class _HopScores2(torch.autograd.Function):
         p = torch.empty((n, h1 - h0), dtype=torch.float32, device=dev_)
         a = torch.empty(n, dtype=torch.float32, device=dev_)
         ptrs, lds = _lib.hop_arrays(feats_d)
-        with torch.cuda.device(dev_):
-            check(lib().sgl_hop_rowdot2_f32(L, ptrs, lds, ptr(up), ldu, ctypes.c_uint64(mask), ptr(vp), h0, h1, ptr(p), h1 - h0,
-                                            ptr(a), n, d, current_stream_ptr()), "sgl_hop_rowdot2_f32")
+        _call(dev_, "sgl_hop_rowdot2_f32", L, ptrs, lds, ptr(up), ldu, ctypes.c_uint64(mask), ptr(vp), h0, h1, ptr(p), h1 - h0, ptr(a), n, d)
         ctx.save_for_backward(v.detach(), u.detach(), *feats_d)
         ctx.meta = (mask, h0, h1)
         return p, a
@@ -1488,18 +1464,18 @@ def nafs_aggregate(feats, return_weights=False):
     H = len(feats)
     out = alloc_rows(n, d, feats[0].device)
     w = torch.empty((n, H), dtype=torch.float32, device=feats[0].device)
-    with torch.cuda.device(out.device):
-        if direct:
-            ptrs, lds = _lib.hop_arrays(feats)
-            rc = lib().sgl_nafs_bf16_f32(H, ptrs, lds, ptr(out), _ld(out), own_pad(out), ptr(w), H, n, d, current_stream_ptr())
-            if rc == _lib.SGL_ERR_UNSUPPORTED:         # not a shape of the bf16 kernel: today's route, no second bf16 kernel
-                feats = widen_hops(feats)
-            else:
-                check(rc, "sgl_nafs_bf16_f32")
-                return (out, w) if return_weights else out
+
+    def launch(name, raw=False):
         ptrs, lds = _lib.hop_arrays(feats)
-        check(lib().sgl_nafs_padded_f32(H, ptrs, lds, ptr(out), _ld(out), own_pad(out), ptr(w), H, n, d, current_stream_ptr()),
-              "sgl_nafs_padded_f32")
+        return _call(out.device, name, H, ptrs, lds, ptr(out), _ld(out), own_pad(out), ptr(w), H, n, d, raw=raw)
+
+    rc = launch("sgl_nafs_bf16_f32", raw=True) if direct else _lib.SGL_ERR_UNSUPPORTED
+    if rc == _lib.SGL_ERR_UNSUPPORTED:             # float32 hops, or not a shape of the bf16 kernel: no second bf16 kernel
+        if direct:
+            feats = widen_hops(feats)
+        launch("sgl_nafs_padded_f32")
+    else:
+        check(rc, "sgl_nafs_bf16_f32")
     return (out, w) if return_weights else out
 
 
@@ -1536,9 +1512,7 @@ def nafs_prefix(feats, emit_hops, outs=None, combine=NAFS_STORE, divisor=1.0, ou
         mask |= 1 << h
     ptrs, lds = _lib.hop_arrays(feats)
     optrs, olds = _lib.hop_arrays(outs)
-    with torch.cuda.device(feats[0].device):
-        check(lib().sgl_nafs_prefix_f32(len(feats), ptrs, lds, mask, optrs, olds, pad, int(combine), float(divisor), n, d,
-                                        current_stream_ptr()), "sgl_nafs_prefix_f32")
+    _call(feats[0].device, "sgl_nafs_prefix_f32", len(feats), ptrs, lds, mask, optrs, olds, pad, int(combine), float(divisor), n, d)
     _wrote(*outs)
     return outs
 
@@ -1557,9 +1531,8 @@ def scatter_rows(x, src, dst, out):
         raise ValueError("scatter_rows: src and dst must have the same length")
     if src.numel() == 0:
         return out
-    with torch.cuda.device(x.device):
-        check(lib().sgl_scatter_rows_f32(ptr(x), _ld(x), x.shape[0], ptr(src), ptr(dst), src.numel(), ptr(out), _ld(out),
-                                         out.shape[0], x.shape[1], current_stream_ptr()), "sgl_scatter_rows_f32")
+    _call(x.device, "sgl_scatter_rows_f32", ptr(x), _ld(x), x.shape[0], ptr(src), ptr(dst), src.numel(), ptr(out), _ld(out), out.shape[0],
+          x.shape[1])
     _wrote(out)
     return out
 
@@ -1591,14 +1564,10 @@ def column_signature(x):
     dw = round_up(d, 4)
     if n == 0 or d == 0:
         return None
-    ld = x.stride(0) if n > 1 else dw
-    if x.stride(1) != 1 or ld % 4 or ld < dw or x.data_ptr() % 16:
-        return None
-    if x.untyped_storage().nbytes() // 4 - x.storage_offset() < (n - 1) * ld + dw:
+    if x.stride(1) != 1 or not rows_vectored(x, single_row=True, width=dw, room=True):
         return None
     sig = torch.empty(dw, dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib().sgl_col_signature_f32(ptr(x), ld, n, d, ptr(sig), current_stream_ptr()), "sgl_col_signature_f32")
+    _call(x.device, "sgl_col_signature_f32", ptr(x), _ld(x, one_row=dw), n, d, ptr(sig))
     return sig
 
 
@@ -1618,7 +1587,7 @@ def gather_hops(feats, idx, one_launch=None):
             _check_mat(f, f"feat_list[{i}]", bf16=True)
             if f.dtype != torch.bfloat16 or f.shape != feats[0].shape or f.device != feats[0].device:
                 raise ValueError("gather_hops: bfloat16 hop matrices must all be bfloat16, of one shape, on one device")
-        return _gather_bf16(feats, _device_index(idx, feats[0].shape[0], feats[0].device))
+        return _gather(feats, _device_index(idx, feats[0].shape[0], feats[0].device))
     same_rows = all(torch.is_tensor(f) and f.is_cuda and f.dim() == 2 and f.shape[0] == feats[0].shape[0] and f.device == feats[0].device
                     for f in feats)
     if same_rows:
@@ -1632,57 +1601,55 @@ def gather_hops(feats, idx, one_launch=None):
 def _gather_hops_one_launch(feats, idx):
     """sgl_gather_hops_padded_f32 when every hop matrix is a float32 [n, d] matrix of 16-byte rows (what propagate() returns), else None"""
     n_rows, d = feats[0].shape
-    m = int(idx.numel())
-    dp = round_up(d, 4)
-    if m < 2 or n_rows < 2 or len(feats) > 16:
+    if idx.numel() < 2 or n_rows < 2 or len(feats) > 16:
         return None
-    for x in feats:
-        if not (x.dtype == torch.float32 and x.shape == (n_rows, d) and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= dp
-                and x.data_ptr() % 16 == 0 and x.untyped_storage().nbytes() // 4 - x.storage_offset() >= (n_rows - 1) * x.stride(0) + dp):
-            return None
-    outs = [alloc_rows(m, d, feats[0].device, zero_pad=False) for _ in feats]
-    ldo = outs[0].stride(0)
-    if ldo % 4 or ldo < dp or any(o.data_ptr() % 16 for o in outs):
+    if not all(x.dtype == torch.float32 and x.shape == (n_rows, d) and x.stride(1) == 1 for x in feats):
         return None
-    pad = (ldo - d) if ldo - d < 32 else (dp - d)
-    if pad != ldo - d:
-        for o in outs:
-            padded_parent(o)[:, d + pad:].zero_()
-    ptrs, lds = _lib.hop_arrays(feats)
-    optrs, olds = _lib.hop_arrays(outs)
-    with torch.cuda.device(feats[0].device):
-        check(lib().sgl_gather_hops_padded_f32(len(feats), ptrs, lds, n_rows, ptr(idx), m, optrs, olds, d, pad, current_stream_ptr()),
-              "sgl_gather_hops_padded_f32")
-    return outs
+    return _gather(feats, idx, hops_entry=True)
 
 
-def _gather_bf16(feats, idx, outs=None):
-    """[x[idx] as float32 for x in feats] for bfloat16 matrices of one shape (sgl_gather_hops_bf16_f32: up to 16 hops per launch).
-    Our own outputs are padded float32 buffers whose pad columns are written as zeros by the kernel."""
+def _gather(feats, idx, outs=None, hops_entry=False):
+    """[x[idx] as float32 for x in feats] for matrices of ONE dtype, shape and device; idx from _device_index.  outs: the caller's
+    destinations, else padded float32 buffers of our own whose pad columns the kernel writes as zeros (own_out_pad).
+    bfloat16 rows (sgl_gather_rows_bf16_f32 / sgl_gather_hops_bf16_f32, 16 hops per launch) are widened exactly, whatever their layout.
+    float32 rows (sgl_gather_rows_padded_f32 / sgl_gather_hops_padded_f32) use 16-byte lanes for any d when source and destination
+    rows are 16-byte vectors: the vector that straddles column d is READ from the source (its pitch covers it, and the storage must
+    hold it for the last row too) but only the d data columns reach the result; the pad columns that get written are written as
+    zeros -- never the source's tail, which may be real data when x is a column view of a wider matrix.  A caller's output is padded
+    up to the next multiple of 4 only.  Several float32 hops whose rows are not such vectors: None (the caller gathers hop by hop).
+    hops_entry: a single matrix goes to the many-hop entry point too (what _gather_hops_one_launch has always launched)."""
+    bf16 = feats[0].dtype == torch.bfloat16
     n_rows, d = feats[0].shape
-    m = int(idx.numel())
+    m, dp, device = int(idx.numel()), round_up(d, 4), feats[0].device
+    own = outs is None
+    if own:
+        outs = [alloc_rows(m, d, device, zero_pad=False) for _ in feats]
+    vec = (not bf16 and m > 1 and all(rows_vectored(x, width=dp, room=True) for x in feats)
+           and all(rows_vectored(o, width=dp) for o in outs))
+    if not (bf16 or vec or (len(feats) == 1 and not hops_entry)):
+        return None
     pad = 0
-    if outs is None:
-        outs = [alloc_rows(m, d, feats[0].device, zero_pad=m <= 1) for _ in feats]
+    if own:                      # the pitch's tail is ours: the kernel zeroes what it is told about, the rest is zeroed here
         ldo = outs[0].stride(0)
-        if m > 1 and ldo > d:
-            pad = (ldo - d) if ldo - d < 32 else (round_up(d, 4) - d)
-            if pad != ldo - d:
-                for o in outs:
-                    padded_parent(o)[:, d + pad:].zero_()
-    if m == 0 or d == 0:
+        if (m > 1) if bf16 else vec:
+            pad = own_out_pad(ldo, d)
+        if pad != ldo - d:
+            for o in outs:
+                padded_parent(o)[:, d + pad:].zero_()
+    elif vec:
+        pad = dp - d
+    if m == 0 or (bf16 and d == 0):
         return outs
-    with torch.cuda.device(feats[0].device):
-        for a in range(0, len(feats), 16):
-            fs, os_ = feats[a:a + 16], outs[a:a + 16]
+    for a in range(0, len(feats), 16):
+        fs, os_ = feats[a:a + 16], outs[a:a + 16]
+        if len(fs) == 1 and not hops_entry:
+            _call(device, "sgl_gather_rows_bf16_f32" if bf16 else "sgl_gather_rows_padded_f32", ptr(fs[0]), _ld(fs[0]), n_rows, ptr(idx), m,
+                  ptr(os_[0]), _ld(os_[0]), d, pad)
+        else:
             ptrs, lds = _lib.hop_arrays(fs)
             optrs, olds = _lib.hop_arrays(os_)
-            if len(fs) == 1:
-                check(lib().sgl_gather_rows_bf16_f32(ptr(fs[0]), _ld(fs[0]), n_rows, ptr(idx), m, ptr(os_[0]), _ld(os_[0]), d, pad,
-                                                     current_stream_ptr()), "sgl_gather_rows_bf16_f32")
-            else:
-                check(lib().sgl_gather_hops_bf16_f32(len(fs), ptrs, lds, n_rows, ptr(idx), m, optrs, olds, d, pad, current_stream_ptr()),
-                      "sgl_gather_hops_bf16_f32")
+            _call(device, "sgl_gather_hops_bf16_f32" if bf16 else "sgl_gather_hops_padded_f32", len(fs), ptrs, lds, n_rows, ptr(idx), m,
+                  optrs, olds, d, pad)
     _wrote(*outs)
     return outs
 
@@ -1743,16 +1710,15 @@ def edge_dot(a, b, edges, out=None):
               and out.numel() == n_e and out.is_contiguous()):
         raise ValueError("edge_dot: `out` must be a contiguous float32 [E] tensor on the matrices' device")
     step, lo = max(int(EDGE_DOT_MAX_EDGES), 1), 0
-    with torch.cuda.device(a.device):
-        while lo < n_e:
-            m = min(step, n_e - lo)
-            rc = lib().sgl_edge_dot_f32(ptr(a), _ld(a), a.shape[0], ptr(b), _ld(b), b.shape[0], c_void_p(edges.data_ptr() + 16 * lo), m, d,
-                                        c_void_p(out.data_ptr() + 4 * lo), current_stream_ptr())
-            if rc == _lib.SGL_ERR_UNSUPPORTED and m > 1:      # more than one launch covers: halve
-                step = (m + 1) // 2
-                continue
-            check(rc, "sgl_edge_dot_f32")
-            lo += m
+    while lo < n_e:
+        m = min(step, n_e - lo)
+        rc = _call(a.device, "sgl_edge_dot_f32", ptr(a), _ld(a), a.shape[0], ptr(b), _ld(b), b.shape[0], c_void_p(edges.data_ptr() + 16 * lo),
+                   m, d, c_void_p(out.data_ptr() + 4 * lo), raw=True)
+        if rc == _lib.SGL_ERR_UNSUPPORTED and m > 1:      # more than one launch covers: halve
+            step = (m + 1) // 2
+            continue
+        check(rc, "sgl_edge_dot_f32")
+        lo += m
     _wrote(out)
     return out
 
@@ -1762,43 +1728,9 @@ def gather_rows(x, idx, out=None):
     preallocated [len(idx), d] destination (the pack step of the need-aware exchange re-uses one send buffer per hop).
     A bfloat16 x (bf16 hop storage) is gathered into float32 (sgl_gather_rows_bf16_f32): `out`, given or not, is float32."""
     _check_mat(x, "x", bf16=True)
-    n_rows, d = x.shape
-    idx = _device_index(idx, n_rows, x.device)
-    if x.dtype == torch.bfloat16:
-        if out is not None:
-            _check_mat(out, "out")
-            if out.shape != (idx.numel(), d):
-                raise ValueError("gather_rows: `out` must be [len(idx), d]")
-        return _gather_bf16([x], idx, None if out is None else [out])[0]
-    own_out = out is None
-    if out is None:
-        # (the pad columns of our own output are written by the kernel below whenever the vector path applies: no separate zero fill)
-        fast = (n_rows > 1 and idx.numel() > 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and 0 < row_pitch(d) - d < 32
-                and x.stride(0) >= round_up(d, 4)
-                and x.untyped_storage().nbytes() // 4 - x.storage_offset() >= (n_rows - 1) * x.stride(0) + round_up(d, 4))
-        out = alloc_rows(idx.numel(), d, x.device, zero_pad=not fast)
-    else:
+    idx = _device_index(idx, x.shape[0], x.device)
+    if out is not None:
         _check_mat(out, "out")
-        if out.shape != (idx.numel(), d):
+        if out.shape != (idx.numel(), x.shape[1]):
             raise ValueError("gather_rows: `out` must be [len(idx), d]")
-    if idx.numel() == 0:
-        return out
-    # 16-byte lanes for any d: the vector that straddles column d is READ from the source (its pitch is a multiple of 4 floats, and the
-    # storage must hold it for the last row too) but only the d data columns reach the result; the columns of the destination's
-    # padding that get written are written as zeros (sgl_gather_rows_padded_f32) -- never the source's tail, which may be real
-    # data when x is a column view of a wider matrix.  Our own output: its whole pitch is padding we own, so every line of a row is
-    # written whole (a row of 147 floats on a 160-float pitch would otherwise end in a partly written line: a read-modify-write in
-    # HBM); a caller's output: up to the next multiple of 4, as before.
-    dp = round_up(d, 4)
-    ldx, ldo = x.stride(0) if n_rows > 1 else max(x.stride(0), d), out.stride(0) if idx.numel() > 1 else max(out.stride(0), d)
-    room = x.untyped_storage().nbytes() // 4 - x.storage_offset() >= (n_rows - 1) * ldx + dp
-    vec_ok = (n_rows > 1 and idx.numel() > 1 and ldx % 4 == 0 and ldx >= dp and ldo % 4 == 0 and ldo >= dp and room
-              and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0)
-    pad = 0
-    if vec_ok:
-        pad = (ldo - d) if (own_out and ldo - d < 32) else (dp - d)
-    with torch.cuda.device(x.device):
-        check(lib().sgl_gather_rows_padded_f32(ptr(x), _ld(x), n_rows, ptr(idx), idx.numel(), ptr(out), _ld(out), d, pad,
-                                               current_stream_ptr()), "sgl_gather_rows_padded_f32")
-    _wrote(out)
-    return out
+    return _gather([x], idx, None if out is None else [out])[0]

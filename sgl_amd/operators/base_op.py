@@ -124,12 +124,6 @@ def clear_graph_cache():
     dev.clear_power_cache()
 
 
-def _lib_reduce(kind):
-    from .. import _lib
-    return {"sum": _lib.SGL_REDUCE_SUM, "mean": _lib.SGL_REDUCE_MEAN, "wsum": _lib.SGL_REDUCE_WSUM,
-            "max": _lib.SGL_REDUCE_MAX, "min": _lib.SGL_REDUCE_MIN}[kind]
-
-
 class GraphOp:
     def __init__(self, prop_steps, device=None, host_output=None, strict_types=None, strict_order=None, cache_adj=None,
                  slab_hops=None, reorder=None, hop_cache_dir=None, hop_dtype=None):
@@ -256,7 +250,7 @@ class GraphOp:
         device = self._adj.device
         x0 = feature if (isinstance(feature, Tensor) and feature.is_cuda and feature.dtype == torch.float32) else None
         cur = dev.upload_rows(feature, device) if x0 is None else x0
-        if (cur.shape[1] > 1 and cur.stride(1) != 1) or cur.data_ptr() % 16 != 0 or \
+        if (cur.shape[1] > 1 and cur.stride(1) != 1) or not dev.rows_vectored(cur, single_row=True) or \
                 (cur.shape[0] > 1 and cur.stride(0) != dev.row_pitch(cur.shape[1])):
             cur = dev.upload_rows(cur, device)  # re-pack into an aligned buffer with the line-aware row pitch
         return cur
@@ -282,68 +276,41 @@ class GraphOp:
                 return None
         bf16 = self._bf16_hops()
         self._checked(adj, feature)
+        # The two pieces that depend on the hop dtype: hop 0 as the SpMM reads it, and (first_term) how the aggregate starts.
+        # bfloat16 hops are stored (two buffers alive) and read back as bf16; the running aggregate is float32, starts from the widened
+        # STORED hop s and takes every later hop as stored (sgl_spmm_acc_bf16) -- bit for bit hop_reduce over the widened hops
+        # propagate() would return.  `last` returns the bfloat16 hop K itself.
         if bf16:
-            return self._propagate_reduce_bf16(feature, kind, s, e, w if kind == "wsum" else None, divisor)
-        cur = self._device_features(feature)
-        d = cur.shape[1]
-        src = dev.padded_parent(cur) if cur.stride(0) % 4 == 0 else cur
-        n = self._adj.shape[0]
-        bufs = [dev.padded_parent(dev.alloc_rows(n, d, src.device)) for _ in range(min(2, e - 1))]
-
-        def begin(x_s):           # the aggregate's first term, with the aggregator kernel's own arithmetic
-            if kind == "wsum":
-                return dev.padded_parent(dev.hop_reduce(_lib_reduce("wsum"), [x_s[:, :d]], torch.tensor(w[:1])))
-            return dev.padded_parent(dev.hop_reduce(_lib_reduce(kind if kind in ("max", "min") else "sum"), [x_s[:, :d]]))
-
-        acc = begin(src) if (s == 0 and kind != "last") else None
-        x = src
-        for h in range(1, e):
-            y = bufs[(h - 1) % len(bufs)]
-            if acc is not None:
-                last = h == e - 1
-                div = float(divisor if divisor is not None else (e - s)) if (kind == "mean" and last) else 1.0
-                self._adj.spmm_acc(x, y, acc, w=w[h - s] if kind == "wsum" else 1.0, divisor=div,
-                                   mode=kind if kind in ("wsum", "max", "min") else "sum")
-            else:
-                self._adj.spmm(x, out=y)
-                if h == s and kind != "last":
-                    acc = begin(y)
-            x = y
-        if kind == "last":
-            return x[:, :d] if x.shape[1] != d else x
-        if kind == "mean" and e - s == 1:      # a single hop in range: the division has no SpMM to ride on
-            acc = acc / torch.tensor(float(divisor if divisor is not None else 1), device=acc.device)   # true division
-        return acc[:, :d] if acc.shape[1] != d else acc
-
-    def _propagate_reduce_bf16(self, feature, kind, s, e, w, divisor):
-        """propagate_reduce over bfloat16 hops (sgl_spmm_acc_bf16): the hops are stored (two buffers alive) and read back as bf16,
-        the running aggregate is float32, starts from the widened STORED hop s and takes every later hop as stored -- bit for bit
-        hop_reduce over the widened hops propagate() would return.  `last` returns the bfloat16 hop K itself."""
-        x0 = self._device_features_bf16(feature)
+            x0 = self._device_features_bf16(feature)
+            x = dev.padded_parent(x0)
+        else:
+            x0 = self._device_features(feature)
+            x = dev.padded_parent(x0) if dev.pitch_vectored(x0) else x0
         d = x0.shape[1]
-        x = dev.padded_parent(x0)
         n, W = self._adj.shape[0], x.shape[1]
-        bufs = [dev.padded_parent(dev.alloc_rows(n, d, x.device, dtype=torch.bfloat16)) for _ in range(min(2, e - 1))]
+        bufs = [dev.padded_parent(dev.alloc_rows(n, d, x.device, dtype=x.dtype)) for _ in range(min(2, e - 1))]
 
-        def begin(x_s):           # the aggregate's first term, with the aggregator kernel's own arithmetic, over the whole pitch
-            wide = torch.empty((n, W), dtype=torch.float32, device=x_s.device)
-            wide.copy_(x_s)
-            if kind == "wsum":
-                return dev.padded_parent(dev.hop_reduce(_lib_reduce("wsum"), [wide], torch.tensor(w[:1])))
-            return dev.padded_parent(dev.hop_reduce(_lib_reduce(kind if kind in ("max", "min") else "sum"), [wide]))
+        def first_term(x_s):      # with the aggregator kernel's own arithmetic: float32 over the d columns, bfloat16 over the whole pitch
+            if bf16:
+                t = torch.empty((n, W), dtype=torch.float32, device=x_s.device)
+                t.copy_(x_s)
+            else:
+                t = x_s[:, :d]
+            op = dev.HOP_KINDS[kind if kind in ("wsum", "max", "min") else "sum"][0]
+            return dev.padded_parent(dev.hop_reduce(op, [t], torch.tensor(w[:1]) if kind == "wsum" else None))
 
-        acc = begin(x) if (s == 0 and kind != "last") else None
+        acc = first_term(x) if (s == 0 and kind != "last") else None
         for h in range(1, e):
             y = bufs[(h - 1) % len(bufs)]
             if acc is not None:
                 last = h == e - 1
                 div = float(divisor if divisor is not None else (e - s)) if (kind == "mean" and last) else 1.0
-                self._adj.spmm_acc(x, y, acc[:, :W] if acc.shape[1] != W else acc, w=w[h - s] if kind == "wsum" else 1.0, divisor=div,
-                                   mode=kind if kind in ("wsum", "max", "min") else "sum")
+                self._adj.spmm_acc(x, y, acc[:, :W] if (bf16 and acc.shape[1] != W) else acc, w=w[h - s] if kind == "wsum" else 1.0,
+                                   divisor=div, mode=kind if kind in ("wsum", "max", "min") else "sum")
             else:
                 self._adj.spmm(x, out=y)
                 if h == s and kind != "last":
-                    acc = begin(y)
+                    acc = first_term(y)
             x = y
         if kind == "last":
             return x[:, :d] if x.shape[1] != d else x
@@ -473,7 +440,7 @@ class GraphOp:
             views[0].copy_(cur)
             self._adj.spmm_chain(views[0], K, outs=views[1:])
             return views
-        src = dev.padded_parent(cur) if cur.stride(0) % 4 == 0 else cur
+        src = dev.padded_parent(cur) if dev.pitch_vectored(cur) else cur
         if self._opt("host_output"):
             pooled = self._propagate_to_pooled_host(feature, cur, src, d, K)
             if pooled is not None:

@@ -43,6 +43,61 @@ def test_library_exports_every_declared_symbol():
     assert _lib.probe_lib().sgl_probe_last_error() == b""
 
 
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+             "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def header_declarations(header):
+    """{name: (return type, [parameter types])} of every function declared in include/<header>: the types as C text without the
+    parameter names ('const float *const *', 'int64_t', ...); an array parameter counts as the pointer it is"""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^\s*#[^\n]*(\\\n[^\n]*)*", " ", text, flags=re.M)
+    decls = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?[\s\*])(\w+)\s*\(([^()]*)\)\s*;", text):
+        if "typedef" in ret.split():
+            continue
+        types = []
+        for p in (q.strip() for q in params.split(",")):
+            if p in ("", "void"):
+                continue
+            m = re.fullmatch(r"(.*?[\s\*])(\w+)((?:\s*\[[^\]]*\])*)", p, flags=re.S)
+            assert m, (name, p)
+            types.append(" ".join(m.group(1).split()) + (" *" if m.group(3) else ""))
+        decls[name] = (" ".join(ret.split()), types)
+    return decls
+
+
+def binding_matches(c_type, ctype, returned=False):
+    """a pointer against c_void_p / c_char_p / POINTER(...), a scalar against exactly its ctypes class, void against None"""
+    if "*" in c_type:
+        return ctype in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, ctypes._Pointer))
+    base = " ".join(w for w in c_type.split() if w != "const")
+    if returned and base == "void":
+        return ctype is None
+    return base in C_SCALARS and ctype is C_SCALARS[base]
+
+
+def test_binding_agrees_with_the_headers_in_every_type():
+    """a c_int where the header says int64_t, or a c_float where it says double, corrupts a call silently: every declaration of
+    both headers against its row of PROTOTYPES / PROBE_PROTOTYPES, return type and each argument"""
+    assert binding_matches("int64_t", ctypes.c_int64) and not binding_matches("int64_t", ctypes.c_int)
+    assert not binding_matches("double", ctypes.c_float) and not binding_matches("const float *", ctypes.c_float)
+    assert binding_matches("void **", ctypes.POINTER(ctypes.c_void_p)) and not binding_matches("int", ctypes.c_void_p)
+    for header, table in (("sgl_hip.h", _lib.PROTOTYPES), ("sgl_probe.h", _lib.PROBE_PROTOTYPES)):
+        decls = header_declarations(header)
+        # every declaration was read (one the parser cannot read fails here instead of being skipped), and nothing else
+        assert len(decls) == len(table) and sorted(decls) == sorted(table) == header_functions(header), sorted(set(decls) ^ set(table))
+        for name, (ret, params) in decls.items():
+            restype, argtypes = table[name]
+            assert binding_matches(ret, restype, returned=True), (name, ret, restype)
+            assert len(argtypes) == len(params), (name, len(argtypes), params)
+            for i, (c_type, ctype) in enumerate(zip(params, argtypes)):
+                assert binding_matches(c_type, ctype), (name, i, c_type, ctype)
+    assert len(_lib.PROTOTYPES) >= 83 and len(_lib.PROBE_PROTOTYPES) >= 8
+
+
 def test_device_count_never_aborts():
     assert _lib.device_count() >= 0
 
