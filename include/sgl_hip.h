@@ -29,6 +29,7 @@
  *   sgl_gather_rows_f32        the `feat[idx]` row gather of BaseSGAPModel.forward (sgl/models/base_model.py:58,60).
  *   sgl_edge_dot_f32           `torch.mm(Z, Z.t())[e0, e1]`, the edge scores of link prediction (sgl/tasks/link_prediction.py:282-283,
  *                              sgl/tasks/utils.py:281-285), without the N x N matrix.
+ *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
  *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
  *   sgl_hop_concat_bf16(_f32), STORED as bfloat16 (opt-in hop storage): read in place, widened exactly, float32 arithmetic in
  *   sgl_nafs_bf16_f32          the float32 entries' order -- bit-identical to widening every hop first, without the copies.
@@ -512,6 +513,18 @@ int sgl_scatter_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const in
  * than one launch covers -> SGL_ERR_UNSUPPORTED (split the list: edges are independent). */
 int sgl_edge_dot_f32(const float *d_a, int64_t lda, int64_t n_a, const float *d_b, int64_t ldb, int64_t n_b,
                      const int64_t *d_edges, int64_t n_edges, int64_t d, float *d_out, void *stream);
+
+/* The assignment step of k-means: labels[i] = argmin_j sum_c (X[i, c] - C[j, c])^2 (int64) and, when d_mindist is not NULL, that
+ * minimum -- what KMeans.fit_predict spends its time on in NodeClusteringNAFS (sgl/tasks/node_clustering.py:254-255).  The distance is
+ * the direct sum of squared differences (fmaf; translation-invariant, no |x|^2 - 2 x.c + |c|^2), centres staged in LDS tiles of at
+ * most 64 KiB with a running best across tiles: any k x d.  The lowest centre index wins a tie; a NaN distance never wins, and a row
+ * whose distances are all NaN (a NaN in the row) gets label 0 and mindist NaN -- the kernel never traps.  Columns d .. pitch are
+ * never used (they may hold NaN), nothing beyond column d of a matrix's last row is read.  16-byte aligned bases with pitches that are
+ * multiples of 4 floats (X and C) get 16-byte lane accesses, everything else one float per lane; the summation order depends on d and
+ * that layout alone: not on n, k, the tile or the row's position, and two runs are bit-equal (no atomics).  n = 0: nothing is done;
+ * d = 0: labels 0, distances 0. */
+int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_centres, int64_t ldc, int64_t k,
+                          int64_t *d_labels, float *d_mindist, void *stream);
 
 /* Per-column content signature of a DEVICE matrix: d_sig[c] = wrapping 64-bit sum over the rows r of mix(bits(X[r, c]), r), for
  * c < round_up(d, 4) (uint64 on device; rows 16-byte aligned, pitch a multiple of 4 floats covering round_up(d, 4)).  One streaming

@@ -26,28 +26,6 @@ namespace {
 using i64x2 = long __attribute__((ext_vector_type(2)));
 static_assert(sizeof(i64x2) == 16, "an edge is two int64");
 
-// the vector of row `p` at column c: whole when it lies inside the row's d columns or (not the last row) inside its pitch
-template <int VEC>
-__device__ __forceinline__ typename Vt<VEC>::type edge_load(const float *__restrict__ p, const int c, const int d, const bool last_row) {
-    if constexpr (VEC == 4) {
-        f4 v;
-        if (c + 4 <= d) {
-            v = *reinterpret_cast<const f4 *>(p + c);
-        } else if (!last_row) {
-            v = *reinterpret_cast<const f4 *>(p + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (c + e >= d) v[e] = 0.f;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = (c + e < d) ? p[c + e] : 0.f;
-        }
-        return v;
-    } else {
-        return p[c];
-    }
-}
-
 template <int LPR, int VEC, int U>
 __global__ __launch_bounds__(256) void edge_dot_kernel(const float *__restrict__ a, const int64_t lda, const int64_t n_a,
                                                        const float *__restrict__ b, const int64_t ldb, const int64_t n_b,

@@ -44,6 +44,28 @@ __device__ __forceinline__ typename Vt<VEC>::type load_masked(const float *p, in
     return v;
 }
 
+// The vector of row `p` at column c where the pad may not be read (sgl_edge.hip, sgl_kmeans.hip): whole when it lies inside the row's d columns or (not the last row) inside its pitch
+template <int VEC>
+__device__ __forceinline__ typename Vt<VEC>::type edge_load(const float *__restrict__ p, const int c, const int d, const bool last_row) {
+    if constexpr (VEC == 4) {
+        f4 v;
+        if (c + 4 <= d) {
+            v = *reinterpret_cast<const f4 *>(p + c);
+        } else if (!last_row) {
+            v = *reinterpret_cast<const f4 *>(p + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c + e >= d) v[e] = 0.f;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = (c + e < d) ? p[c + e] : 0.f;
+        }
+        return v;
+    } else {
+        return p[c];
+    }
+}
+
 // ---- row-wise reductions: LPR lanes cooperate on one row, 64/LPR rows per wavefront ------------------------
 // All-lanes sum over groups of LPR consecutive lanes.  Inside a 16-lane row the exchange is done by the VALU's DPP
 // modifiers (quad permutes, half-row / row mirrors) -- no LDS-crossbar instruction; only the steps that cross rows

@@ -1723,6 +1723,25 @@ def edge_dot(a, b, edges, out=None):
     return out
 
 
+def kmeans_assign(x, centres, want_dist=True):
+    """(labels, mindist) of the k-means assignment step (sgl_kmeans_assign_f32): labels[i] = argmin_j |x[i] - centres[j]|^2 (int64 [n],
+    the lowest index on a tie) and that minimum (float32 [n]; None with want_dist=False) -- the direct sum of squared differences, not
+    the expanded form.  x: [n, d], centres: [k, d] float32 CUDA matrices on one device, read in place (padded buffers, column views).
+    A row that holds NaN gets label 0 and mindist NaN.  No atomics: two runs are bit-equal."""
+    _no_bf16("kmeans_assign", x, centres)
+    _check_mat(x, "x")
+    _check_mat(centres, "centres")
+    if x.shape[1] != centres.shape[1] or x.device != centres.device:
+        raise ValueError("kmeans_assign: x and centres must have the same row length and live on one device")
+    n, k = x.shape[0], centres.shape[0]
+    if k < 1 and n > 0:
+        raise ValueError("kmeans_assign: at least one centre is needed")
+    labels = torch.empty(n, dtype=torch.int64, device=x.device)
+    mindist = torch.empty(n, dtype=torch.float32, device=x.device) if want_dist else None
+    _call(x.device, "sgl_kmeans_assign_f32", ptr(x), _ld(x), n, x.shape[1], ptr(centres), _ld(centres), k, ptr(labels), _opt_ptr(mindist))
+    return labels, mindist
+
+
 def gather_rows(x, idx, out=None):
     """x[idx] on device (BaseSGAPModel.forward's per-step row gather, models/base_model.py:58,60).  `out`: optional
     preallocated [len(idx), d] destination (the pack step of the need-aware exchange re-uses one send buffer per hop).

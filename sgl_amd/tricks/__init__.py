@@ -1,8 +1,10 @@
 """Consumers of the same device SpMM beyond GraphOp.propagate:
 label propagation / Correct&Smooth (reference: sgl/tricks) and the NAFS feature-smoothing pipeline of the
 NAFS clustering / link-prediction tasks (reference: sgl/tasks/node_clustering.py:205-258); the edge scores and ranking metrics that
-end the link-prediction task (sgl/tasks/link_prediction.py:282-283, without the N x N matrix); and the label use / label reuse
+end the link-prediction task (sgl/tasks/link_prediction.py:282-283, without the N x N matrix); the k-means and the three
+scores that end the clustering task (sgl/tasks/node_clustering.py:254-257); and the label use / label reuse
 loop around `model.preprocess` (reference: sgl/tasks/node_classification_with_label_use.py:58-137)."""
+from .clustering import KMeansResult, NodeClusteringResult, clustering_scores, kmeans, nafs_node_clustering
 from .correct_and_smooth import CorrectAndSmooth
 from .label_reuse import add_labels, label_reuse, predict_all
 from .link_prediction import LinkPredictionResult, binary_ranking_metrics, edge_predict_score, edge_scores, nafs_link_prediction
@@ -10,4 +12,5 @@ from .nafs_features import nafs_ensemble_features, nafs_ensemble_sweep
 from .utils import label_propagation
 
 __all__ = ["CorrectAndSmooth", "label_propagation", "nafs_ensemble_features", "nafs_ensemble_sweep", "add_labels", "label_reuse", "predict_all",
-           "edge_scores", "binary_ranking_metrics", "edge_predict_score", "nafs_link_prediction", "LinkPredictionResult"]
+           "edge_scores", "binary_ranking_metrics", "edge_predict_score", "nafs_link_prediction", "LinkPredictionResult",
+           "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult"]
