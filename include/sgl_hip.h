@@ -29,6 +29,8 @@
  *   sgl_gather_rows_f32        the `feat[idx]` row gather of BaseSGAPModel.forward (sgl/models/base_model.py:58,60).
  *   sgl_edge_dot_f32           `torch.mm(Z, Z.t())[e0, e1]`, the edge scores of link prediction (sgl/tasks/link_prediction.py:282-283,
  *                              sgl/tasks/utils.py:281-285), without the N x N matrix.
+ *   sgl_csr_find,              the edge set and the random negative pairs of mask_test_edges (sgl/tasks/utils.py:148-259): is (i, j)
+ *   sgl_edge_candidates        stored, as a search inside one CSR row; a seeded candidate stream with each pair's verdict.
  *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
  *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
  *   sgl_hop_concat_bf16(_f32), STORED as bfloat16 (opt-in hop storage): read in place, widened exactly, float32 arithmetic in
@@ -513,6 +515,27 @@ int sgl_scatter_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const in
  * than one launch covers -> SGL_ERR_UNSUPPORTED (split the list: edges are independent). */
 int sgl_edge_dot_f32(const float *d_a, int64_t lda, int64_t n_a, const float *d_b, int64_t ldb, int64_t n_b,
                      const int64_t *d_edges, int64_t n_edges, int64_t d, float *d_out, void *stream);
+
+/* Where a list of pairs is stored in a canonical CSR (columns sorted and unique inside each row -- what sgl_coo_to_csr produces; not
+ * checked): pos[q] = the p in [rowptr[u_q], rowptr[u_q + 1]) with col[p] == v_q, or -1 when (u_q, v_q) is not stored.  The membership
+ * test behind the reference's `edges_all_set` (sgl/tasks/utils.py:166-168, 187) as a search inside one row: two rowptr reads and
+ * ceil(log2(len + 1)) probes per pair, no nnz-sized key array.  d_edges: int64 [n_q, 2] row-major, 8-byte aligned is enough.  Negative
+ * indices count from the end (u against n_rows, v against n_cols); a pair still outside gives -1 and reads nothing -- the kernel
+ * never traps (the rule of sgl_edge_dot_f32).  n_cols <= INT32_MAX.  n_q = 0: nothing is done; more pairs than one launch covers ->
+ * SGL_ERR_UNSUPPORTED (split the list: pairs are independent). */
+int sgl_csr_find(const int64_t *d_rowptr, const int32_t *d_col, int64_t n_rows, int64_t n_cols, const int64_t *d_edges, int64_t n_q,
+                 int64_t *d_pos, void *stream);
+
+/* The candidate stream of the negative edges of a link-prediction split (the np.random.randint pairs of the reference's
+ * mask_test_edges, sgl/tasks/utils.py:181-236), for the candidates t = first .. first + count - 1 of an [n, n] canonical CSR:
+ *     i = mulhi64(h(seed, 102, t, 0), n),  j = mulhi64(h(seed, 102, t, 1), n)        h: the hash of csrc/sgl_hash.h,
+ *                                                                                    mulhi64(h, n) = floor(h n / 2^64)
+ *     d_edges[t - first] = (i, j)          int64 [count, 2]
+ *     d_key[t - first]   = min(i, j) * n + max(i, j)  when i != j and (i, j) is not stored, else -1
+ * A candidate depends on (seed, t) alone: any division of a range into calls gives the same bytes.  1 <= n < 2^31 (the key fits
+ * int64).  count = 0: nothing is done; more candidates than one launch covers -> SGL_ERR_UNSUPPORTED (split the range). */
+int sgl_edge_candidates(const int64_t *d_rowptr, const int32_t *d_col, int64_t n, uint64_t seed, int64_t first, int64_t count,
+                        int64_t *d_edges, int64_t *d_key, void *stream);
 
 /* The assignment step of k-means: labels[i] = argmin_j sum_c (X[i, c] - C[j, c])^2 (int64) and, when d_mindist is not NULL, that
  * minimum -- what KMeans.fit_predict spends its time on in NodeClusteringNAFS (sgl/tasks/node_clustering.py:254-255).  The distance is

@@ -12,23 +12,11 @@
 //   val(row, j)    = (h(seed, 2, row, j) >> 40) * 2^-29                     in [0, 1/32), exact in fp32
 //   x(row, k)      = ((h(seed, 3, row, k) >> 40) - 2^23) * 2^-23            in [-1, 1),   exact in fp32
 #include "sgl_common.h"
+#include "sgl_hash.h"   // mix64, hash4, mulhi64
 
 #include "../../include/sgl_probe.h"
 
 namespace {
-
-__host__ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-__host__ __device__ __forceinline__ uint64_t hash4(uint64_t seed, uint64_t stream, uint64_t a, uint64_t b) {
-    return mix64(mix64(mix64(seed * 0x9E3779B97F4A7C15ull + stream) ^ a) + b);
-}
-
-__device__ __forceinline__ uint64_t mulhi64(uint64_t a, uint64_t b) { return __umul64hi(a, b); }
 
 // keyed balanced Feistel network on 2*half bits, cycle-walked into [0, n)
 __device__ __forceinline__ uint64_t permute_id(uint64_t x, uint64_t n, int half, uint64_t key) {

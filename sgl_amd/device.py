@@ -1709,18 +1709,76 @@ def edge_dot(a, b, edges, out=None):
     elif not (torch.is_tensor(out) and out.is_cuda and out.device == a.device and out.dtype == torch.float32 and out.dim() == 1
               and out.numel() == n_e and out.is_contiguous()):
         raise ValueError("edge_dot: `out` must be a contiguous float32 [E] tensor on the matrices' device")
-    step, lo = max(int(EDGE_DOT_MAX_EDGES), 1), 0
-    while lo < n_e:
-        m = min(step, n_e - lo)
-        rc = _call(a.device, "sgl_edge_dot_f32", ptr(a), _ld(a), a.shape[0], ptr(b), _ld(b), b.shape[0], c_void_p(edges.data_ptr() + 16 * lo),
-                   m, d, c_void_p(out.data_ptr() + 4 * lo), raw=True)
-        if rc == _lib.SGL_ERR_UNSUPPORTED and m > 1:      # more than one launch covers: halve
-            step = (m + 1) // 2
-            continue
-        check(rc, "sgl_edge_dot_f32")
-        lo += m
+    _split_calls("sgl_edge_dot_f32", n_e,
+                 lambda lo, m: _call(a.device, "sgl_edge_dot_f32", ptr(a), _ld(a), a.shape[0], ptr(b), _ld(b), b.shape[0],
+                                     c_void_p(edges.data_ptr() + 16 * lo), m, d, c_void_p(out.data_ptr() + 4 * lo), raw=True))
     _wrote(out)
     return out
+
+
+def _split_calls(name, n_items, one):
+    """edge_dot's list splitting for an entry point whose items are independent: `one(lo, m)` makes the call for the items
+    [lo, lo + m) and returns its unchecked code; a piece more than one launch covers (SGL_ERR_UNSUPPORTED) is halved."""
+    step, lo = max(int(EDGE_DOT_MAX_EDGES), 1), 0
+    while lo < n_items:
+        m = min(step, n_items - lo)
+        rc = one(lo, m)
+        if rc == _lib.SGL_ERR_UNSUPPORTED and m > 1:
+            step = (m + 1) // 2
+            continue
+        check(rc, name)
+        lo += m
+
+
+def _csr_arrays(adj, who):
+    """(rowptr, col) of a device CSR (DeviceAdjacency or anything with its fields) as the two search entries take them; a matrix
+    without entries gets one unread column slot, so that the pointer is never NULL"""
+    rowptr, col = adj.rowptr, adj.col
+    if not (torch.is_tensor(rowptr) and rowptr.is_cuda and rowptr.dtype == torch.int64 and rowptr.is_contiguous()
+            and rowptr.numel() == adj.shape[0] + 1):
+        raise TypeError(f"{who}: adj.rowptr must be a contiguous int64 CUDA tensor of n_rows + 1 offsets")
+    if not (torch.is_tensor(col) and col.device == rowptr.device and col.dtype == torch.int32 and col.is_contiguous()):
+        raise TypeError(f"{who}: adj.col must be a contiguous int32 tensor on the device of adj.rowptr")
+    if col.numel() == 0:
+        col = torch.zeros(1, dtype=torch.int32, device=rowptr.device)
+    return rowptr, col
+
+
+def csr_find(adj, edges):
+    """pos[q] = where the pair edges[q] = (u, v) is stored in the canonical device CSR `adj` (a DeviceAdjacency: columns sorted and
+    unique inside each row): the p in [rowptr[u], rowptr[u + 1]) with col[p] == v, or -1 (sgl_csr_find: a search inside one row per
+    pair).  edges: see _device_edges.  Negative indices count from the end; in a DEVICE index tensor a pair outside the matrix gives
+    -1 (host indices raise IndexError).  Returns an int64 [Q] tensor.  Lists too long for one launch are split."""
+    rowptr, col = _csr_arrays(adj, "csr_find")
+    n_rows, n_cols = adj.shape
+    edges = _device_edges(edges, n_rows, n_cols, rowptr.device)
+    pos = torch.empty(edges.shape[0], dtype=torch.int64, device=rowptr.device)
+    _split_calls("sgl_csr_find", edges.shape[0],
+                 lambda lo, m: _call(rowptr.device, "sgl_csr_find", ptr(rowptr), ptr(col), n_rows, n_cols, c_void_p(edges.data_ptr() + 16 * lo), m,
+                                     c_void_p(pos.data_ptr() + 8 * lo), raw=True))
+    _wrote(pos)
+    return pos
+
+
+def edge_candidates(adj, seed, first, count):
+    """(edges int64 [count, 2], key int64 [count]) for the candidates first .. first + count - 1 of the seeded stream of ordered pairs
+    over the square canonical device CSR `adj` (sgl_edge_candidates): key = min(i, j) * n + max(i, j) when i != j and (i, j) is not
+    stored, else -1.  A candidate depends on (seed, its number) alone, so ranges can be drawn in any pieces."""
+    rowptr, col = _csr_arrays(adj, "edge_candidates")
+    n = adj.shape[0]
+    first, count = int(first), int(count)
+    if adj.shape[1] != n or n < 1:
+        raise ValueError("edge_candidates: adj must be square with at least one node")
+    if first < 0 or count < 0:
+        raise ValueError("edge_candidates: first and count must not be negative")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    edges = torch.empty((count, 2), dtype=torch.int64, device=rowptr.device)
+    key = torch.empty(count, dtype=torch.int64, device=rowptr.device)
+    _split_calls("sgl_edge_candidates", count,
+                 lambda lo, m: _call(rowptr.device, "sgl_edge_candidates", ptr(rowptr), ptr(col), n, seed, first + lo, m,
+                                     c_void_p(edges.data_ptr() + 16 * lo), c_void_p(key.data_ptr() + 8 * lo), raw=True))
+    _wrote(edges, key)
+    return edges, key
 
 
 def kmeans_assign(x, centres, want_dist=True):

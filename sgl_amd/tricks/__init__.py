@@ -7,10 +7,12 @@ loop around `model.preprocess` (reference: sgl/tasks/node_cl
 from .clustering import KMeansResult, NodeClusteringResult, clustering_scores, kmeans, nafs_node_clustering
 from .correct_and_smooth import CorrectAndSmooth
 from .label_reuse import add_labels, label_reuse, predict_all
-from .link_prediction import LinkPredictionResult, binary_ranking_metrics, edge_predict_score, edge_scores, nafs_link_prediction
+from .link_prediction import (EdgeSplit, LinkPredictionResult, binary_ranking_metrics, edge_predict_score, edge_scores, has_edges,
+                              mask_test_edges, nafs_link_prediction)
 from .nafs_features import nafs_ensemble_features, nafs_ensemble_sweep
 from .utils import label_propagation
 
 __all__ = ["CorrectAndSmooth", "label_propagation", "nafs_ensemble_features", "nafs_ensemble_sweep", "add_labels", "label_reuse", "predict_all",
            "edge_scores", "binary_ranking_metrics", "edge_predict_score", "nafs_link_prediction", "LinkPredictionResult",
+           "has_edges", "mask_test_edges", "EdgeSplit",
            "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult"]
