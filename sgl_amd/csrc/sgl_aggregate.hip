@@ -1121,20 +1121,26 @@ __global__ __launch_bounds__(256) void gather_hops_y_kernel(const Hops hx, const
     }
 }
 
-// out[:, h*d + k] = X_h[:, k]
+// out[:, h*d + k] = X_h[:, k]; then the row's declared pad columns [H d, H d + padv * VEC) as zeros (padv lane accesses per row, 0:
+// none), in the same pass: a row's last line is written by neighbouring threads of one launch
 template <int VEC>
 __global__ __launch_bounds__(256) void hop_concat_kernel(const Hops hx, const int n_hops, float *__restrict__ out,
-                                                         const int64_t ldo, const int64_t n, const int d) {
+                                                         const int64_t ldo, const int64_t n, const int d, const int64_t padv) {
     using V = typename Vt<VEC>::type;
     const int dv = d / VEC;
-    const int64_t per_hop = n * (int64_t)dv;
-    const int64_t total = per_hop * n_hops;
+    const int64_t row_v = (int64_t)dv * n_hops;     // lane accesses that copy
+    const int64_t per_row = row_v + padv;
+    const int64_t total = n * per_row;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-        const int64_t row = i / ((int64_t)dv * n_hops);
-        const int rem = (int)(i - row * (int64_t)dv * n_hops);
-        const int h = rem / dv;
-        const int col = (rem - h * dv) * VEC;
+        const int64_t row = i / per_row;
+        const int64_t rem = i - row * per_row;
+        if (rem >= row_v) {
+            *reinterpret_cast<V *>(out + row * ldo + (int64_t)n_hops * d + (rem - row_v) * VEC) = (V)(0.f);
+            continue;
+        }
+        const int h = (int)rem / dv;
+        const int col = ((int)rem - h * dv) * VEC;
         *reinterpret_cast<V *>(out + row * ldo + (int64_t)h * d + col) =
             *reinterpret_cast<const V *>(hx.p[h] + row * hx.ld[h] + col);
     }
@@ -1825,8 +1831,9 @@ SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, co
     hipStream_t st = sgl::as_stream(stream);
     const bool out16 = (ldo % 4 == 0) && aligned_to(d_out, 16) && d * n_hops < INT32_MAX;
     if (vec4) {
-        const int grid = stream_grid(n * (d / 4) * n_hops);
-        hipLaunchKernelGGL((hop_concat_kernel<4>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d);
+        // d % 4 == 0 and (check_pad) H d + pad_cols a multiple of 4: the pad is whole vectors
+        const int grid = stream_grid(n * ((d / 4) * n_hops + pad_cols / 4));
+        hipLaunchKernelGGL((hop_concat_kernel<4>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d, pad_cols / 4);
     } else if (out16 && d >= 4 && vec4_rows(hx, n_hops) && d * n_hops >= 256 && sgl::out_cols(d * n_hops, pad_cols, INT32_MAX) <= kConcatRowCap &&
                (sgl::tuning("concat_lds", 1) == 3 ||
                 (sgl::tuning("concat_lds", 1) == 1 &&      // where the 1024-float tiles of the kernel below would be < 85 % full
@@ -1858,8 +1865,8 @@ SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, co
         const int grid = stream_grid(n * (((int64_t)width_w + 3) / 4));
         hipLaunchKernelGGL(hop_concat_any_kernel, dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d, width_w);
     } else {
-        const int grid = stream_grid(n * d * n_hops);
-        hipLaunchKernelGGL((hop_concat_kernel<1>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d);
+        const int grid = stream_grid(n * (d * n_hops + pad_cols));
+        hipLaunchKernelGGL((hop_concat_kernel<1>), dim3(grid), dim3(256), 0, st, hx, n_hops, d_out, ldo, n, (int)d, pad_cols);
     }
     SGL_LAUNCH_CHECK("sgl_hop_concat_f32");
     return SGL_OK;

@@ -1,5 +1,6 @@
-"""Shared by the row-register aggregator tests (test_agg_rows_cpu.py, test_gpu_agg_variants.py); no GPU and no torch needed to
-import it.
+"""Shared by the row-register aggregator tests (test_agg_rows_cpu.py, test_gpu_agg_variants.py) and, for the statements at the
+end, by every GPU test module that states the same reference (test_gpu_parity.py, test_gpu_bf16.py, test_gpu_bf16_agg.py,
+test_gpu_far_offsets.py); no GPU and no torch needed to import it (the statements import numpy / torch / the oracle when called).
 
 Restatements, each made ONCE here, of what the library (csrc/sgl_core.cpp) decides on its own for the kernels that keep the hop
 rows of a node in registers:
@@ -199,3 +200,126 @@ def tuned(**kw):
     finally:
         for k, v in saved.items():
             _lib.set_tuning(k, v)
+
+
+# ---- statements shared by several GPU test modules: each is made ONCE here ----------------------------------------------------------
+PARITY_TOL = 1e-5                 # the project's parity contract
+BIAS = 0.37                       # the gate bias of test_gpu_agg_variants.py and test_gpu_far_offsets.py
+
+
+def t64(x):
+    import numpy as np
+    import torch
+    return torch.from_numpy(np.asarray(x)).double()
+
+
+def t32(x):
+    import numpy as np
+    import torch
+    return torch.from_numpy(np.asarray(x)).float()
+
+
+def vector(d, seed, scale):
+    import numpy as np
+    from inputs import hash_matrix
+    return np.ascontiguousarray(hash_matrix(1, d, seed=seed)[0] * np.float32(scale)).astype(np.float32)
+
+
+def gate_reference(host, v, dt):
+    """(out, W, G) of the learnable gate over the host hops with the Linear v and the bias BIAS, plain torch in dtype dt"""
+    import torch
+    ff = [torch.from_numpy(x).to(dt) for x in host]
+    vv = torch.from_numpy(v).to(dt)
+    g = torch.sigmoid(torch.stack([f @ vv + torch.tensor(BIAS, dtype=torch.float32).to(dt) for f in ff], dim=1))
+    w = torch.softmax(g, dim=1)
+    return sum(w[:, h:h + 1] * ff[h] for h in range(len(ff))), w, g
+
+
+def rne(a):
+    """the one definition of rounding to bfloat16: torch's round to nearest even on the CPU"""
+    import numpy as np
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16)
+
+
+def bits32(a):
+    import numpy as np
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same_bits32(got, want):
+    """32-bit patterns equal; where the expected value is a NaN the result must be a NaN (payloads are not compared)"""
+    import numpy as np
+    got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
+    if got.shape != want.shape:
+        return False
+    nan = np.isnan(want)
+    return bool(np.array_equal(np.isnan(got), nan) and np.array_equal(bits32(got)[~nan], bits32(want)[~nan]))
+
+
+def reduce_statement(kind, wide, w):
+    """hop_reduce_kernel's order in numpy float32: sum / mean start from 0 + X_s, mean ends with one true division, the weighted
+    sum is a rounded product, then an add, max / min propagate NaN"""
+    import numpy as np
+    with np.errstate(all="ignore"):
+        if kind in ("sum", "mean"):
+            acc = np.float32(0.0) + wide[0]
+            for x in wide[1:]:
+                acc = acc + x
+            return acc / np.float32(len(wide)) if kind == "mean" else acc
+        if kind == "wsum":
+            acc = wide[0] * w[0]
+            for h in range(1, len(wide)):
+                acc = acc + wide[h] * w[h]
+            return acc
+        acc = wide[0]
+        for x in wide[1:]:
+            acc = (np.maximum if kind == "max" else np.minimum)(acc, x)
+        return acc
+
+
+def long_row_graph(n=1500, seed=5, unit_rows=False):
+    """power-law rows plus three huge rows (1400, 900 and 1499 non-zeros) and some empty ones (canonical CSR, not symmetric).
+    unit_rows: the values are divided by the square root of their row's length, so that row sums of |a| are of order 1 and several
+    hops stay of order 1 (the bfloat16 tests)"""
+    import numpy as np
+    import scipy.sparse as sp
+    rng = np.random.default_rng(seed)
+    deg = np.minimum(rng.lognormal(1.2, 1.0, n).astype(np.int64), 200)
+    deg[rng.integers(0, n, 60)] = 0
+    deg[[3, 700, n - 1]] = [1400, 900, 1499]
+    rows, cols = [], []
+    for i in range(n):
+        c = np.sort(rng.choice(n, int(deg[i]), replace=False))
+        rows.append(np.full(len(c), i))
+        cols.append(c)
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    vals = rng.uniform(-1, 1, len(rows))
+    vals = (vals / np.sqrt(np.maximum(deg[rows], 1)) if unit_rows else vals).astype(np.float32)
+    a = sp.csr_matrix((vals, (rows, cols)), shape=(n, n))
+    a.sort_indices()
+    return a
+
+
+def sig_mix(bits, r):
+    """the mix of sgl_col_signature_f32's definition, sig[c] = sum_r mix(bits(X[r, c]), r) mod 2^64, in numpy uint64"""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        h = (bits.astype(np.uint64) ^ (r.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15))) * np.uint64(0xBF58476D1CE4E5B9)
+        h ^= h >> np.uint64(31)
+        h *= np.uint64(0x94D049BB133111EB)
+        return h ^ (h >> np.uint64(29))
+
+
+def bf16_fast_order_bound(a64, ptr, col, val, xin, got):
+    """(err, bound) per element of one bfloat16 fast-order product from the stored input xin (float32 values of a bf16 matrix):
+    T = the float64 product, R = the oracle (float32, strict order), G = got widened;  b = max(2 max|R - T|, TRUTH_FLOOR max|T|)
+    (truth_report's bound);  |G - T| <= 2^-8 |T| + (1 + 2^-8) b: RNE to 8 significant bits errs by at most 2^-8 relative, the
+    float32 sum in another order gets the standing factor 2"""
+    import numpy as np
+    import oracle
+    T = a64 @ xin.astype(np.float64)
+    R = oracle.oracle_spmm(ptr, col, val, xin).astype(np.float64)
+    G = np.asarray(got).astype(np.float64)
+    b = max(2.0 * np.abs(R - T).max(), oracle.TRUTH_FLOOR * np.abs(T).max())
+    return np.abs(G - T), 2.0 ** -8 * np.abs(T) + (1.0 + 2.0 ** -8) * b

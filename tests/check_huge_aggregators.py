@@ -2,7 +2,11 @@
 """Robustness check at the largest shape of the contract: the aggregators over WHOLE ogbn-papers100M-sized hop matrices
 ([111 059 956, 128] = 14.2 G elements = 57 GB each) on one GPU -- more elements than a 32-bit index, more threads than one HIP
 launch carries.  Checks sampled rows against numpy / the oracle and that kernels which cannot take the shape say so.
-(A script, not a collected test: it needs 120 GB of HBM and a minute.  It lives under tests/ because it uses the oracle.)"""
+(A script, not a collected test: it needs 120 GB of HBM and a minute.  It lives under tests/ because it uses the oracle.)
+The collected suite now covers its claim about 64-bit offsets at smaller sizes: test_gpu_far_offsets.py runs sum / max / the weighted
+sum / NAFS (and every other dense-matrix entry point) with rows beyond 2^32 elements through a large pitch, and sum / max / concat
+over contiguous [16 777 300, 128] matrices, just over 2^31 elements.  What only this script does: contiguous matrices beyond 2^32
+elements, and more threads than one launch carries."""
 import os
 import sys
 

@@ -17,8 +17,8 @@ import pytest
 import torch
 
 import oracle
-from agg_rows_common import (FAMILIES, HOP_SWEEP, N_ROWS, WIDTH_8X5, case_list, compiled_variants, expected_kernel,
-                             parse_agg_kernel_name, recursive_step_by_step, tuned)
+from agg_rows_common import (BIAS, FAMILIES, HOP_SWEEP, N_ROWS, WIDTH_8X5, case_list, compiled_variants, expected_kernel, gate_reference,
+                             parse_agg_kernel_name, recursive_step_by_step, t32, t64, tuned, vector)
 from inputs import hash_matrix
 from sgl_amd import _lib
 from sgl_amd import device as dev
@@ -28,7 +28,6 @@ pytestmark = pytest.mark.gpu
 SENTINEL = 7.0
 POISONS = (float("nan"), 1e30)
 ROUNDING = 2.0 ** -24               # one float32 rounding of a value near 1 (the unit of oracle.TRUTH_FLOOR)
-BIAS = 0.37
 NAN = float("nan")
 
 
@@ -116,10 +115,6 @@ def device_hops(n, d, n_hops, cuda):
     return [per[k][:n_hops] for k in range(len(POISONS))]
 
 
-def vector(d, seed, scale):
-    return np.ascontiguousarray(hash_matrix(1, d, seed=seed)[0] * np.float32(scale)).astype(np.float32)
-
-
 def padded_out(n, d, cuda):
     """(view, parent, pad): an alloc_rows output pre-filled with the sentinel, pad columns included"""
     t = dev.alloc_rows(n, d, cuda, zero_pad=False)
@@ -195,14 +190,6 @@ def same(a, b):
     return a.shape == b.shape and torch.equal(a, b)
 
 
-def t64(x):
-    return torch.from_numpy(np.asarray(x)).double()
-
-
-def t32(x):
-    return torch.from_numpy(np.asarray(x)).float()
-
-
 def sweep(family, cuda, one_case, **kw):
     """every case of the family's list under one Trace; the layout keys are set per case"""
     rep = Report(family)
@@ -216,14 +203,6 @@ def sweep(family, cuda, one_case, **kw):
 
 
 # ---- the gate --------------------------------------------------------------------------------------------------------------------
-def gate_reference(host, v, dt):
-    ff = [torch.from_numpy(x).to(dt) for x in host]
-    vv = torch.from_numpy(v).to(dt)
-    g = torch.sigmoid(torch.stack([f @ vv + torch.tensor(BIAS, dtype=torch.float32).to(dt) for f in ff], dim=1))
-    w = torch.softmax(g, dim=1)
-    return sum(w[:, h:h + 1] * ff[h] for h in range(len(ff))), w, g
-
-
 def gate_case(tr, rep, cuda, n, d, H, tuning):
     label = ("gate", n, d, H, tuple(tuning.items()))
     kern = expected_kernel("gate", d, H, tuning)

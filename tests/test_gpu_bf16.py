@@ -10,6 +10,8 @@ import scipy.sparse as sp
 import torch
 
 import oracle
+from agg_rows_common import bf16_fast_order_bound, rne
+from agg_rows_common import long_row_graph as _long_row_graph
 from inputs import hash_matrix
 from sgl_amd import _lib, config
 from sgl_amd import device as dev
@@ -28,10 +30,6 @@ def cuda():
     return torch.device("cuda", 0)
 
 
-def rne(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16)
-
-
 def bits(t):
     """the 16-bit patterns of a bfloat16 tensor (any device / pitch) as a uint16 array"""
     return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
@@ -44,20 +42,7 @@ def widened(t):
 def long_row_graph(n=1500, seed=5):
     """power-law rows plus three rows of >= 900 non-zeros and some empty ones (canonical CSR, not symmetric); row sums of |a|
     are kept of order 1 so that three hops stay of order 1"""
-    rng = np.random.default_rng(seed)
-    deg = np.minimum(rng.lognormal(1.2, 1.0, n).astype(np.int64), 200)
-    deg[rng.integers(0, n, 60)] = 0
-    deg[[3, 700, n - 1]] = [1400, 900, 1499]
-    rows, cols = [], []
-    for i in range(n):
-        c = np.sort(rng.choice(n, int(deg[i]), replace=False))
-        rows.append(np.full(len(c), i))
-        cols.append(c)
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    vals = (rng.uniform(-1, 1, len(rows)) / np.sqrt(np.maximum(deg[rows], 1))).astype(np.float32)
-    a = sp.csr_matrix((vals, (rows, cols)), shape=(n, n))
-    a.sort_indices()
-    return a
+    return _long_row_graph(n, seed, unit_rows=True)
 
 
 def matrix(goldens, name):
@@ -139,12 +124,7 @@ def test_fast_order_per_hop_within_derived_bound(goldens, cuda, gname):
             assert np.array_equal(bits(hops[0]), bits(rne(x)))
             for k in range(1, K + 1):
                 xin = widened(hops[k - 1])
-                T = a64 @ xin.astype(np.float64)
-                R = oracle.oracle_spmm(ptr, col, val, xin).astype(np.float64)
-                G = widened(hops[k]).astype(np.float64)
-                b = max(2.0 * np.abs(R - T).max(), oracle.TRUTH_FLOOR * np.abs(T).max())
-                bound = 2.0 ** -8 * np.abs(T) + (1.0 + 2.0 ** -8) * b
-                err = np.abs(G - T)
+                err, bound = bf16_fast_order_bound(a64, ptr, col, val, xin, widened(hops[k]))
                 worst = max(worst, float((err / np.maximum(bound, 1e-300)).max()))
                 if not (err <= bound).all():
                     bad.append((layout, d, k, float((err - bound).max()), int((err > bound).sum())))

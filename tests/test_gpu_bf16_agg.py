@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import oracle
-from agg_rows_common import case_list, compiled_variants, expected_kernel, tuned
+from agg_rows_common import bits32, case_list, compiled_variants, expected_kernel, reduce_statement, rne, same_bits32, tuned
 from inputs import hash_matrix
 from sgl_amd import _lib, config
 from sgl_amd import device as dev
@@ -39,25 +39,8 @@ def cuda():
     return torch.device("cuda", 0)
 
 
-def rne(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(torch.bfloat16)
-
-
 def bits16(t):
     return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
-
-
-def bits32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same_bits32(got, want):
-    """32-bit patterns equal; where the expected value is a NaN the result must be a NaN (payloads are not compared)"""
-    got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
-    if got.shape != want.shape:
-        return False
-    nan = np.isnan(want)
-    return bool(np.array_equal(np.isnan(got), nan) and np.array_equal(bits32(got)[~nan], bits32(want)[~nan]))
 
 
 def call(name, *args):
@@ -121,26 +104,6 @@ def _planted(n, d, n_hops, seed):
     if n > 1:
         hops[last // 2][n - 1, d - 1] = float("nan")
     return hops
-
-
-def reduce_statement(kind, wide, w):
-    """hop_reduce_kernel's order in numpy float32: sum / mean start from 0 + X_s, mean ends with one true division, the weighted
-    sum is a rounded product, then an add, max / min propagate NaN"""
-    with np.errstate(all="ignore"):
-        if kind in ("sum", "mean"):
-            acc = np.float32(0.0) + wide[0]
-            for x in wide[1:]:
-                acc = acc + x
-            return acc / np.float32(len(wide)) if kind == "mean" else acc
-        if kind == "wsum":
-            acc = wide[0] * w[0]
-            for h in range(1, len(wide)):
-                acc = acc + wide[h] * w[h]
-            return acc
-        acc = wide[0]
-        for x in wide[1:]:
-            acc = (np.maximum if kind == "max" else np.minimum)(acc, x)
-        return acc
 
 
 # ---- 1. reduce ------------------------------------------------------------------------------------------------------------------------

@@ -12,14 +12,14 @@ import scipy.sparse as sp
 import torch
 
 import oracle
+from agg_rows_common import PARITY_TOL as TOL
+from agg_rows_common import long_row_graph, sig_mix
 from agg_rows_common import recursive_step_by_step as _recursive_step_by_step
 from inputs import hash_matrix
 from sgl_amd import _lib
 from sgl_amd import device as dev
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -41,24 +41,6 @@ def device_csr(ptr, col, val, shape, dev, **kw):
     from sgl_amd.device import DeviceCSR
     return DeviceCSR(torch.from_numpy(np.asarray(ptr, np.int64)).to(dev), torch.from_numpy(np.asarray(col, np.int32)).to(dev),
                      torch.from_numpy(np.asarray(val, np.float32)).to(dev), shape, **kw)
-
-
-def long_row_graph(n=1500, seed=5):
-    """power-law rows plus three huge rows and some empty ones (canonical CSR, not symmetric)"""
-    rng = np.random.default_rng(seed)
-    deg = np.minimum(rng.lognormal(1.2, 1.0, n).astype(np.int64), 200)
-    deg[rng.integers(0, n, 60)] = 0
-    deg[[3, 700, n - 1]] = [1400, 900, 1499]
-    rows, cols = [], []
-    for i in range(n):
-        c = np.sort(rng.choice(n, int(deg[i]), replace=False))
-        rows.append(np.full(len(c), i))
-        cols.append(c)
-    rows, cols = np.concatenate(rows), np.concatenate(cols)
-    vals = rng.uniform(-1, 1, len(rows)).astype(np.float32)
-    a = sp.csr_matrix((vals, (rows, cols)), shape=(n, n))
-    a.sort_indices()
-    return a
 
 
 D_LIST = [1, 2, 3, 4, 7, 8, 16, 32, 47, 64, 100, 128, 147, 256, 500]
@@ -2208,12 +2190,6 @@ def test_label_reuse_loop_matches_reference_task(goldens, cuda, delta, monkeypat
 
 def test_column_signature_matches_its_definition(cuda):
     """sgl_col_signature_f32 against a numpy statement of its definition: sig[c] = sum_r mix(bits(X[r, c]), r) mod 2^64"""
-    def mix(bits, r):
-        with np.errstate(over="ignore"):
-            h = (bits.astype(np.uint64) ^ (r.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15))) * np.uint64(0xBF58476D1CE4E5B9)
-            h ^= h >> np.uint64(31)
-            h *= np.uint64(0x94D049BB133111EB)
-            return h ^ (h >> np.uint64(29))
     for n, d in ((1, 4), (7, 3), (1000, 147), (4097, 100), (300, 1030), (513, 64)):
         xp = dev.alloc_rows(n, d, cuda)
         xp.copy_(torch.from_numpy(hash_matrix(n, d, seed=n + d)).to(cuda))
@@ -2222,7 +2198,7 @@ def test_column_signature_matches_its_definition(cuda):
         assert sig is not None and sig.numel() == dw
         full = dev.padded_parent(xp)[:, :dw].cpu().numpy()
         with np.errstate(over="ignore"):
-            want = mix(full.view(np.uint32), np.arange(n, dtype=np.uint64)[:, None]).sum(axis=0, dtype=np.uint64)
+            want = sig_mix(full.view(np.uint32), np.arange(n, dtype=np.uint64)[:, None]).sum(axis=0, dtype=np.uint64)
         assert np.array_equal(sig.cpu().numpy().view(np.uint64), want), (n, d)
         # one element moved -> exactly its column's signature moves; two rows swapped -> every column that differs between them
         if n > 1:
