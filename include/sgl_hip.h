@@ -29,6 +29,8 @@
  *   sgl_gather_rows_f32        the `feat[idx]` row gather of BaseSGAPModel.forward (sgl/models/base_model.py:58,60).
  *   sgl_edge_dot_f32           `torch.mm(Z, Z.t())[e0, e1]`, the edge scores of link prediction (sgl/tasks/link_prediction.py:282-283,
  *                              sgl/tasks/utils.py:281-285), without the N x N matrix.
+ *   sgl_edge_loss_grad_f32     loss and gradient of edge_predict_train (sgl/tasks/utils.py:280-295: sigmoid, loss_fn, backward) on an edge
+ *                              list grouped by endpoint once: scores, coefficients and dZ in one pass, no sort, no atomics.
  *   sgl_csr_find,              the edge set and the random negative pairs of mask_test_edges (sgl/tasks/utils.py:148-259): is (i, j)
  *   sgl_edge_candidates        stored, as a search inside one CSR row; a seeded candidate stream with each pair's verdict.
  *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
@@ -515,6 +517,36 @@ int sgl_scatter_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const in
  * than one launch covers -> SGL_ERR_UNSUPPORTED (split the list: edges are independent). */
 int sgl_edge_dot_f32(const float *d_a, int64_t lda, int64_t n_a, const float *d_b, int64_t ldb, int64_t n_b,
                      const int64_t *d_edges, int64_t n_edges, int64_t d, float *d_out, void *stream);
+
+/* One training step of link prediction on a PREPARED edge list: loss, per-edge coefficient and dZ in one pass -- what
+ * `sim = torch.mm(Z, Z.t()); pred = torch.sigmoid(sim[e0, e1]); loss = loss_fn(pred, labels); loss.backward()` computes
+ * (edge_predict_train, sgl/tasks/utils.py:280-295; default loss_fn F.binary_cross_entropy_with_logits, sgl/tasks/link_prediction.py:15)
+ * without the N x N matrix, without atomics and without a per-step sort.  The list is prepared once (sgl_amd.tricks.EdgePlan):
+ *   d_inc_other [n_inc] int32, d_inc_edge [n_inc] int64   the incidences grouped by node, n_inc = 2 n_edges: entry k of node i's range
+ *                        says "edge e joins i and d_inc_other[k]"; d_inc_edge[k] = e when i is u_e (the PRIMARY entry), ~e when i is v_e.
+ *                        Inside a node's range the entries ascend by e, a self pair has both entries there, primary first.
+ *   d_pieces [n_pieces, 4] int64, 32-byte aligned   (row, begin, end, dest): entries [begin, end) of d_inc_* belong to `row`; dest < 0:
+ *                        the piece is the whole row and writes d_dz[row]; dest >= 0: it writes row dest of d_partial.  EVERY row has at
+ *                        least one piece (a node without incidences an empty one), so d_dz is overwritten whole: exact zeros there.
+ *   d_fold [n_fold, 3] int64   (row, first, count): d_dz[row] = d_partial[first] + ... + d_partial[first + count - 1], added in that order
+ *                        after the pieces of THIS call.  A caller that splits the piece table passes n_fold = 0 until its last call.
+ * Per entry (i, j, e): s = <z_i, z_j>, summed exactly as sgl_edge_dot_f32 sums it for the same (d, pitch, alignment) -- the same bits
+ * from either endpoint and the bits of that entry point.  mode, with y = d_labels[e] and w one scalar (1 / n_edges for the mean):
+ *   0 SIGMOID_LOGITS  the reference as written, sigmoid and THEN the with-logits loss: p = sigma(s), L = (1 - y) p + log1p(exp(-p)),
+ *                     c = w (sigma(p) - y) p (1 - p)
+ *   1 LOGITS          L = max(s, 0) - s y + log1p(exp(-|s|)), c = w (sigma(s) - y)
+ *   2 GIVEN           c = d_given[e]; no dot product; d_score, d_coef and d_piece_loss must be NULL
+ * L and c are finite for every finite s.  d_dz[i] = sum over i's entries, in entry order, of c z_j (fmaf).  Optional d_score [n_edges]
+ * and d_coef [n_edges] are written by the primary entry; d_piece_loss [n_pieces] = the float32 sum of L over the piece's primary
+ * entries in entry order (the caller adds them up in float64 and scales by w).  Indices are NOT checked here: the plan validated
+ * them.  Columns d .. pitch of z are never used, nothing beyond column d of its last row is read or of any output row written.
+ * n_pieces = 0 and n_fold = 0: nothing is done; d = 0: zeros in d_score / d_coef / d_piece_loss, no kernel; more pieces than one
+ * launch covers -> SGL_ERR_UNSUPPORTED (split the table: pieces are independent). */
+int sgl_edge_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, int64_t d, const int64_t *d_pieces, int64_t n_pieces,
+                           const int32_t *d_inc_other, const int64_t *d_inc_edge, int64_t n_inc, const float *d_labels,
+                           const float *d_given, int64_t n_edges, int mode, float w, float *d_dz, int64_t lddz,
+                           float *d_partial, int64_t ldp, int64_t n_partial, const int64_t *d_fold, int64_t n_fold,
+                           float *d_score, float *d_coef, float *d_piece_loss, void *stream);
 
 /* Where a list of pairs is stored in a canonical CSR (columns sorted and unique inside each row -- what sgl_coo_to_csr produces; not
  * checked): pos[q] = the p in [rowptr[u_q], rowptr[u_q + 1]) with col[p] == v_q, or -1 when (u_q, v_q) is not stored.  The membership

@@ -1730,6 +1730,112 @@ def _split_calls(name, n_items, one):
         lo += m
 
 
+# ---- the prepared edge list of the link-prediction training step (sgl_edge_loss_grad_f32; tricks.link_prediction.EdgePlan) ------------
+EDGE_LOSS_MODES = {"sigmoid": 0, "none": 1, "given": 2}      # SIGMOID_LOGITS (the reference as written), LOGITS, GIVEN
+EDGE_LOSS_MAX_PIECE = 128             # incidences per piece: the fastest of 128 ... 4096, uncut (profiles/edge_loss.log); max_piece=None means this
+
+
+def edge_incidence(u, v, n):
+    """(inc_ptr int64 [n + 1], inc_other int32 [2 E], inc_edge int64 [2 E]): the edges (u_e, v_e) grouped by node, on the device u
+    and v are on (CPU included; index arithmetic in torch only).  Entry k of node i's range [inc_ptr[i], inc_ptr[i + 1]) joins i and
+    inc_other[k] through edge e: inc_edge[k] = e when i is u_e (the primary entry), ~e when i is v_e.  Inside a range the entries
+    ascend by e; a self pair (i, i) has both entries in i's range, primary first; duplicates stay separate.  u, v: int64 [E], every
+    index in [0, n)."""
+    e = int(u.numel())
+    rows = torch.stack((u, v), dim=1).reshape(-1)                                   # entry 2 e: u_e, entry 2 e + 1: v_e
+    rows, order = torch.sort(rows, stable=True)                                     # stable: ascending e, primary first
+    ids = torch.arange(e, dtype=torch.int64, device=u.device)
+    inc_edge = torch.stack((ids, ~ids), dim=1).reshape(-1)[order]
+    inc_other = torch.stack((v, u), dim=1).reshape(-1)[order].to(torch.int32)
+    inc_ptr = torch.zeros(n + 1, dtype=torch.int64, device=u.device)
+    torch.cumsum(torch.bincount(rows, minlength=n), 0, out=inc_ptr[1:])
+    return inc_ptr, inc_other.contiguous(), inc_edge.contiguous()
+
+
+def edge_pieces(inc_ptr, max_piece):
+    """(pieces int64 [P, 4], fold int64 [F, 3], n_partial) for the ranges of inc_ptr cut into pieces of at most max_piece entries.
+    pieces[p] = (row, begin, end, dest), in row order and inside a row in entry order: dest = -1 for a row that is one piece (it
+    writes dZ[row]; a row without entries has one empty piece), else the row of the partial buffer the piece writes.  fold[f] =
+    (row, first, count) for every cut row: its partial rows are first .. first + count - 1, in piece order."""
+    n = int(inc_ptr.numel()) - 1
+    dv = inc_ptr.device
+    max_piece = int(max_piece)
+    if max_piece < 1:
+        raise ValueError("max_piece must be at least 1")
+    deg = inc_ptr[1:] - inc_ptr[:-1]
+    per_row = torch.clamp((deg + (max_piece - 1)) // max_piece, min=1)
+    first_piece = torch.cumsum(per_row, 0) - per_row
+    row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dv), per_row)
+    n_pieces = int(row.numel())
+    begin = inc_ptr[:-1][row] + (torch.arange(n_pieces, dtype=torch.int64, device=dv) - first_piece[row]) * max_piece
+    end = torch.minimum(begin + max_piece, inc_ptr[1:][row])
+    cut = per_row[row] > 1
+    dest = torch.where(cut, torch.cumsum(cut.to(torch.int64), 0) - 1, torch.full_like(row, -1))
+    pieces = torch.stack((row, begin, end, dest), dim=1).contiguous()
+    cut_rows = torch.nonzero(per_row > 1).reshape(-1)
+    count = per_row[cut_rows]
+    fold = torch.stack((cut_rows, torch.cumsum(count, 0) - count, count), dim=1).contiguous()
+    return pieces, fold, int(count.sum()) if cut_rows.numel() else 0
+
+
+def edge_loss_grad(z, plan, mode, w=1.0, given=None, dz=None, score=None, coef=None):
+    """One launch of sgl_edge_loss_grad_f32 over the prepared edge list `plan` (anything with EdgePlan's tables): dz [n, d] is
+    OVERWRITTEN with sum over the edges at i of c_e z_j -- a node without edges gets exact zeros -- and the piece losses land in
+    plan.piece_loss.  mode: a key of EDGE_LOSS_MODES; "given": c_e = given[e], nothing else is computed.  score / coef: optional
+    float32 [E] outputs (the logits of dev.edge_dot, bit for bit, and the coefficients).  Returns dz (allocated when None).  Nothing
+    here synchronises; a piece table longer than one launch covers is split (pieces are independent, the fold runs last)."""
+    _no_bf16("edge_loss_grad", z)
+    _check_mat(z, "z")
+    n, d = z.shape
+    if n != plan.n:
+        raise ValueError(f"edge_loss_grad: z has {n} rows, the plan was built for {plan.n} nodes")
+    if plan.pieces.device != z.device:
+        raise ValueError("edge_loss_grad: the plan and z must live on one device")
+    m = EDGE_LOSS_MODES[mode]
+    n_e = plan.n_edges
+
+    def vector(t, name):
+        if t is None:
+            return None
+        if not (torch.is_tensor(t) and t.device == z.device and t.dtype == torch.float32 and t.dim() == 1 and t.numel() == n_e
+                and t.is_contiguous()):
+            raise ValueError(f"edge_loss_grad: `{name}` must be a contiguous float32 [E] tensor on z's device")
+        return t
+
+    given, score, coef = vector(given, "given"), vector(score, "score"), vector(coef, "coef")
+    if (mode == "given") != (given is not None) or (mode == "given" and (score is not None or coef is not None)):
+        raise ValueError("edge_loss_grad: `given` goes with mode 'given' alone, which has no score or coef output")
+    if dz is None:
+        dz = alloc_rows(n, d, z.device)
+    else:
+        _check_mat(dz, "dz")
+        if dz.shape != z.shape or dz.device != z.device:
+            raise ValueError("edge_loss_grad: `dz` must have z's shape and device")
+    if n_e == 0 or d == 0:                              # no edges: dZ = 0 and no loss; no columns: every score is an empty sum
+        dz.zero_()
+        plan.piece_loss.zero_()
+        for t in (score, coef):
+            if t is not None:
+                t.zero_()
+        return dz
+    partial = plan.partial_rows(d)
+    pieces, fold = plan.pieces, plan.fold
+    n_p, n_f = pieces.shape[0], fold.shape[0]
+    loss = None if mode == "given" else plan.piece_loss
+
+    def one(lo, cnt):
+        last = lo + cnt == n_p
+        return _call(z.device, "sgl_edge_loss_grad_f32", ptr(z), _ld(z), n, d, c_void_p(pieces.data_ptr() + 32 * lo), cnt,
+                     ptr(plan.inc_other), ptr(plan.inc_edge), 2 * n_e, ptr(plan.labels), _opt_ptr(given), n_e, m, float(w), ptr(dz),
+                     _ld(dz), _opt_ptr(partial), _ld(partial) if partial is not None else 0, plan.n_partial,
+                     ptr(fold) if (last and n_f) else None, n_f if last else 0, _opt_ptr(score), _opt_ptr(coef),
+                     c_void_p(loss.data_ptr() + 4 * lo) if loss is not None else None, raw=True)
+
+    _split_calls("sgl_edge_loss_grad_f32", n_p, one)
+    _wrote(dz, score, coef, loss)
+    return dz
+
+
 def _csr_arrays(adj, who):
     """(rowptr, col) of a device CSR (DeviceAdjacency or anything with its fields) as the two search entries take them; a matrix
     without entries gets one unread column slot, so that the pointer is never NULL"""

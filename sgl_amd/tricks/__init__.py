@@ -7,7 +7,8 @@ loop around `model.preprocess` (reference: sgl/tasks/node_cl
 from .clustering import KMeansResult, NodeClusteringResult, clustering_scores, kmeans, nafs_node_clustering
 from .correct_and_smooth import CorrectAndSmooth
 from .label_reuse import add_labels, label_reuse, predict_all
-from .link_prediction import (EdgeSplit, LinkPredictionResult, binary_ranking_metrics, edge_predict_score, edge_scores, has_edges,
+from .link_prediction import (EdgePlan, EdgeSplit, GAELinkPredictionResult, LinkPredictionResult, binary_ranking_metrics, edge_bce_loss,
+                              edge_predict_eval, edge_predict_score, edge_predict_train, edge_scores, gae_link_prediction, has_edges,
                               mask_test_edges, nafs_link_prediction)
 from .nafs_features import nafs_ensemble_features, nafs_ensemble_sweep
 from .utils import label_propagation
@@ -15,4 +16,5 @@ from .utils import label_propagation
 __all__ = ["CorrectAndSmooth", "label_propagation", "nafs_ensemble_features", "nafs_ensemble_sweep", "add_labels", "label_reuse", "predict_all",
            "edge_scores", "binary_ranking_metrics", "edge_predict_score", "nafs_link_prediction", "LinkPredictionResult",
            "has_edges", "mask_test_edges", "EdgeSplit",
+           "EdgePlan", "edge_bce_loss", "edge_predict_train", "edge_predict_eval", "gae_link_prediction", "GAELinkPredictionResult",
            "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult"]

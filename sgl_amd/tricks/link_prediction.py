@@ -22,7 +22,8 @@ from .. import device as dev
 from .nafs_features import nafs_ensemble_sweep
 
 __all__ = ["edge_scores", "binary_ranking_metrics", "edge_predict_score", "nafs_link_prediction", "LinkPredictionResult",
-           "has_edges", "mask_test_edges", "EdgeSplit"]
+           "has_edges", "mask_test_edges", "EdgeSplit",
+           "EdgePlan", "edge_bce_loss", "edge_predict_train", "edge_predict_eval", "gae_link_prediction", "GAELinkPredictionResult"]
 
 
 def _grad_spmm(rows, cols, vals, n_rows, n_cols, x):
@@ -76,7 +77,20 @@ def edge_scores(z, edges, z2=None, sigmoid=False):
     indices are validated (IndexError); in a device tensor a pair outside the matrices scores NaN.
     sigmoid=True applies torch.sigmoid_ to the logits in place (what the reference's torch.sigmoid makes of the same logits).
     When z (or z2) requires grad the scores carry it: the backward is one SpMM per gradient with the matrix of the (u, v, g)
-    triplets -- no atomics, two runs are bit-equal (a device index outside the matrices raises there)."""
+    triplets -- no atomics, two runs are bit-equal (a device index outside the matrices raises there).
+    edges may also be an EdgePlan (z2 must then be z): the same forward, and a backward that is ONE launch over the prepared list
+    (sgl_edge_loss_grad_f32 with the upstream gradient as the coefficients) -- no sort and no new CSR per step."""
+    if isinstance(edges, EdgePlan):
+        if not (z2 is None or z2 is z):
+            raise ValueError("edge_scores: an EdgePlan scores one matrix against itself (z2 must be z)")
+        if torch.is_grad_enabled() and z.requires_grad:
+            dev._no_bf16("edge_scores", z)
+            dev._check_mat(z, "z")
+            edges._check_z(z, "edge_scores")
+            out = _EdgeDotPlanned.apply(z, edges)
+            return torch.sigmoid(out) if sigmoid else out
+        edges._check_z(z, "edge_scores")
+        edges = edges.edges
     same = z2 is None or z2 is z
     b = z if same else z2
     if torch.is_grad_enabled() and (z.requires_grad or b.requires_grad):
@@ -370,3 +384,337 @@ def mask_test_edges(adj, seed=0, device="cuda", negatives=_NEGATIVE_SETS, round_
             false[s] = drawn[lo:lo + sizes[s]]
             lo += sizes[s]
     return EdgeSplit(adj_train, train_edges, false["train"], val_edges, false["val"], test_edges, false["test"])
+
+
+# ---- the trainable task: LinkPredictionGAE of the reference (sgl/tasks/link_prediction.py:14-157) ---------------------------------------
+class EdgePlan:
+    """An edge list with labels, prepared ONCE for every training step on it (the edge list of a training run never changes):
+
+        plan = EdgePlan(edges, labels, n)            # or EdgePlan.from_pos_neg(pos, neg, n): cat(pos, neg), labels 1 .. 1, 0 .. 0
+        loss = edge_bce_loss(z, plan)                # every epoch: nothing sorted, no new CSR, no atomics (paths: see edge_bce_loss)
+
+    edges: [E, 2] integers or a pair (u, v), host or device; labels: [E] float32 (soft labels are allowed); n: the number of nodes.
+    Negative indices are wrapped HERE and an index outside [-n, n) raises IndexError here, for device tensors too (one min / max
+    reduction on the setup path): the kernel has no bad-index path.  max_piece: incidences per piece (None: device.EDGE_LOSS_MAX_PIECE).
+    device: where the tables live; "cpu" builds the same tables with the same torch ops (index arithmetic only).
+
+    Tables (device.edge_incidence, device.edge_pieces): inc_ptr int64 [n + 1], inc_other int32 [2 E], inc_edge int64 [2 E] -- the
+    incidences grouped by node, ascending by edge position inside a node, a self pair's two entries both there, primary first,
+    duplicates separate -- and pieces [P, 4] / fold [F, 3]: rows cut into pieces of at most max_piece incidences; a row that is one
+    piece writes dZ[row], the pieces of a cut row write rows of a partial buffer that are added in piece order, without atomics.
+    Also kept: edges (wrapped, int64 [E, 2]), labels, and the buffers of a step -- piece_loss, coef, score, and per width the partial
+    rows and the fused path's dZ -- allocated once.  They serve ONE step at a time: a backward after another forward on the same
+    plan raises.  (The default, unfused path of edge_bce_loss hands autograd a dZ of its own every step: see there.)"""
+
+    def __init__(self, edges, labels, n, max_piece=None, device="cuda"):
+        device = _indexed(device)
+        n = int(n)
+        if n < 0 or n >= 2 ** 31:
+            raise ValueError("EdgePlan: n must be in [0, 2^31)")
+        e = _plan_edges(edges, device)
+        if e.shape[0]:
+            lo, hi = int(e.min()), int(e.max())
+            if lo < -n or hi >= n:
+                raise IndexError("index out of range in edge list")
+        e = _wrapped(e, n).contiguous()
+        labels = torch.as_tensor(labels)
+        if labels.dim() != 1 or labels.numel() != e.shape[0]:
+            raise ValueError(f"EdgePlan: labels must be [E] = [{e.shape[0]}], got {tuple(labels.shape)}")
+        self.n, self.n_edges = n, int(e.shape[0])
+        self.edges = e
+        self.labels = labels.to(device=device, dtype=torch.float32).contiguous()
+        self.max_piece = dev.EDGE_LOSS_MAX_PIECE if max_piece is None else int(max_piece)
+        self.inc_ptr, self.inc_other, self.inc_edge = dev.edge_incidence(e[:, 0], e[:, 1], n)
+        self.pieces, self.fold, self.n_partial = dev.edge_pieces(self.inc_ptr, self.max_piece)
+        self.n_pieces = int(self.pieces.shape[0])
+        self.piece_loss = torch.zeros(self.n_pieces, dtype=torch.float32, device=device)
+        self.coef = torch.zeros(self.n_edges, dtype=torch.float32, device=device)
+        self.score = torch.zeros(self.n_edges, dtype=torch.float32, device=device)
+        self.device = device
+        self._partial, self._dz, self.step = {}, {}, 0
+
+    @classmethod
+    def from_pos_neg(cls, pos_edges, neg_edges, n, max_piece=None, device="cuda"):
+        """the reference's layout (sgl/tasks/utils.py:282-283): torch.cat((pos, neg)) with labels ones then zeros"""
+        device = _indexed(device)
+        pos, neg = _plan_edges(pos_edges, device), _plan_edges(neg_edges, device)
+        labels = torch.cat((torch.ones(len(pos), device=device), torch.zeros(len(neg), device=device)))
+        return cls(torch.cat((pos, neg)), labels, n, max_piece=max_piece, device=device)
+
+    def partial_rows(self, d):
+        """the [n_partial, d] buffer the pieces of cut rows write (None when no row is cut), allocated once per width"""
+        if self.n_partial == 0:
+            return None
+        if d not in self._partial:
+            self._partial[d] = dev.alloc_rows(self.n_partial, d, self.device)
+        return self._partial[d]
+
+    def dz_rows(self, d):
+        if d not in self._dz:
+            self._dz[d] = dev.alloc_rows(self.n, d, self.device)
+        return self._dz[d]
+
+    def _check_z(self, z, who):
+        if z.dim() != 2 or z.shape[0] != self.n:
+            raise ValueError(f"{who}: z must be [{self.n}, d] (the plan's node count), got {tuple(z.shape)}")
+        if z.device != self.device:
+            raise ValueError(f"{who}: z is on {z.device}, the plan on {self.device}")
+
+
+def _indexed(device):
+    """torch.device(device), "cuda" as the current device with its index (what the tensors on it report)"""
+    device = torch.device(device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
+
+
+def _plan_edges(edges, device):
+    """an edge list of any kind as int64 [E, 2] on `device`, indices as given (EdgePlan validates and wraps them itself)"""
+    if isinstance(edges, (tuple, list)) and len(edges) == 2 and not (torch.is_tensor(edges) or isinstance(edges, np.ndarray)):
+        u, v = (torch.as_tensor(np.asarray(t) if not torch.is_tensor(t) else t).reshape(-1) for t in edges)
+        if u.shape != v.shape:
+            raise ValueError("EdgePlan: u and v must be of one length")
+        edges = torch.stack((u.to(device=device, dtype=torch.int64), v.to(device=device, dtype=torch.int64)), dim=1)
+    t = edges if torch.is_tensor(edges) else torch.from_numpy(np.asarray(edges))
+    if t.numel() == 0:
+        t = t.reshape(0, 2)
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError("EdgePlan: edges must be [E, 2] (or a pair (u, v))")
+    if t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise TypeError("EdgePlan: edges must be integers")
+    return t.to(device=device, dtype=torch.int64)
+
+
+class _EdgeDotPlanned(torch.autograd.Function):
+    """edge scores of a prepared list: the forward of _EdgeDot, the backward one GIVEN-mode launch"""
+
+    @staticmethod
+    def forward(ctx, z, plan):
+        ctx.plan = plan
+        ctx.save_for_backward(z)
+        return dev.edge_dot(z, z, plan.edges)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        z, = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return dev.edge_loss_grad(z, ctx.plan, "given", given=g.contiguous().to(torch.float32)), None
+
+
+def _bce_terms(s, y, activation):
+    """(L, c) per edge in torch, c = dL / ds WITHOUT the weight w: the formulas of csrc/sgl_edge_loss.hip, formed from e = exp(-|s|)
+    like there -- not by autograd through max / abs, whose subgradients at s = 0 are not sigma(s) - y"""
+    e = torch.exp(-s.abs())
+    r = 1.0 / (1.0 + e)
+    sig = torch.where(s >= 0, r, e * r)                                              # sigma(s)
+    if activation == "sigmoid":
+        ep = torch.exp(-sig)
+        return (1 - y) * sig + torch.log1p(ep), (1.0 / (1.0 + ep) - y) * (e * r * r)
+    return torch.clamp(s, min=0) - s * y + torch.log1p(e), torch.where(s >= 0, (1 - y) - e * r, sig - y)
+
+
+def _loss_of(scores, plan, activation, w):
+    return (_bce_terms(scores, plan.labels, activation)[0].double().sum() * w).to(torch.float32)
+
+
+class _ZeroGrad(torch.autograd.Function):
+    """a constant that hangs on z in the graph: its gradient is exact zeros whatever z holds (E = 0, d = 0)"""
+
+    @staticmethod
+    def forward(ctx, z, value):
+        ctx.shape = z.shape
+        return value.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.new_zeros(ctx.shape), None
+
+
+class _EdgeBCEUnfused(torch.autograd.Function):
+    """plan reuse without fusing: device.edge_dot into the plan's score buffer, loss and coefficients by _bce_terms on E floats (the
+    coefficients into the plan's coef buffer), and in the backward ONE GIVEN-mode launch with g x coef"""
+
+    @staticmethod
+    def forward(ctx, z, plan, activation, w):
+        plan.step += 1
+        ctx.plan, ctx.step = plan, plan.step
+        ctx.save_for_backward(z)
+        dev.edge_dot(z, z, plan.edges, out=plan.score)
+        terms, coef = _bce_terms(plan.score, plan.labels, activation)
+        torch.mul(coef, w, out=plan.coef)
+        ctx.mark_non_differentiable(plan.score)
+        return (terms.double().sum() * w).to(torch.float32), plan.score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gs):
+        if ctx.plan.step != ctx.step:
+            raise RuntimeError("edge_bce_loss: the plan ran another step since this forward; its buffers hold that step's coefficients "
+                               "(one EdgePlan serves one step at a time)")
+        z, = ctx.saved_tensors
+        return dev.edge_loss_grad(z, ctx.plan, "given", given=ctx.plan.coef * g), None, None, None
+
+
+class _EdgeBCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, plan, activation, w, want_scores):
+        plan.step += 1
+        ctx.plan, ctx.step, ctx.d = plan, plan.step, z.shape[1]
+        # the logits are written only when asked for (E scattered 4-byte stores), the coefficients never: they live in registers
+        dev.edge_loss_grad(z, plan, activation, w=w, dz=plan.dz_rows(z.shape[1]), score=plan.score if want_scores else None)
+        loss = (plan.piece_loss.double().sum() * w).to(torch.float32)
+        if not want_scores:
+            return loss, None
+        ctx.mark_non_differentiable(plan.score)
+        return loss, plan.score
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gs):
+        if ctx.plan.step != ctx.step:
+            raise RuntimeError("edge_bce_loss: the plan ran another step since this forward; its buffers hold that step's gradient "
+                               "(one EdgePlan serves one step at a time)")
+        return ctx.plan.dz_rows(ctx.d) * g, None, None, None, None
+
+
+# edge_bce_loss's default path.  Measured interleaved at the products shape, d = 100 (profiles/edge_loss.log): the fused launch 4.07 ms,
+# plan reuse without fusing 3.48 ms per step -- the fused kernel stays, tested and selectable, and is not the default (DESIGN.md K11)
+FUSED_EDGE_LOSS = False
+
+
+def edge_bce_loss(z, plan, activation="sigmoid", reduction="mean", return_scores=False, fused=None):
+    """The training loss of the reference's link prediction on a prepared edge list, a float32 scalar on the device that carries
+    the gradient to z -- `loss_fn(torch.sigmoid(torch.mm(z, z.t())[e0, e1]), labels)` of edge_predict_train (sgl/tasks/utils.py:281-293)
+    without the N x N matrix.  With s_e = <z[u_e], z[v_e]> and y_e the plan's labels, per edge:
+      activation="sigmoid"  the reference AS WRITTEN: its default loss_fn is binary_cross_entropy_with_logits, applied to the sigmoid
+                            of the logits -- p = sigmoid(s), L = (1 - y) p + log1p(exp(-p))
+      activation="none"     the with-logits loss on the logits themselves: L = max(s, 0) - s y + log1p(exp(-|s|))
+    reduction "mean" (w = 1 / E) or "sum" (w = 1); the loss is w times the float64 sum of the pieces' float32 sums.
+    With grad enabled and z.requires_grad there are two paths over the plan, neither of which sorts anything or uses atomics (two
+    runs are bit-equal):
+      fused=True   ONE launch (sgl_edge_loss_grad_f32) computes scores, loss and dZ into the plan's buffers, and the backward returns
+                   the upstream gradient times that dZ; nothing but that product is allocated per step
+      fused=False  plan reuse WITHOUT fusing, THE DEFAULT: device.edge_dot into the plan's score buffer, loss and coefficients by the
+                   kernel's formulas in torch on E floats (a few E-sized temporaries), and in the backward one GIVEN-mode launch
+                   over the plan with g x coefficients; that launch writes a NEW [n, d] dZ every step, which autograd owns
+    fused=None takes FUSED_EDGE_LOSS, the faster of the two in the interleaved measurement at d = 100.  Without
+    grad the scores come from device.edge_dot and the formulas run in torch on E floats.  All paths see the same logits bit for
+    bit and use the same formulas for loss and coefficient (c = w (sigma(s) - y) at s = 0 too: nothing goes through the
+    subgradients of max or abs); the torch evaluation may differ from the kernel's in the last bits (torch's exp / log1p are not
+    the device library's, and it sums the E terms in another order).
+    return_scores=True: (loss, logits [E]) -- the logits are the plan's buffer, valid until the next step.  bf16 z is refused."""
+    if activation not in ("sigmoid", "none"):
+        raise ValueError("edge_bce_loss: activation must be 'sigmoid' or 'none'")
+    if reduction not in ("mean", "sum"):
+        raise ValueError("edge_bce_loss: reduction must be 'mean' or 'sum'")
+    if not isinstance(plan, EdgePlan):
+        raise TypeError("edge_bce_loss: plan must be an EdgePlan")
+    dev._no_bf16("edge_bce_loss", z)
+    dev._check_mat(z, "z")
+    plan._check_z(z, "edge_bce_loss")
+    w = 1.0 / plan.n_edges if (reduction == "mean" and plan.n_edges) else 1.0
+    if torch.is_grad_enabled() and z.requires_grad:
+        if plan.n_edges == 0 or z.shape[1] == 0:        # nothing to launch: the torch formulas on E (or no) floats carry a zero gradient
+            with torch.no_grad():
+                scores = edge_scores(z, plan.edges)
+                loss = _loss_of(scores, plan, activation, w)
+            loss = _ZeroGrad.apply(z, loss)
+        elif FUSED_EDGE_LOSS if fused is None else fused:
+            loss, scores = _EdgeBCE.apply(z, plan, activation, w, bool(return_scores))
+        else:
+            loss, scores = _EdgeBCEUnfused.apply(z, plan, activation, w)
+    else:
+        with torch.no_grad():
+            scores = edge_scores(z, plan.edges)
+            loss = _loss_of(scores, plan, activation, w)
+    return (loss, scores) if return_scores else loss
+
+
+def _model_output(model, nodes, device):
+    return model.model_forward(nodes, device) if hasattr(model, "model_forward") else model(nodes)
+
+
+def edge_predict_train(model, train_nodes, plan, optimizer, threshold=0.5, activation="sigmoid"):
+    """edge_predict_train of the reference (sgl/tasks/utils.py:274-303), full batch: one optimizer step on the plan's edges and
+    (loss, roc_auc, avg_prec) of the training edges.  As there, the two metrics are taken on the THRESHOLDED predictions
+    `sigmoid(s) > threshold` (0 / 1 scores: binary_ranking_metrics is tie-aware, so they are sklearn's values).  optimizer=None is
+    the reference's with_params=False: the loss and metrics alone."""
+    device = plan.device
+    if optimizer is not None:
+        model.train()
+        optimizer.zero_grad()
+        z = _model_output(model, train_nodes, device)
+        loss, scores = edge_bce_loss(z, plan, activation=activation, return_scores=True)
+        loss.backward()
+        optimizer.step()
+    else:
+        with torch.no_grad():
+            z = _model_output(model, train_nodes, device)
+            loss, scores = edge_bce_loss(z, plan, activation=activation, return_scores=True)
+    with torch.no_grad():
+        pred = (torch.sigmoid(scores) > threshold).to(torch.float64)
+        roc_auc, avg_prec = binary_ranking_metrics(pred, plan.labels)
+    return float(loss.detach()), roc_auc, avg_prec
+
+
+@torch.no_grad()
+def edge_predict_eval(model, train_nodes, val_pos, val_neg, test_pos, test_neg, device="cuda"):
+    """edge_predict_eval of the reference (sgl/tasks/utils.py:306-315): (roc_auc_val, avg_prec_val, roc_auc_test, avg_prec_test) of
+    the model's output in eval mode, on the sigmoid scores as edge_predict_score ranks them"""
+    model.eval()
+    z = _model_output(model, train_nodes, _indexed(device))
+    return edge_predict_score(z, val_pos, val_neg) + edge_predict_score(z, test_pos, test_neg)
+
+
+GAELinkPredictionResult = namedtuple("GAELinkPredictionResult", ["test_roc_auc", "test_avg_prec", "history", "split"])
+GAELinkPredictionResult.__doc__ = """gae_link_prediction's result: the pair LinkPredictionGAE keeps (the test scores at the best validation
+scores), history = one dict per epoch (loss, roc_auc_train, avg_prec_train, roc_auc_val, avg_prec_val, roc_auc_test, avg_prec_test)
+followed by the post-processing entry (epoch = "post"), and the EdgeSplit that was used"""
+
+
+def gae_link_prediction(model, adj_or_split, x, epochs, lr, weight_decay, seed=42, threshold=0.5, activation="sigmoid", device="cuda"):
+    """LinkPredictionGAE of the reference (sgl/tasks/link_prediction.py:14-157: __init__ and _execute), full batch, on the device.
+    adj_or_split: an adjacency (scipy or DeviceAdjacency; split by mask_test_edges(adj, seed)) or an EdgeSplit.  model: a module with
+    preprocess(adj_train, x) and model_forward(nodes, device) -- and optionally postprocess(adj_train, z) -- like the reference's
+    BaseSGAPModel.  Adam(lr, weight_decay) when the model has parameters; per epoch edge_predict_train on the training edges and
+    their negatives (ONE EdgePlan for all epochs) and edge_predict_eval; the test scores are kept where the validation scores are
+    strictly the best so far (lines 120-134, bests start at 0).  The post-processing step keeps its quirk: the test edges are scored
+    against ALL negative edges (train, val and test; line 156).  The mini-batch mode of the reference is not offered: it bounds
+    nothing there (it still forms N x N), and per-edge scores make the full batch cheap."""
+    device = _indexed(device)
+    split = adj_or_split if isinstance(adj_or_split, EdgeSplit) else mask_test_edges(adj_or_split, seed=seed, device=device)
+    n = int(x.shape[0])
+    torch.manual_seed(seed)
+    model.preprocess(split.adj_train, x)
+    model = model.to(device)
+    params = list(model.parameters())
+    optimizer = torch.optim.Adam(params, lr=lr, weight_decay=weight_decay) if params else None
+    nodes = torch.arange(n, dtype=torch.int64, device=device)
+    plan = EdgePlan.from_pos_neg(split.train_edges, split.train_edges_false, n, device=device)
+    best_val = [0., 0.]
+    best_test = [0., 0.]
+    history = []
+
+    def keep(roc_auc_val, avg_prec_val, roc_auc_test, avg_prec_test):
+        if roc_auc_val > best_val[0]:
+            best_val[0], best_test[0] = roc_auc_val, roc_auc_test
+        if avg_prec_val > best_val[1]:
+            best_val[1], best_test[1] = avg_prec_val, avg_prec_test
+
+    for epoch in range(epochs):
+        loss, roc_auc_train, avg_prec_train = edge_predict_train(model, nodes, plan, optimizer, threshold, activation)
+        scores = edge_predict_eval(model, nodes, split.val_edges, split.val_edges_false, split.test_edges, split.test_edges_false, device)
+        history.append(dict(epoch=epoch, loss=loss, roc_auc_train=roc_auc_train, avg_prec_train=avg_prec_train, roc_auc_val=scores[0],
+                            avg_prec_val=scores[1], roc_auc_test=scores[2], avg_prec_test=scores[3]))
+        keep(*scores)
+    with torch.no_grad():                              # _postprocess (lines 142-157)
+        model.eval()
+        z = _model_output(model, nodes, device)
+        if hasattr(model, "postprocess"):
+            z = model.postprocess(split.adj_train, z)
+        all_neg = torch.cat((split.train_edges_false, split.val_edges_false, split.test_edges_false))
+        scores = edge_predict_score(z, split.val_edges, split.val_edges_false) + edge_predict_score(z, split.test_edges, all_neg)
+    history.append(dict(epoch="post", roc_auc_val=scores[0], avg_prec_val=scores[1], roc_auc_test=scores[2], avg_prec_test=scores[3]))
+    keep(*scores)
+    return GAELinkPredictionResult(best_test[0], best_test[1], history, split)
