@@ -34,6 +34,7 @@
  *   sgl_csr_find,              the edge set and the random negative pairs of mask_test_edges (sgl/tasks/utils.py:148-259): is (i, j)
  *   sgl_edge_candidates        stored, as a search inside one CSR row; a seeded candidate stream with each pair's verdict.
  *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
+ *   sgl_cluster_loss_grad_f32  cluster_loss and its backward (sgl/tasks/utils.py:101-113; clustering_train, 116-136): per-row loss and dX in one pass.
  *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
  *   sgl_hop_concat_bf16(_f32), STORED as bfloat16 (opt-in hop storage): read in place, widened exactly, float32 arithmetic in
  *   sgl_nafs_bf16_f32          the float32 entries' order -- bit-identical to widening every hop first, without the copies.
@@ -580,6 +581,22 @@ int sgl_edge_candidates(const int64_t *d_rowptr, const int32_t *d_col, int64_t n
  * d = 0: labels 0, distances 0. */
 int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_centres, int64_t ldc, int64_t k,
                           int64_t *d_labels, float *d_mindist, void *stream);
+
+/* The loss of the trainable clustering task and its gradient (cluster_loss, sgl/tasks/utils.py:101-113, and the backward that
+ * clustering_train runs on it, 116-136) in one pass over X: with D_ij = |x_i - c_j|_2 and y_i = d_labels[i],
+ *     d_row_loss[i] = 2 D_{i, y_i} - (1 / k) sum_j D_ij                  float32 [n]; the caller adds the rows in float64 and scales
+ *     d_dx[i]       = w sum_j a_ij (x_i - c_j),  a_ij = (2 [j = y_i] - 1 / k) / D_ij, and a_ij = 0 where D_ij = 0 (torch.norm's subgradient)
+ * w is one scalar (1 / n for the mean).  Either output may be NULL, not both (unless n = 0).  The centres and the labels carry no gradient.  Direct
+ * form only -- the difference first, for the distance and for the gradient (translation-invariant) -- one read of X and one write of
+ * dX, centres staged in LDS tiles of at most 64 KiB with the running sums crossing tiles: any k x d.  A label outside [0, k) means "no
+ * assigned centre": the 2 D term and its gradient are absent and nothing is read out of bounds.  A non-finite row gives non-finite
+ * results in that row alone; the kernel never traps.  Columns d .. pitch are never used (they may hold NaN), nothing beyond column d of
+ * a last row is read or of any row written.  16-byte aligned bases with pitches that are multiples of 4 floats (X, C and, when given,
+ * dX) get 16-byte lane accesses, everything else one float per lane; the sums run centre after centre in an order that depends on d,
+ * that layout and k alone: not on n, the tile or the row's position, and two runs are bit-equal (no atomics).  k >= 1 always.
+ * n = 0: nothing is done; d = 0: d_row_loss = 0, no kernel. */
+int sgl_cluster_loss_grad_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_centres, int64_t ldc, int64_t k,
+                              const int64_t *d_labels, float w, float *d_dx, int64_t lddx, float *d_row_loss, void *stream);
 
 /* Per-column content signature of a DEVICE matrix: d_sig[c] = wrapping 64-bit sum over the rows r of mix(bits(X[r, c]), r), for
  * c < round_up(d, 4) (uint64 on device; rows 16-byte aligned, pitch a multiple of 4 floats covering round_up(d, 4)).  One streaming

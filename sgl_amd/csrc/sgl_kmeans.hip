@@ -22,44 +22,9 @@
 // distance never wins; a row whose k distances are ALL NaN (a NaN in the row) gets label 0 and mindist NaN.  Nothing traps.
 // VEC = 4 needs 16-byte aligned bases and pitches that are multiples of 4 floats on both matrices; pads are zeroed before use and
 // nothing beyond column d of a LAST row is read (edge_load).
-#include "sgl_rows.h"
+#include "sgl_centres.h"   // Sq, stage_centres, kTileFloats: shared with sgl_cluster_loss.hip (K12)
 
 namespace {
-
-using f2 = float __attribute__((ext_vector_type(2)));
-
-template <int VEC>
-struct Sq;                                           // a lane's partial sum of squared differences
-template <>
-struct Sq<4> {
-    f2 a = {0.f, 0.f};
-    __device__ __forceinline__ void add(const f4 x, const f4 c) {
-        const f2 lo = x.lo - c.lo, hi = x.hi - c.hi;
-        a = __builtin_elementwise_fma(lo, lo, a);
-        a = __builtin_elementwise_fma(hi, hi, a);
-    }
-    // the same with the centre NEGATED: x + (-c) is x - c bit for bit, and of the two only the packed add is selected as one
-    // instruction (the subtraction of two float2 compiles to two scalar subtractions and two moves that pair their results again)
-    __device__ __forceinline__ void add_negated(const f4 x, const f4 nc) {
-        const f2 lo = x.lo + nc.lo, hi = x.hi + nc.hi;
-        a = __builtin_elementwise_fma(lo, lo, a);
-        a = __builtin_elementwise_fma(hi, hi, a);
-    }
-    __device__ __forceinline__ float total() const { return a[0] + a[1]; }
-};
-template <>
-struct Sq<1> {
-    float a = 0.f;
-    __device__ __forceinline__ void add(const float x, const float c) {
-        const float t = x - c;
-        a = fmaf(t, t, a);
-    }
-    __device__ __forceinline__ void add_negated(const float x, const float nc) {
-        const float t = x + nc;
-        a = fmaf(t, t, a);
-    }
-    __device__ __forceinline__ float total() const { return a; }
-};
 
 struct Best {                                        // running minimum of one row over the centres seen so far
     float dist = __builtin_inff();
@@ -124,23 +89,6 @@ __device__ __forceinline__ void merge_rows(Best &b) {
     };
     if constexpr (LPR == 64) step([](unsigned v) { return __builtin_amdgcn_permlane32_swap(v, v, false, false); });
     if constexpr (LPR >= 32) step([](unsigned v) { return __builtin_amdgcn_permlane16_swap(v, v, false, false); });
-}
-
-constexpr int kTileFloats = 16384;                   // 64 KiB of centres per tile
-
-// centres j0 .. j0 + kt - 1, NEGATED (Sq::add_negated), into the tile (pitch dp = d rounded up to VEC), pad zeroed: one wavefront
-// per centre row
-template <int VEC>
-__device__ __forceinline__ void stage_centres(float *__restrict__ tile, const float *__restrict__ cen, const int64_t ldc, const int k,
-                                              const int j0, const int kt, const int d, const int dp) {
-    using V = typename Vt<VEC>::type;
-    const int lane = threadIdx.x % 64;
-    for (int jj = threadIdx.x / 64; jj < kt; jj += 4) {
-        const float *crow = cen + (int64_t)(j0 + jj) * ldc;
-        const bool last = j0 + jj == k - 1;
-        for (int col = lane * VEC; col < dp; col += 64 * VEC)
-            *reinterpret_cast<V *>(tile + jj * dp + col) = -edge_load<VEC>(crow, col, d, last);
-    }
 }
 
 template <int LPR, int VEC, int CH, int U>

@@ -1906,6 +1906,46 @@ def kmeans_assign(x, centres, want_dist=True):
     return labels, mindist
 
 
+def cluster_loss_grad(x, centres, labels, w, dx=None, row_loss=None):
+    """One launch of sgl_cluster_loss_grad_f32: with D_ij = |x[i] - centres[j]|_2 and y_i = labels[i] (int64 [n] on x's device),
+    row_loss[i] = 2 D_{i, y_i} - mean_j D_ij (float32 [n]) and dx[i] = w sum_j a_ij (x[i] - centres[j]), a_ij = (2 [j = y_i] - 1 / k) /
+    D_ij and 0 where D_ij = 0 -- the direct form, differences first.  x: [n, d], centres: [k, d] float32 CUDA matrices on one device,
+    read in place (padded buffers, column views).  dx / row_loss: True allocates the output, a tensor is written in place, None /
+    False leaves it out; at least one is needed.  A label outside [0, k) means "no assigned centre" (nothing is indexed by it).
+    Returns (dx, row_loss).  No atomics: two runs are bit-equal.  Nothing here synchronises."""
+    _no_bf16("cluster_loss_grad", x, centres, dx, row_loss)
+    _check_mat(x, "x")
+    _check_mat(centres, "centres")
+    if x.shape[1] != centres.shape[1] or x.device != centres.device:
+        raise ValueError("cluster_loss_grad: x and centres must have the same row length and live on one device")
+    n, d = x.shape
+    k = centres.shape[0]
+    if k < 1:
+        raise ValueError("cluster_loss_grad: at least one centre is needed")
+    if not (torch.is_tensor(labels) and labels.device == x.device and labels.dtype == torch.int64 and labels.dim() == 1
+            and labels.numel() == n and labels.is_contiguous()):
+        raise ValueError("cluster_loss_grad: `labels` must be a contiguous int64 [n] tensor on x's device")
+    dx = None if dx is False else dx
+    row_loss = None if row_loss is False else row_loss
+    if dx is None and row_loss is None:
+        raise ValueError("cluster_loss_grad: at least one of `dx` and `row_loss` is needed")
+    if dx is True:
+        dx = alloc_rows(n, d, x.device)
+    elif dx is not None:
+        _check_mat(dx, "dx")
+        if dx.shape != x.shape or dx.device != x.device:
+            raise ValueError("cluster_loss_grad: `dx` must have x's shape and device")
+    if row_loss is True:
+        row_loss = torch.empty(n, dtype=torch.float32, device=x.device)
+    elif row_loss is not None and not (torch.is_tensor(row_loss) and row_loss.device == x.device and row_loss.dtype == torch.float32
+                                       and row_loss.dim() == 1 and row_loss.numel() == n and row_loss.is_contiguous()):
+        raise ValueError("cluster_loss_grad: `row_loss` must be a contiguous float32 [n] tensor on x's device")
+    _call(x.device, "sgl_cluster_loss_grad_f32", ptr(x), _ld(x), n, d, ptr(centres), _ld(centres), k, ptr(labels), float(w), _opt_ptr(dx),
+          _ld(dx) if dx is not None else 0, _opt_ptr(row_loss))
+    _wrote(dx, row_loss)
+    return dx, row_loss
+
+
 def gather_rows(x, idx, out=None):
     """x[idx] on device (BaseSGAPModel.forward's per-step row gather, models/base_model.py:58,60).  `out`: optional
     preallocated [len(idx), d] destination (the pack step of the need-aware exchange re-uses one send buffer per hop).

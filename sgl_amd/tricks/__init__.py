@@ -2,9 +2,11 @@
 label propagation / Correct&Smooth (reference: sgl/tricks) and the NAFS feature-smoothing pipeline of the
 NAFS clustering / link-prediction tasks (reference: sgl/tasks/node_clustering.py:205-258); the edge scores and ranking metrics that
 end the link-prediction task (sgl/tasks/link_prediction.py:282-283, without the N x N matrix); the k-means and the three
-scores that end the clustering task (sgl/tasks/node_clustering.py:254-257); and the label use / label reuse
+scores that end the clustering task (sgl/tasks/node_clustering.py:254-257); the loss, the step and the loop of the trainable clustering
+task (sgl/tasks/utils.py:101-136, node_clustering.py:12-119); and the label use / label reuse
 loop around `model.preprocess` (reference: sgl/tasks/node_classification_with_label_use.py:58-137)."""
-from .clustering import KMeansResult, NodeClusteringResult, clustering_scores, kmeans, nafs_node_clustering
+from .clustering import (KMeansResult, NodeClusteringResult, NodeClusteringTrainResult, cluster_loss, clustering_scores, clustering_train,
+                         kmeans, nafs_node_clustering, node_clustering)
 from .correct_and_smooth import CorrectAndSmooth
 from .label_reuse import add_labels, label_reuse, predict_all
 from .link_prediction import (EdgePlan, EdgeSplit, GAELinkPredictionResult, LinkPredictionResult, binary_ranking_metrics, edge_bce_loss,
@@ -17,4 +19,5 @@ __all__ = ["CorrectAndSmooth", "label_propagation", "nafs_ensemble_features", "n
            "edge_scores", "binary_ranking_metrics", "edge_predict_score", "nafs_link_prediction", "LinkPredictionResult",
            "has_edges", "mask_test_edges", "EdgeSplit",
            "EdgePlan", "edge_bce_loss", "edge_predict_train", "edge_predict_eval", "gae_link_prediction", "GAELinkPredictionResult",
-           "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult"]
+           "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult",
+           "cluster_loss", "clustering_train", "node_clustering", "NodeClusteringTrainResult"]

@@ -18,7 +18,12 @@ on CPU cores, after copying [N, d] to the host.  Here the features stay where na
 What is and is not sklearn parity: the Lloyd loop follows sklearn's stopping rule exactly, so from the SAME initial centres it ends
 with the same labels after the same number of iterations wherever no row sits on a tie.  The seeding is plain k-means++ (one
 candidate per step) from a torch.Generator -- sklearn's greedy variant tries 2 + ln k candidates per step and draws from numpy --
-so with a seed alone the two agree only on inputs with a single optimum."""
+so with a seed alone the two agree only on inputs with a single optimum.
+
+The TRAINABLE task, NodeClustering (sgl/tasks/node_clustering.py:12-119), trains a model on cluster_loss (sgl/tasks/utils.py:101-113)
+with a k-means of the model output in every step (clustering_train, 116-136).  Here the output never leaves the device: kmeans above,
+then ONE launch for the loss and its gradient (device.cluster_loss_grad -> sgl_cluster_loss_grad_f32), then clustering_scores:
+cluster_loss, clustering_train and node_clustering below."""
 from collections import namedtuple
 
 import numpy as np
@@ -27,7 +32,8 @@ import torch
 from .. import device as dev
 from .nafs_features import nafs_ensemble_sweep
 
-__all__ = ["kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult"]
+__all__ = ["kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult",
+           "cluster_loss", "clustering_train", "node_clustering", "NodeClusteringTrainResult"]
 
 KMeansResult = namedtuple("KMeansResult", ["labels", "centres", "inertia", "n_iter"])
 KMeansResult.__doc__ = """kmeans' result: labels int64 [n] and centres float32 [k, d] on x's device, inertia (float: the float64 sum of the
@@ -268,3 +274,143 @@ def nafs_node_clustering(adj, x, y, hops, r_list=(0.5, 0.4, 0.3, 0.2, 0.1, 0), m
         if adjscore > best_adjscore:
             best_adjscore, best_hop_adjscore = adjscore, hop
     return NodeClusteringResult(metrics, best_hop_acc, best_hop_nmi, best_hop_adjscore, best_acc, best_nmi, best_adjscore)
+
+
+# ---- the trainable task ---------------------------------------------------------------------------------------------------------------------
+class _ClusterLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, labels, centres, w):
+        dx, row_loss = dev.cluster_loss_grad(output, centres, labels, w, dx=True, row_loss=True)
+        ctx.dx = dx
+        return (row_loss.sum(dtype=torch.float64) * w).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        dx, ctx.dx = ctx.dx, None
+        if dx is None:
+            raise RuntimeError("cluster_loss: backward ran twice; the gradient buffer of the forward launch was handed out the first time")
+        return dx.mul_(g), None, None, None
+
+
+def _device_labels(labels, k, n, device, check):
+    """int64 [n] on `device`; check=True: labels in [-k, k) wrap as numpy indices do, anything else raises IndexError (one host
+    read of the two extremes); check=False: taken as they are (labels that come from kmeans)"""
+    t = torch.as_tensor(np.asarray(labels) if not torch.is_tensor(labels) else labels)
+    if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+        raise TypeError("cluster_loss: labels must be integers")
+    t = t.reshape(-1).to(device=device, dtype=torch.int64).contiguous()
+    if t.numel() != n:
+        raise ValueError(f"cluster_loss: {t.numel()} labels for {n} rows")
+    if check and n:
+        lo, hi = (int(v) for v in torch.aminmax(t))
+        if lo < -k or hi >= k:
+            raise IndexError(f"cluster_loss: label {lo if lo < -k else hi} is out of bounds for {k} centres")
+        if lo < 0:
+            t = torch.where(t < 0, t + k, t)
+    return t
+
+
+def cluster_loss(output, labels, centres, reduction="mean", check=True):
+    """cluster_loss of the reference (sgl/tasks/utils.py:101-113) as a float32 scalar on the device that carries the gradient to
+    `output` alone: with D_ij = |output[i] - centres[j]|_2,
+
+        loss = (1 / n) sum_i (2 D_{i, labels[i]} - (1 / k) sum_j D_ij)        ("mean", the reference; "sum": without the 1 / n)
+
+    output: [n, d] float32 CUDA matrix; centres: [k, d] (tensor or ndarray; moved to output's device; no gradient, as in the
+    reference, which builds them from numpy); labels: n integers (tensor or ndarray).  check=True: labels in [-k, k) wrap as numpy
+    indices do (dist[j, x] in the reference), anything else raises IndexError -- one host read; check=False validates nothing (for
+    labels that come from kmeans): a label outside [0, k) then means "no assigned centre".
+    ONE launch (sgl_cluster_loss_grad_f32) computes the per-row losses and, when output requires grad, dX as well -- the direct form,
+    differences first, one read of output and one write of dX; the loss is the float64 sum of the rows' float32 losses.  The
+    backward multiplies that buffer by the upstream gradient in place: no launch of ours, no host synchronisation, nothing allocated.
+    The gradient where a row coincides with a centre is 0 for that term (torch.norm's subgradient).  No atomics: two runs are
+    bit-equal.  bf16 output is refused."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError("cluster_loss: reduction must be 'mean' or 'sum'")
+    dev._no_bf16("cluster_loss", output, centres)
+    dev._check_mat(output, "output")
+    if not torch.is_tensor(centres):
+        centres = torch.as_tensor(np.asarray(centres), dtype=torch.float32)
+    centres = centres.detach().to(device=output.device)
+    dev._check_mat(centres, "centres")
+    n, d = output.shape
+    k = centres.shape[0]
+    if k < 1 or centres.shape[1] != d:
+        raise ValueError(f"cluster_loss: centres must be [k >= 1, {d}]")
+    labels = _device_labels(labels, k, n, output.device, check)
+    w = 1.0 / n if (reduction == "mean" and n) else 1.0
+    if torch.is_grad_enabled() and output.requires_grad:
+        return _ClusterLoss.apply(output, labels, centres, w)
+    _, row_loss = dev.cluster_loss_grad(output.detach(), centres, labels, w, row_loss=True)
+    return (row_loss.sum(dtype=torch.float64) * w).to(torch.float32)
+
+
+def _model_output(model, nodes, device):
+    return model.model_forward(nodes, device) if hasattr(model, "model_forward") else model(nodes)
+
+
+def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda"):
+    """clustering_train of the reference (sgl/tasks/utils.py:116-136), one step: model_forward, k-means of the DETACHED output
+    (kmeans above: n_init runs seeded with `seed`, on the device -- the reference copies the output to the host for sklearn),
+    cluster_loss on its labels and centres, backward, optimizer.step, and the three scores of the k-means labels against y.
+    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated."""
+    device = torch.device(device)
+    if optimizer is not None:
+        model.train()
+        optimizer.zero_grad()
+    with torch.set_grad_enabled(optimizer is not None):
+        out = _model_output(model, train_idx, device)
+        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed)
+        loss = cluster_loss(out, km.labels, km.centres, check=False)
+        if optimizer is not None:
+            loss.backward()
+            optimizer.step()
+    acc, nmi, adjscore = clustering_scores(y, km.labels)
+    return float(loss.detach()), acc, nmi, adjscore
+
+
+NodeClusteringTrainResult = namedtuple("NodeClusteringTrainResult", ["acc", "nmi", "adjscore", "history"])
+NodeClusteringTrainResult.__doc__ = """node_clustering's result: the three bests NodeClustering keeps, and history = one dict per epoch (epoch,
+loss, acc, nmi, adjscore) followed by the post-processing entry (epoch = "post", without a loss)"""
+
+
+def node_clustering(model, adj, x, y, epochs, lr, weight_decay, n_init=20, seed=42, device="cuda"):
+    """NodeClustering._execute of the reference (sgl/tasks/node_clustering.py:54-119), on the device: model.preprocess(adj, x), Adam(lr,
+    weight_decay), `epochs` steps of clustering_train over ALL nodes (k = the number of distinct labels in y), then the final step --
+    model_forward in eval mode -> model.postprocess(adj, output) when the model has one -> kmeans -> scores -- and the best-of
+    bookkeeping of lines 84-98: strictly greater wins, the bests start at 0.  Returns a NodeClusteringTrainResult.
+    Seeds: torch.manual_seed(seed) once, as the reference's set_seed; the k-means of epoch e is seeded with seed + e and the final one
+    with seed + epochs (the reference leaves KMeans unseeded, so its runs differ; same seed, same result here).
+    The reference calls `postprocess(outputs)` WITHOUT the adjacency, which BaseSGAPModel.postprocess(adj, output) does not accept: it
+    raises at its final step.  Here adj is passed."""
+    device = torch.device(device)
+    y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(-1).to(device)
+    n = int(y.numel())
+    k = int(torch.unique(y).numel())
+    torch.manual_seed(seed)
+    model.preprocess(adj, x)
+    model = model.to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    nodes = torch.arange(n, dtype=torch.int64, device=device)
+    best = [0., 0., 0.]
+    history = []
+
+    def keep(scores):
+        for i, v in enumerate(scores):
+            if v > best[i]:
+                best[i] = v
+
+    for epoch in range(epochs):
+        loss, acc, nmi, adjscore = clustering_train(model, nodes, y, optimizer, k, n_init=n_init, seed=seed + epoch, device=device)
+        history.append(dict(epoch=epoch, loss=loss, acc=acc, nmi=nmi, adjscore=adjscore))
+        keep((acc, nmi, adjscore))
+    with torch.no_grad():                              # _postprocess (lines 106-119)
+        model.eval()
+        out = _model_output(model, nodes, device)
+        if hasattr(model, "postprocess"):
+            out = model.postprocess(adj, out)
+        scores = clustering_scores(y, kmeans(out, k, n_init=n_init, seed=seed + epochs).labels)
+    history.append(dict(epoch="post", acc=scores[0], nmi=scores[1], adjscore=scores[2]))
+    keep(scores)
+    return NodeClusteringTrainResult(best[0], best[1], best[2], history)
