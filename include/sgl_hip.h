@@ -33,6 +33,8 @@
  *                              list grouped by endpoint once: scores, coefficients and dZ in one pass, no sort, no atomics.
  *   sgl_csr_find,              the edge set and the random negative pairs of mask_test_edges (sgl/tasks/utils.py:148-259): is (i, j)
  *   sgl_edge_candidates        stored, as a search inside one CSR row; a seeded candidate stream with each pair's verdict.
+ *   sgl_csr_select_rowptr,     the graph transforms of sgl/data/transforms.py (get_subgraph, drop_edges, random_drop_edges, remove_self_loops,
+ *   sgl_csr_select_fill        ...): a canonical CSR filtered into a canonical CSR in two passes, no sort, no atomics.
  *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
  *   sgl_cluster_loss_grad_f32  cluster_loss and its backward (sgl/tasks/utils.py:101-113; clustering_train, 116-136): per-row loss and dX in one pass.
  *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
@@ -569,6 +571,44 @@ int sgl_csr_find(const int64_t *d_rowptr, const int32_t *d_col, int64_t n_rows, 
  * int64).  count = 0: nothing is done; more candidates than one launch covers -> SGL_ERR_UNSUPPORTED (split the range). */
 int sgl_edge_candidates(const int64_t *d_rowptr, const int32_t *d_col, int64_t n, uint64_t seed, int64_t first, int64_t count,
                         int64_t *d_edges, int64_t *d_key, void *stream);
+
+/* Filter a canonical CSR (columns sorted and unique inside each row; not checked) into a new canonical CSR: the graph transforms of
+ * sgl/data/transforms.py (get_subgraph, random_drop_nodes, drop_edges, biased_drop_edges, random_drop_edges, remove_self_loops) without
+ * the COO edge list, the boolean index and the new csr_matrix.  Two calls, because the size of the result is not known beforehand:
+ *
+ *   sgl_csr_select_rowptr   counts the kept entries of every output row, scans the counts into d_out_rowptr [n_rows_out + 1] and returns
+ *                           the total in *h_nnz_out.  It allocates O(n_rows_out) scratch and SYNCHRONISES the stream, like sgl_coo_to_csr.
+ *   sgl_csr_select_fill     writes d_out_col, d_out_val and, when it is not NULL, d_out_pos [total]: int64, the position in the SOURCE of
+ *                           every kept entry (to carry edge attributes along).  Stream-ordered, no synchronisation.  d_out_rowptr is
+ *                           what the first call wrote; the outputs hold exactly *h_nnz_out entries (non-NULL pointers even when that is 0).
+ *
+ * Both take the same selection arguments and evaluate one predicate.  Entry p = (i, j, v) of the source is kept iff ALL of:
+ *   - d_row_map[i] in [0, n_rows_out) and d_col_map[j] in [0, n_cols_out): int32 old id -> new id, -1 = dropped, NULL = the identity
+ *     (then n_*_out must equal n_*).  Any value outside the range (below -1, at or beyond n_*_out) counts as dropped and indexes
+ *     nothing.  REQUIRED of the caller: the kept ids of a map increase with the old id and no two old ids share a new one (an
+ *     exclusive scan of a 0/1 mask gives that) -- then the output is canonical.  A map that breaks this cannot make the kernels write
+ *     out of bounds, but the output is then not a canonical CSR and entries may be missing.
+ *   - d_entry_keep[p] != 0 (uint8 [nnz], NULL = all), when symmetric_mask == 0;
+ *     d_entry_keep[q] != 0 when symmetric_mask != 0, q = the position of the pair's UPPER entry (min(i, j), max(i, j)): p itself for
+ *     i <= j, else found by a bisection inside row j; a lower entry whose mirror is not stored is dropped.  The mask is never written.
+ *   - not (drop_self != 0 and i == j);
+ *   - h(seed, 103, a, b) >= drop_below (uint64; 0 = nothing is dropped; h: the hash of csrc/sgl_hash.h), (a, b) = (i, j), or
+ *     (min(i, j), max(i, j)) when symmetric != 0, so that both directions of a pair share one decision.  OLD ids: the decision does not
+ *     depend on a node selection made in the same call, nor on the launch shape.
+ * The output row is d_row_map[i], the output column d_col_map[j], the value is copied bit for bit; output rows that no source row maps
+ * to have length 0.  Compaction is stable, there are no atomics: two runs are bit-equal, and so are the compiled shapes.  lanes: the
+ * lanes that walk one row, 4, 16 or 64; 0 = chosen from nnz / n_rows; anything else is refused.  n_rows, n_rows_out < 2^31, n_cols,
+ * n_cols_out <= INT32_MAX; entry positions and row pointers are int64.  nnz must be d_rowptr[n_rows] (not checked here).  Bad sizes,
+ * NULL or misaligned pointers are refused before any launch.  The kernels never trap on the contents of the maps or of the mask. */
+int sgl_csr_select_rowptr(const int64_t *d_rowptr, const int32_t *d_col, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                          const int32_t *d_row_map, const int32_t *d_col_map, int64_t n_rows_out, int64_t n_cols_out,
+                          const uint8_t *d_entry_keep, int symmetric_mask, int drop_self, uint64_t drop_below, uint64_t seed,
+                          int symmetric, int lanes, int64_t *d_out_rowptr, int64_t *h_nnz_out, void *stream);
+int sgl_csr_select_fill(const int64_t *d_rowptr, const int32_t *d_col, const float *d_val, int64_t n_rows, int64_t n_cols, int64_t nnz,
+                        const int32_t *d_row_map, const int32_t *d_col_map, int64_t n_rows_out, int64_t n_cols_out,
+                        const uint8_t *d_entry_keep, int symmetric_mask, int drop_self, uint64_t drop_below, uint64_t seed,
+                        int symmetric, int lanes, const int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val,
+                        int64_t *d_out_pos, void *stream);
 
 /* The assignment step of k-means: labels[i] = argmin_j sum_c (X[i, c] - C[j, c])^2 (int64) and, when d_mindist is not NULL, that
  * minimum -- what KMeans.fit_predict spends its time on in NodeClusteringNAFS (sgl/tasks/node_clustering.py:254-255).  The distance is

@@ -7,5 +7,6 @@
 Python (PyTorch-ROCm for device memory/streams) -> ctypes -> libsgl_hip.so (C ABI, include/sgl_hip.h) -> hand-written
 HIP kernels for gfx950.  There is no CPU fallback: without the built library or without a GPU the hot path raises."""
 from . import config  # noqa: F401
+from . import transforms  # noqa: F401  (the graph transforms of sgl/data/transforms.py on the device)
 
 __version__ = "0.1.0"

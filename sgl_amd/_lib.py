@@ -144,6 +144,10 @@ PROTOTYPES = {
                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sgl_csr_find": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "sgl_edge_candidates": (c_int, [c_void_p, c_void_p, c_int64, c_uint64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sgl_csr_select_rowptr": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_int,
+                                      c_uint64, c_uint64, c_int, c_int, c_void_p, POINTER(c_int64), c_void_p]),
+    "sgl_csr_select_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int,
+                                    c_int, c_uint64, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sgl_kmeans_assign_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "sgl_cluster_loss_grad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p, c_int64,
                                           c_void_p, c_void_p]),

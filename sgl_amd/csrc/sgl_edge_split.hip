@@ -11,6 +11,7 @@
 //
 // Indices (sgl_csr_find): negative ones count from the end; one still outside its range gives -1 and reads NOTHING.  The kernels
 // never trap.  sgl_edge_candidates draws its own indices, in range by construction.
+#include "sgl_csr_search.h"
 #include "sgl_hash.h"
 #include "sgl_rows.h"
 
@@ -18,22 +19,6 @@ namespace {
 
 using i64x2 = long __attribute__((ext_vector_type(2)));
 static_assert(sizeof(i64x2) == 16, "an edge is two int64");
-
-// the p in [rowptr[row], rowptr[row + 1]) with col[p] == v, or -1.  The range [lo, lo + n) always holds v's position if there is
-// one: probe the last element of the lower half, keep one half.
-__device__ __forceinline__ int64_t csr_row_find(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const int64_t row,
-                                                const int32_t v) {
-    int64_t lo = rowptr[row];
-    int64_t n = rowptr[row + 1] - lo;
-    if (n <= 0) return -1;
-    while (n > 1) {
-        const int64_t half = n >> 1;
-        const bool up = col[lo + half - 1] < v;      // v lies beyond the lower half
-        lo = up ? lo + half : lo;
-        n = up ? n - half : half;
-    }
-    return col[lo] == v ? lo : -1;
-}
 
 __global__ __launch_bounds__(256) void csr_find_kernel(const int64_t *__restrict__ rowptr, const int32_t *__restrict__ col, const int64_t n_rows,
                                                        const int64_t n_cols, const int64_t *__restrict__ edges, const int edges16,

@@ -1,11 +1,13 @@
 // The counter-based hash of the seeded generators, shared by the probe library (sgl_synth.hip: the synthetic graphs) and the product
-// library (sgl_edge_split.hip: the candidate stream of the negative edges).  Integer arithmetic only, so a device and its numpy mirror
+// library (sgl_edge_split.hip: the candidate stream of the negative edges; sgl_csr_select.hip: the random edge drop).  Integer arithmetic only, so a device and its numpy mirror
 // (sgl_amd/synthetic.py: _mix64, _hash4, _mulhi64) agree bit for bit.
 //
 //   h(seed, stream, a, b) = mix(mix(mix(seed * GOLD + stream) ^ a) + b),  mix = the splitmix64 finaliser
 //   mulhi64(h, n)         = floor(h * n / 2^64): h scaled into [0, n) without a division
 //
-// Streams in use: 0 degree, 1 column, 2 value, 3 feature (sgl_synth.hip); 101 edge shuffle, 102 negative-edge candidates (the split).
+// Streams in use: 0 degree, 1 column, 2 value, 3 feature (sgl_synth.hip); 101 edge shuffle, 102 negative-edge candidates (the split);
+// 103 edge drop (sgl_csr_select.hip: a = row, b = column of the entry, or the pair's (min, max)), 104 node drop (sgl_amd/transforms.py:
+// a = node, b = 0).
 #pragma once
 #include <hip/hip_runtime.h>
 

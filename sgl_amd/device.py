@@ -1887,6 +1887,79 @@ def edge_candidates(adj, seed, first, count):
     return edges, key
 
 
+CSR_SELECT_LANES = (4, 16, 64)       # the compiled lanes-per-row instances of csr_select_kernel (sgl_csr_select.hip)
+
+
+def csr_select(adj, row_map=None, col_map=None, n_rows_out=None, n_cols_out=None, entry_keep=None, symmetric_mask=False, drop_self=False,
+               drop_below=0, seed=0, symmetric=False, lanes=0, positions=False):
+    """A canonical device CSR filtered into a new one (sgl_csr_select_rowptr + sgl_csr_select_fill; include/sgl_hip.h states the
+    predicate): entry p = (i, j, v) is kept iff row_map[i] and col_map[j] are new ids (int32 [n] device tensors, -1 = dropped, None =
+    identity; kept ids must increase with the old id), entry_keep[p] is set (uint8 / bool [nnz], None = all; with symmetric_mask the
+    flag of the pair's upper entry decides both directions), not (drop_self and i == j), and h(seed, 103, i, j) >= drop_below (with
+    symmetric: h of (min, max)).  Returns a DeviceAdjacency of shape (n_rows_out, n_cols_out) -- defaults: adj's when the map is None --
+    and, with positions=True, also the int64 position in adj of every kept entry.  lanes: 0 = auto, or one of CSR_SELECT_LANES.
+    The first call synchronises the stream (the size of the result comes back through the host)."""
+    from .io import DeviceAdjacency
+    rowptr, col = _csr_arrays(adj, "csr_select")
+    val = adj.val
+    dv = rowptr.device
+    n_rows, n_cols = adj.shape
+    nnz = int(adj.col.numel())
+    if not (torch.is_tensor(val) and val.device == dv and val.dtype == torch.float32 and val.is_contiguous() and val.numel() == nnz):
+        raise TypeError("csr_select: adj.val must be a contiguous float32 tensor of nnz values on the device of adj.rowptr")
+    if n_rows > 0 and int(rowptr[-1]) != nnz:
+        raise ValueError(f"csr_select: adj.rowptr ends at {int(rowptr[-1])}, adj.col holds {nnz} entries")
+    if nnz == 0:
+        val = torch.zeros(1, dtype=torch.float32, device=dv)
+
+    def id_map(m, n_old, n_out, name):
+        if m is None:
+            if n_out is not None and int(n_out) != n_old:
+                raise ValueError(f"csr_select: without `{name}` the output keeps adj's size on that side")
+            return None, n_old
+        if n_out is None:
+            raise ValueError(f"csr_select: `{name}` needs the number of new ids")
+        if not (torch.is_tensor(m) and m.device == dv and m.dtype == torch.int32 and m.dim() == 1 and m.numel() == n_old and m.is_contiguous()):
+            raise ValueError(f"csr_select: `{name}` must be a contiguous int32 [{n_old}] tensor on adj's device")
+        if int(n_out) < 0:
+            raise ValueError("csr_select: the number of new ids must not be negative")
+        return m, int(n_out)
+
+    row_map, n_rows_out = id_map(row_map, n_rows, n_rows_out, "row_map")
+    col_map, n_cols_out = id_map(col_map, n_cols, n_cols_out, "col_map")
+    if entry_keep is not None:
+        if not (torch.is_tensor(entry_keep) and entry_keep.device == dv and entry_keep.dtype in (torch.uint8, torch.bool)
+                and entry_keep.dim() == 1 and entry_keep.numel() == nnz and entry_keep.is_contiguous()):
+            raise ValueError(f"csr_select: `entry_keep` must be a contiguous uint8 or bool [{nnz}] tensor on adj's device")
+        if nnz == 0:
+            entry_keep = torch.zeros(1, dtype=torch.uint8, device=dv)
+    elif symmetric_mask:
+        raise ValueError("csr_select: symmetric_mask needs `entry_keep`")
+    if symmetric_mask and n_rows != n_cols:
+        raise ValueError("csr_select: symmetric_mask needs a square matrix")
+    lanes = int(lanes)
+    if lanes != 0 and lanes not in CSR_SELECT_LANES:
+        raise ValueError(f"csr_select: lanes must be 0 (auto) or one of {CSR_SELECT_LANES}, not {lanes}")
+    drop_below = int(drop_below)
+    if not 0 <= drop_below < (1 << 64):
+        raise ValueError("csr_select: drop_below is an unsigned 64-bit threshold")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    select = (ptr(row_map) if row_map is not None else None, ptr(col_map) if col_map is not None else None, n_rows_out, n_cols_out,
+              _opt_ptr(entry_keep), int(bool(symmetric_mask)), int(bool(drop_self)), drop_below, seed, int(bool(symmetric)), lanes)
+    out_rowptr = torch.empty(n_rows_out + 1, dtype=torch.int64, device=dv)
+    total = c_int64(0)
+    _call(dv, "sgl_csr_select_rowptr", ptr(rowptr), ptr(col), n_rows, n_cols, nnz, *select, ptr(out_rowptr), ctypes.byref(total))
+    m = total.value
+    out_col = torch.empty(max(m, 1), dtype=torch.int32, device=dv)
+    out_val = torch.empty(max(m, 1), dtype=torch.float32, device=dv)
+    out_pos = torch.empty(max(m, 1), dtype=torch.int64, device=dv) if positions else None
+    _call(dv, "sgl_csr_select_fill", ptr(rowptr), ptr(col), ptr(val), n_rows, n_cols, nnz, *select, ptr(out_rowptr), ptr(out_col), ptr(out_val),
+          _opt_ptr(out_pos))
+    _wrote(out_rowptr, out_col, out_val, out_pos)
+    out = DeviceAdjacency(out_rowptr, out_col[:m], out_val[:m], (n_rows_out, n_cols_out))
+    return (out, out_pos[:m]) if positions else out
+
+
 def kmeans_assign(x, centres, want_dist=True):
     """(labels, mindist) of the k-means assignment step (sgl_kmeans_assign_f32): labels[i] = argmin_j |x[i] - centres[j]|^2 (int64 [n],
     the lowest index on a tie) and that minimum (float32 [n]; None with want_dist=False) -- the direct sum of squared differences, not
