@@ -246,7 +246,9 @@ int sgl_reorder_lpa_round(const int64_t *d_rowptr, const int32_t *d_col, int64_t
 /* The rows of a CSR in processing order: storage row k of the output = input row d_perm[k]; column ids and the order of every
  * row's entries unchanged (out_rowptr [n+1], out_col / out_val [nnz] caller-allocated).  A handle created on the output and
  * given the same array as its row map computes bit for bit the products of the original matrix -- X and Y keep the caller's node
- * order, only the order in which rows are processed (and with it the reuse of gathered rows in L2 / the Infinity Cache) changes. */
+ * order, only the order in which rows are processed (and with it the reuse of gathered rows in L2 / the Infinity Cache) changes.
+ * With any of d_col / d_val / d_out_col / d_out_val NULL only d_out_rowptr is written.  n = 0: d_perm may be NULL.  d_perm is not
+ * validated here (sgl_csr_set_rowmap validates the same array). */
 int sgl_csr_permute_rows(const int64_t *d_rowptr, const int32_t *d_col, const float *d_val, int64_t n, const int32_t *d_perm,
                          int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val, void *stream);
 /* Storage row i of the handle is output row d_rowmap[i] (a permutation of 0..n_rows-1; NULL removes the map; the array must
@@ -364,8 +366,10 @@ int sgl_norm_degree_powers(int64_t n, const double *d_deg, double r, double *d_l
 
 /* ---- ingest: COO edge list -> canonical CSR on device (sgl/data/base_data.py:29, dataset/custom_dataset.py:52-54) ---- */
 /* d_row / d_col: int64 [nnz] (the reference keeps them as torch.LongTensor), d_val float32 [nnz].  Duplicate (row,col)
- * pairs are summed in input order (fp32), columns come out sorted inside each row -- what scipy's
- * csr_matrix((data,(row,col))) produces.  Outputs: d_out_rowptr [n_rows+1]; d_out_col / d_out_val sized for nnz
+ * pairs are folded into one sequential fp32 sum in input (storage) order, columns come out sorted inside each row: the
+ * structure of scipy's csr_matrix((data,(row,col))) everywhere (a sum that cancels to zero stays an entry) and its value
+ * bits wherever a pair is stored at most twice -- scipy sorts a row with an unstable sort before it folds, so a pair stored
+ * three times or more may be added in another order there.  Outputs: d_out_rowptr [n_rows+1]; d_out_col / d_out_val sized for nnz
  * entries, the first *h_nnz_out of them are valid.  Synchronises `stream`.  Fails on an out-of-range index. */
 int sgl_coo_to_csr(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *d_row, const int64_t *d_col,
                    const float *d_val, int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val, int64_t *h_nnz_out,

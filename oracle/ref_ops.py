@@ -536,13 +536,17 @@ def nafs_task_sweep(indptr, indices, data, n, x, hops_list, r_list, method):
     return {int(h): nafs_task_features(indptr, indices, data, n, x, int(h), r_list, method) for h in hops_list}
 
 
-def coo_to_csr(row, col, data, n):
-    """Edge's csr_matrix((w,(row,col)), shape=(n,n)) (sgl/data/base_data.py:29): float32, duplicates summed in input
-    order, sorted columns.  Returns (indptr int64, indices int32, values float32)."""
+def coo_to_csr(row, col, data, n, n_cols=None):
+    """Edge's csr_matrix((w,(row,col)), shape=(n,n)) (sgl/data/base_data.py:29): float32, sorted columns, the duplicates of a
+    (row, col) pair folded into ONE SEQUENTIAL float32 SUM IN STORAGE (input) ORDER.  scipy gives these bits wherever a pair occurs
+    at most twice (a + b = b + a); it sorts a row's entries with an unstable sort before it folds them, so a pair stored three
+    times or more may be added in another order there (tests/test_ingest_cpu.py).  n_cols (default n): a rectangular shape
+    (n, n_cols).  Returns (indptr int64, indices int32, values float32)."""
+    n_cols = n if n_cols is None else n_cols
     row = np.asarray(row, dtype=np.int64)
     col = np.asarray(col, dtype=np.int64)
     data = np.asarray(data, dtype=np.float32)
-    order = np.argsort(row * n + col, kind="stable")
+    order = np.argsort(row * n_cols + col, kind="stable")
     r, c, v = row[order], col[order], data[order]
     head = np.ones(len(r), dtype=bool)
     head[1:] = (r[1:] != r[:-1]) | (c[1:] != c[:-1])

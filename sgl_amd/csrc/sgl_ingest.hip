@@ -5,8 +5,12 @@
 // i.e. float32 values, duplicate (row, col) pairs SUMMED (in storage order), columns sorted inside each row --
 // the only route by which a raw `adj_matrix.npz{row,col,data}` dump (dataset/custom_dataset.py:52-54) becomes the
 // matrix GraphOp.propagate consumes.  Here: 64-bit (row,col) keys, a STABLE radix sort (rocPRIM), run heads by
-// comparison with the predecessor, exclusive scan for output slots, and one sequential fp32 sum per run (runs are
-// short; sequential = the order scipy adds them in) -- int64-safe, no atomics, deterministic.
+// comparison with the predecessor, exclusive scan for output slots, and one sequential fp32 sum per run, in STORAGE
+// order (runs are short) -- int64-safe, no atomics, deterministic.  The contract for the values: the storage-order
+// sequential fp32 sum, bit-equal to scipy's wherever a (row, col) pair is stored at most twice (a + b = b + a).  scipy
+// sorts a row's entries with an UNSTABLE sort before it folds equal columns, so a pair stored three times or more may
+// be added in another order there; structure and entry count (sums that cancel to zero stay entries) are scipy's
+// everywhere.  tests/ingest_common.py states it in numpy, tests/test_gpu_ingest.py pins it bit for bit.
 #include "sgl_common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>

@@ -220,12 +220,13 @@ SGL_EXPORT int sgl_reorder_lpa_round(const int64_t *d_rowptr, const int32_t *d_c
 SGL_EXPORT int sgl_csr_permute_rows(const int64_t *d_rowptr, const int32_t *d_col, const float *d_val, int64_t n,
                                     const int32_t *d_perm, int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val,
                                     void *stream) {
-    SGL_REQUIRE(d_rowptr && d_perm && d_out_rowptr && n >= 0 && n < INT32_MAX, "sgl_csr_permute_rows: bad arguments");
+    SGL_REQUIRE(d_rowptr && d_out_rowptr && n >= 0 && n < INT32_MAX, "sgl_csr_permute_rows: bad arguments");
     hipStream_t st = sgl::as_stream(stream);
-    if (n == 0) {
+    if (n == 0) {   // an empty permutation has no address (an empty tensor's pointer is NULL)
         SGL_HIP_CHECK(hipMemsetAsync(d_out_rowptr, 0, sizeof(int64_t), st));
         return SGL_OK;
     }
+    SGL_REQUIRE(d_perm, "sgl_csr_permute_rows: NULL permutation");
     SGL_REQUIRE(sgl::launch_fits((n + 3) / 4, 256), "sgl_csr_permute_rows: too many rows for one launch");
     Tmp tmp;
     int rc;

@@ -2474,6 +2474,11 @@ def test_ingest_raw_files_to_device_adjacency(goldens, cuda, tmp_path):
     assert np.array_equal(adj.rowptr.cpu().numpy(), g7["indptr"]) and np.array_equal(adj.col.cpu().numpy(), g7["indices"])
     v = adj.val.cpu().numpy()
     assert (v != g7["values"]).sum() <= 2 and np.allclose(v, g7["values"], rtol=3e-7, atol=0)
+    # the contract: the storage-order sequential float32 sum, bit for bit; scipy's bits (the golden) wherever a pair is stored at most twice
+    assert np.array_equal(v, oracle.coo_to_csr(g7["row"], g7["col"], g7["data"], n)[2])
+    key = np.sort(g7["row"].astype(np.int64) * n + g7["col"].astype(np.int64))
+    stored = np.diff(np.flatnonzero(np.concatenate(([True], key[1:] != key[:-1], [True]))))
+    assert len(stored) == len(v) and stored.max() >= 3 and np.array_equal(v[stored <= 2], g7["values"][stored <= 2])
     assert ds["y"].shape == (n,) and len(ds["train_idx"]) == n // 2 and ds["val_idx"] is None
     hops = LaplacianGraphOp(2, strict_order=True).propagate(adj, ds["x"])
     ref = oracle.propagate(oracle.laplacian_adj(g7["indptr"], g7["indices"], v, n, 0.5), x, 2)
