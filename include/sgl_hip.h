@@ -37,6 +37,7 @@
  *   sgl_csr_select_fill        ...): a canonical CSR filtered into a canonical CSR in two passes, no sort, no atomics.
  *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
  *   sgl_cluster_loss_grad_f32  cluster_loss and its backward (sgl/tasks/utils.py:101-113; clustering_train, 116-136): per-row loss and dX in one pass.
+ *   sgl_class_loss_grad_f32    nn.CrossEntropyLoss, its backward and accuracy's arg-max (train / evaluate, sgl/tasks/utils.py:12-98): per-row loss, dZ and the predicted class in one pass.
  *   sgl_hop_reduce_bf16_f32,   the same Sum/Mean/Max/Min/weighted, Concat and OverSmoothDistance _combine over hop matrices
  *   sgl_hop_concat_bf16(_f32), STORED as bfloat16 (opt-in hop storage): read in place, widened exactly, float32 arithmetic in
  *   sgl_nafs_bf16_f32          the float32 entries' order -- bit-identical to widening every hop first, without the copies.
@@ -641,6 +642,26 @@ int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, c
  * n = 0: nothing is done; d = 0: d_row_loss = 0, no kernel. */
 int sgl_cluster_loss_grad_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_centres, int64_t ldc, int64_t k,
                               const int64_t *d_labels, float w, float *d_dx, int64_t lddx, float *d_row_loss, void *stream);
+
+/* The loss of the node-classification task, its gradient and the predicted class (nn.CrossEntropyLoss on class indices, accuracy's
+ * output.max(1)[1], and the backward that train / mini_batch_train run, sgl/tasks/utils.py:12-98) in one pass over the logits Z [n, c]:
+ * with m_i = max_j z_ij, s_i = sum_j exp(z_ij - m_i), lse_i = m_i + log s_i, y_i = d_labels[i] and row i LIVE iff 0 <= y_i < c,
+ *     d_row_loss[i] = lse_i - z_{i, y_i}                         for a live row, else 0; float32 [n]; the caller adds the rows in float64 and scales
+ *     d_dz[i, j]    = w (exp(z_ij - m_i) / s_i - [j = y_i])      for a live row, else 0; every row is overwritten whole, columns 0 .. c - 1 only
+ *     d_pred[i]     = the lowest index of the row's maximum (int64); a NaN counts as the maximum and the first NaN wins, as
+ *                     output.max(1)[1] does on the CPU.  It does not depend on the label: when d_pred is the only output requested no exp
+ *                     is evaluated and d_labels may be NULL.
+ * w is one scalar (1 / live rows for the mean).  Any of the three outputs may be NULL, not all (unless n = 0).  The labels carry no
+ * gradient.  Accurate expf / logf and IEEE division; the maximum is subtracted first, so rows with entries of magnitude 1e4 stay finite.
+ * An entry of -inf is a class of probability 0.  A NaN or +inf in a row (or a row of -inf alone) gives non-finite loss and dZ in that
+ * row alone; the kernel never traps.  A label outside [0, c) means "no label" (this is how ignore_index arrives): nothing is read out
+ * of bounds.  Columns c .. pitch are never used (they may hold NaN), nothing beyond column c of a last row is read or of any row
+ * written.  16-byte aligned bases with pitches that are multiples of 4 floats (Z and, when given, dZ) get 16-byte lane accesses,
+ * everything else one float per lane; the summation order depends on c and that layout alone: not on n or the row's position, and two
+ * runs are bit-equal (no atomics), as are the outputs of a call that asks for fewer of them.  n = 0: nothing is done; c < 1 (or c > 2^30):
+ * SGL_ERR_INVALID.  Element offsets are 64-bit. */
+int sgl_class_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, int64_t c, const int64_t *d_labels, float w,
+                            float *d_dz, int64_t lddz, float *d_row_loss, int64_t *d_pred, void *stream);
 
 /* Per-column content signature of a DEVICE matrix: d_sig[c] = wrapping 64-bit sum over the rows r of mix(bits(X[r, c]), r), for
  * c < round_up(d, 4) (uint64 on device; rows 16-byte aligned, pitch a multiple of 4 floats covering round_up(d, 4)).  One streaming

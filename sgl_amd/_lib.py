@@ -151,6 +151,7 @@ PROTOTYPES = {
     "sgl_kmeans_assign_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "sgl_cluster_loss_grad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p, c_int64,
                                           c_void_p, c_void_p]),
+    "sgl_class_loss_grad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sgl_col_signature_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "sgl_content_hash": (c_int, [c_void_p, c_int64, POINTER(c_uint64)]),
 }

@@ -96,6 +96,10 @@ struct RowInstance {
     int lpr, ch, hmax;   // hmax: the even hop capacity of the compiled instance; 0 = the layout has none for this hop count
 };
 int pick_lpr(int64_t d, int vec);                                    // the smallest of 8 / 16 / 32 / 64 lanes that covers ceil(d / vec)
+struct ClassLossInstance {
+    int lpr, ch;         // lanes per row x vectors per lane; ch = 0: the streaming kernel (64 lanes)
+};
+ClassLossInstance class_loss_instance(int64_t c, int vec);           // sgl_class_loss_grad_f32's kernel for rows of c logits
 RowLayout row_layout(int64_t d, int n_hops, bool allow_8x5 = false);  // reads the tuning keys row_lpr32x2, row_narrow_groups
 RowInstance row_instance(int64_t d, int n_hops, bool allow_8x5 = false);
 int out_cols(int64_t d, int64_t pad, int64_t room);                  // columns a row kernel writes; reads row_whole_lines

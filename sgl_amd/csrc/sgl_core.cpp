@@ -132,6 +132,21 @@ int pick_lpr(int64_t d, int vec) {
     return lpr;
 }
 
+// The instance of class_loss_kernel (sgl_class_loss.hip) that serves rows of c logits read `vec` floats at a time: the narrowest lane
+// group that covers the row with one vector per lane; beyond 64 lanes the next compiled number of vectors per lane -- 2 / 4 of 16
+// bytes, 2 / 4 / 8 / 16 of one float, so both lane sizes keep rows of up to 1024 logits in at most 16 registers; beyond: ch = 0,
+// the streaming kernel.
+ClassLossInstance class_loss_instance(int64_t c, int vec) {
+    ClassLossInstance r;
+    r.lpr = pick_lpr(c, vec);
+    const int64_t chunks = (c + (int64_t)r.lpr * vec - 1) / ((int64_t)r.lpr * vec);
+    const int most = vec == 4 ? 4 : 16;
+    r.ch = 0;
+    for (int ch = 1; ch <= most && r.ch == 0; ch <<= 1)
+        if (chunks <= ch) r.ch = ch;
+    return r;
+}
+
 // A row of d floats is ceil(d / 4) 16-byte slots; LPR lanes take CH slots each (slot (c * LPR + l) of the row for lane l, chunk c),
 // 64 / LPR rows per wavefront.  Power-of-two groups leave slots idle when the row is not a power of two wide, and idle slots still
 // cost their share of every load and VALU instruction: d = 147 (BASELINE config 3: 100 features + 47 label columns = 37 slots) on
@@ -338,7 +353,7 @@ int build_plan(Plan &plan, const int64_t *rowptr, int64_t n_rows, int32_t item_n
 
 }  // namespace sgl
 
-SGL_EXPORT int sgl_version(void) { return 108; }
+SGL_EXPORT int sgl_version(void) { return 109; }
 
 SGL_EXPORT const char *sgl_last_error(void) { return sgl::get_error(); }
 

@@ -2019,6 +2019,52 @@ def cluster_loss_grad(x, centres, labels, w, dx=None, row_loss=None):
     return dx, row_loss
 
 
+def class_loss_grad(z, labels, w, dz=False, row_loss=False, pred=False):
+    """One launch of sgl_class_loss_grad_f32 over the logits z [n, c]: with lse_i = log sum_j exp(z[i, j]) (the row's maximum taken out
+    first) and y_i = labels[i] (int64 [n] on z's device), row i LIVE iff 0 <= y_i < c,
+    row_loss[i] = lse_i - z[i, y_i] (float32 [n]), dz[i] = w (softmax(z[i]) - onehot(y_i)), both 0 for a row that is not live, and
+    pred[i] = the lowest index of the row's maximum (int64 [n]; a NaN counts as the maximum, the first NaN wins).  z: a float32 CUDA
+    matrix read in place (padded buffers, column views).  dz / row_loss / pred: True allocates the output, a tensor is written in
+    place, None / False leaves it out; at least one is needed.  labels may be None when pred is the only output: no exp is evaluated
+    then.  Returns (dz, row_loss, pred).  No atomics: two runs are bit-equal.  Nothing here synchronises."""
+    _no_bf16("class_loss_grad", z, dz, row_loss)
+    _check_mat(z, "z")
+    n, c = z.shape
+    if c < 1:
+        raise ValueError("class_loss_grad: at least one class is needed")
+    dz = None if dz is False else dz
+    row_loss = None if row_loss is False else row_loss
+    pred = None if pred is False else pred
+    if dz is None and row_loss is None and pred is None:
+        raise ValueError("class_loss_grad: at least one of `dz`, `row_loss` and `pred` is needed")
+    if labels is None:
+        if dz is not None or row_loss is not None:
+            raise ValueError("class_loss_grad: `labels` may be None only when `pred` is the only output")
+    elif not (torch.is_tensor(labels) and labels.device == z.device and labels.dtype == torch.int64 and labels.dim() == 1
+              and labels.numel() == n and labels.is_contiguous()):
+        raise ValueError("class_loss_grad: `labels` must be a contiguous int64 [n] tensor on z's device")
+    if dz is True:
+        dz = alloc_rows(n, c, z.device)
+    elif dz is not None:
+        _check_mat(dz, "dz")
+        if dz.shape != z.shape or dz.device != z.device:
+            raise ValueError("class_loss_grad: `dz` must have z's shape and device")
+    if row_loss is True:
+        row_loss = torch.empty(n, dtype=torch.float32, device=z.device)
+    elif row_loss is not None and not (torch.is_tensor(row_loss) and row_loss.device == z.device and row_loss.dtype == torch.float32
+                                       and row_loss.dim() == 1 and row_loss.numel() == n and row_loss.is_contiguous()):
+        raise ValueError("class_loss_grad: `row_loss` must be a contiguous float32 [n] tensor on z's device")
+    if pred is True:
+        pred = torch.empty(n, dtype=torch.int64, device=z.device)
+    elif pred is not None and not (torch.is_tensor(pred) and pred.device == z.device and pred.dtype == torch.int64 and pred.dim() == 1
+                                   and pred.numel() == n and pred.is_contiguous()):
+        raise ValueError("class_loss_grad: `pred` must be a contiguous int64 [n] tensor on z's device")
+    _call(z.device, "sgl_class_loss_grad_f32", ptr(z), _ld(z), n, c, _opt_ptr(labels), float(w), _opt_ptr(dz),
+          _ld(dz) if dz is not None else 0, _opt_ptr(row_loss), _opt_ptr(pred))
+    _wrote(dz, row_loss, pred)
+    return dz, row_loss, pred
+
+
 def gather_rows(x, idx, out=None):
     """x[idx] on device (BaseSGAPModel.forward's per-step row gather, models/base_model.py:58,60).  `out`: optional
     preallocated [len(idx), d] destination (the pack step of the need-aware exchange re-uses one send buffer per hop).
