@@ -35,6 +35,8 @@
  *   sgl_edge_candidates        stored, as a search inside one CSR row; a seeded candidate stream with each pair's verdict.
  *   sgl_csr_select_rowptr,     the graph transforms of sgl/data/transforms.py (get_subgraph, drop_edges, random_drop_edges, remove_self_loops,
  *   sgl_csr_select_fill        ...): a canonical CSR filtered into a canonical CSR in two passes, no sort, no atomics.
+ *   sgl_csr_merge_rowptr,      the transforms that add entries (add_edges, add_self_loops of sgl/data/transforms.py; to_undirected of
+ *   sgl_csr_merge_fill         sgl/data/utils.py): the row-wise union of two canonical CSRs in two passes, no sort, no atomics.
  *   sgl_kmeans_assign_f32      the assignment step of the KMeans that NodeClusteringNAFS calls (sgl/tasks/node_clustering.py:254-255).
  *   sgl_cluster_loss_grad_f32  cluster_loss and its backward (sgl/tasks/utils.py:101-113; clustering_train, 116-136): per-row loss and dX in one pass.
  *   sgl_class_loss_grad_f32    nn.CrossEntropyLoss, its backward and accuracy's arg-max (train / evaluate, sgl/tasks/utils.py:12-98): per-row loss, dZ and the predicted class in one pass.
@@ -614,6 +616,45 @@ int sgl_csr_select_fill(const int64_t *d_rowptr, const int32_t *d_col, const flo
                         const uint8_t *d_entry_keep, int symmetric_mask, int drop_self, uint64_t drop_below, uint64_t seed,
                         int symmetric, int lanes, const int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val,
                         int64_t *d_out_pos, void *stream);
+
+/* The union of two canonical CSRs A and B of one shape (columns sorted and unique inside each row; not checked) as a new canonical
+ * CSR: the graph transforms that ADD entries -- add_edges (with del_repeated) and add_self_loops of sgl/data/transforms.py, and
+ * to_undirected (sgl/dataset/utils.py:11-17, sgl/data/utils.py:18) followed by the csr_matrix of Edge -- without the concatenated COO
+ * list and without a sort.  Two calls, shaped like the sgl_csr_select pair:
+ *
+ *   sgl_csr_merge_rowptr   counts the union of every row (len A + len B - common columns), scans the counts into d_out_rowptr
+ *                          [n_rows + 1] and returns the total in *h_nnz_out.  O(n_rows) scratch; SYNCHRONISES the stream.
+ *   sgl_csr_merge_fill     writes d_out_col, d_out_val and, when they are not NULL, d_out_pos_a and d_out_pos_b [total]: int64, the
+ *                          position of output entry o in A and in B, or -1 where that side does not store the column (to carry edge
+ *                          attributes along).  Stream-ordered, no synchronisation.  d_out_rowptr is what the first call wrote.
+ *
+ * Output row i holds the sorted union of the columns of row i of A and of row i of B, each once.  Values by `mode`:
+ *   SGL_MERGE_SUM     a column stored on both sides gets a + b: ONE IEEE float32 addition.  The entry stays when the sum is zero (the
+ *                     reference's csr_matrix((w, (row, col))) keeps it; scipy's A + B would drop it).
+ *   SGL_MERGE_KEEP_A  a column stored on both sides keeps A's 32 bits.
+ *   In both modes a column stored on one side only copies that side's 32 bits as they are: NaN payloads, -0.0 and explicit zeros
+ *   survive.
+ * NUMERICS against the reference: SUM is bit-equal to Edge(...).sparse_matrix of the concatenated lists wherever a pair occurs at
+ * most twice in the concatenation.  A pair that occurs three times or more differs: here it is a + (what B holds for it -- after
+ * sgl_coo_to_csr the storage-order float32 sum of the added duplicates), in scipy whatever order its unstable in-row sort leaves --
+ * the caveat sgl_coo_to_csr already carries.
+ * No sort, no atomics, no entry-sized temporary; the slot of every entry follows from its ranks in the two rows, so two runs are
+ * bit-equal and so are the compiled shapes, any grid and any stream.  lanes: the lanes that walk one row, 4, 16 or 64; 0 = chosen from
+ * max(nnz_a, nnz_b) / n_rows; anything else is refused.  n_rows < 2^31, n_cols <= INT32_MAX; entry positions and row pointers are
+ * int64.  nnz_a / nnz_b must be a_rowptr[n_rows] / b_rowptr[n_rows] (not checked here).  nnz_a == 0 or nnz_b == 0 is legal (the result
+ * is the other side; the pointers stay non-NULL), and so is n_rows == 0.  Negative sizes, NULL or misaligned pointers, a lanes or a
+ * mode outside the compiled set are refused before any launch.  The kernels never trap on the CONTENTS: a row's range is clamped
+ * into [0, nnz], a search reads inside one row, columns index nothing, and a fill never writes outside its output row -- a row that is
+ * not sorted and unique loses entries instead. */
+#define SGL_MERGE_SUM 0
+#define SGL_MERGE_KEEP_A 1
+int sgl_csr_merge_rowptr(const int64_t *a_rowptr, const int32_t *a_col, int64_t nnz_a, const int64_t *b_rowptr, const int32_t *b_col,
+                         int64_t nnz_b, int64_t n_rows, int64_t n_cols, int lanes, int64_t *d_out_rowptr, int64_t *h_nnz_out,
+                         void *stream);
+int sgl_csr_merge_fill(const int64_t *a_rowptr, const int32_t *a_col, const float *a_val, int64_t nnz_a, const int64_t *b_rowptr,
+                       const int32_t *b_col, const float *b_val, int64_t nnz_b, int64_t n_rows, int64_t n_cols, int mode, int lanes,
+                       const int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val, int64_t *d_out_pos_a, int64_t *d_out_pos_b,
+                       void *stream);
 
 /* The assignment step of k-means: labels[i] = argmin_j sum_c (X[i, c] - C[j, c])^2 (int64) and, when d_mindist is not NULL, that
  * minimum -- what KMeans.fit_predict spends its time on in NodeClusteringNAFS (sgl/tasks/node_clustering.py:254-255).  The distance is

@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SGL_HIP_LIB") or os.path.join(_HERE, "csrc", "libsgl_
 SGL_CSR_STRICT_ORDER = 0x1
 SGL_CSR_NO_XCD_REMAP = 0x2
 SGL_REDUCE_SUM, SGL_REDUCE_MEAN, SGL_REDUCE_MAX, SGL_REDUCE_MIN, SGL_REDUCE_WSUM = 0, 1, 2, 3, 4
+SGL_MERGE_SUM, SGL_MERGE_KEEP_A = 0, 1
 SGL_MAX_HOPS = 64
 SGL_ERR_UNSUPPORTED = 1003
 SGL_MEM_DEFAULT, SGL_MEM_CONTIGUOUS, SGL_MEM_VMM = 0, 1, 2
@@ -148,6 +149,10 @@ PROTOTYPES = {
                                       c_uint64, c_uint64, c_int, c_int, c_void_p, POINTER(c_int64), c_void_p]),
     "sgl_csr_select_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int,
                                     c_int, c_uint64, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sgl_csr_merge_rowptr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                                     POINTER(c_int64), c_void_p]),
+    "sgl_csr_merge_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sgl_kmeans_assign_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "sgl_cluster_loss_grad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p, c_int64,
                                           c_void_p, c_void_p]),

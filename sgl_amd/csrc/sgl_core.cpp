@@ -353,7 +353,7 @@ int build_plan(Plan &plan, const int64_t *rowptr, int64_t n_rows, int32_t item_n
 
 }  // namespace sgl
 
-SGL_EXPORT int sgl_version(void) { return 109; }
+SGL_EXPORT int sgl_version(void) { return 110; }
 
 SGL_EXPORT const char *sgl_last_error(void) { return sgl::get_error(); }
 

@@ -1960,6 +1960,58 @@ def csr_select(adj, row_map=None, col_map=None, n_rows_out=None, n_cols_out=None
     return (out, out_pos[:m]) if positions else out
 
 
+CSR_MERGE_LANES = (4, 16, 64)        # the compiled lanes-per-row instances of csr_merge_kernel (sgl_csr_merge.hip)
+CSR_MERGE_MODES = {"sum": _lib.SGL_MERGE_SUM, "keep": _lib.SGL_MERGE_KEEP_A}
+
+
+def csr_merge(a, b, mode="sum", lanes=0, positions=False):
+    """The row-wise union of two canonical device CSRs of one shape as a new one (sgl_csr_merge_rowptr + sgl_csr_merge_fill;
+    include/sgl_hip.h states the contract): every column stored in row i of `a` or of `b`, once, ascending.  A column stored on both
+    sides gets a + b (one float32 addition; a zero sum stays stored) under mode="sum" and a's value under mode="keep"; a column
+    stored on one side keeps that side's bits.  Returns a DeviceAdjacency and, with positions=True, also (pos_a, pos_b): the int64
+    position of every output entry in `a` and in `b`, -1 where that side does not store it.  lanes: 0 = auto, or one of
+    CSR_MERGE_LANES.  The first call synchronises the stream (the size of the result comes back through the host)."""
+    from .io import DeviceAdjacency
+    rowptr_a, col_a = _csr_arrays(a, "csr_merge")
+    rowptr_b, col_b = _csr_arrays(b, "csr_merge")
+    dv = rowptr_a.device
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"csr_merge: the shapes differ: {tuple(a.shape)} and {tuple(b.shape)}")
+    if rowptr_b.device != dv:
+        raise ValueError("csr_merge: a and b must live on one device")
+    n_rows, n_cols = a.shape
+    if mode not in CSR_MERGE_MODES:
+        raise ValueError(f"csr_merge: mode must be one of {tuple(CSR_MERGE_MODES)}, not {mode!r}")
+    lanes = int(lanes)
+    if lanes != 0 and lanes not in CSR_MERGE_LANES:
+        raise ValueError(f"csr_merge: lanes must be 0 (auto) or one of {CSR_MERGE_LANES}, not {lanes}")
+    sides = []
+    for name, adj, rowptr, col in (("a", a, rowptr_a, col_a), ("b", b, rowptr_b, col_b)):
+        val = adj.val
+        nnz = int(adj.col.numel())
+        if not (torch.is_tensor(val) and val.device == dv and val.dtype == torch.float32 and val.is_contiguous() and val.numel() == nnz):
+            raise TypeError(f"csr_merge: {name}.val must be a contiguous float32 tensor of nnz values on the device of a.rowptr")
+        if n_rows > 0 and int(rowptr[-1]) != nnz:
+            raise ValueError(f"csr_merge: {name}.rowptr ends at {int(rowptr[-1])}, {name}.col holds {nnz} entries")
+        if nnz == 0:
+            col, val = torch.zeros(1, dtype=torch.int32, device=dv), torch.zeros(1, dtype=torch.float32, device=dv)
+        sides.append((rowptr, col, val, nnz))
+    (ra, ca, va, na), (rb, cb, vb, nb) = sides
+    out_rowptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dv)
+    total = c_int64(0)
+    _call(dv, "sgl_csr_merge_rowptr", ptr(ra), ptr(ca), na, ptr(rb), ptr(cb), nb, n_rows, n_cols, lanes, ptr(out_rowptr), ctypes.byref(total))
+    m = total.value
+    out_col = torch.empty(max(m, 1), dtype=torch.int32, device=dv)
+    out_val = torch.empty(max(m, 1), dtype=torch.float32, device=dv)
+    pos_a = torch.empty(max(m, 1), dtype=torch.int64, device=dv) if positions else None
+    pos_b = torch.empty(max(m, 1), dtype=torch.int64, device=dv) if positions else None
+    _call(dv, "sgl_csr_merge_fill", ptr(ra), ptr(ca), ptr(va), na, ptr(rb), ptr(cb), ptr(vb), nb, n_rows, n_cols, CSR_MERGE_MODES[mode], lanes,
+          ptr(out_rowptr), ptr(out_col), ptr(out_val), _opt_ptr(pos_a), _opt_ptr(pos_b))
+    _wrote(out_rowptr, out_col, out_val, pos_a, pos_b)
+    out = DeviceAdjacency(out_rowptr, out_col[:m], out_val[:m], (n_rows, n_cols))
+    return (out, (pos_a[:m], pos_b[:m])) if positions else out
+
+
 def kmeans_assign(x, centres, want_dist=True):
     """(labels, mindist) of the k-means assignment step (sgl_kmeans_assign_f32): labels[i] = argmin_j |x[i] - centres[j]|^2 (int64 [n],
     the lowest index on a tie) and that minimum (float32 [n]; None with want_dist=False) -- the direct sum of squared differences, not

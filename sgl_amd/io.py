@@ -72,9 +72,14 @@ def coo_to_csr_device(row, col, data, num_node, device="cuda", num_col=None):
     return DeviceAdjacency(out_ptr, out_col[:m].clone(), out_val[:m].clone(), (num_node, num_col))
 
 
-def load_custom_homo_raw(raw_dir, num_node=0, device="cuda"):
+def load_custom_homo_raw(raw_dir, num_node=0, device="cuda", undirected=None):
     """Read the Custom_Homo raw files and build the adjacency on the device.
-    Returns dict(adj=DeviceAdjacency, x=ndarray|None, y=LongTensor|None, train_idx, val_idx, test_idx)."""
+    Returns dict(adj=DeviceAdjacency, x=ndarray|None, y=LongTensor|None, train_idx, val_idx, test_idx).
+    undirected: None keeps the edge list as it is stored; "sum" / "keep" symmetrise it on the device (transforms.to_undirected: "sum"
+    is what the reference's loaders do to a directed dump before they build the Edge)."""
+    if undirected not in (None, "sum", "keep"):
+        raise ValueError('undirected must be None, "sum" or "keep"')
+
     def have(f):
         return os.path.exists(os.path.join(raw_dir, f))
 
@@ -90,6 +95,9 @@ def load_custom_homo_raw(raw_dir, num_node=0, device="cuda"):
         raise ValueError('the adjacency matrix in coo-format is necessary')
     f = np.load(os.path.join(raw_dir, "adj_matrix.npz"))
     adj = coo_to_csr_device(f["row"], f["col"], f["data"], num_node, device=device)
+    if undirected is not None:
+        from .transforms import to_undirected
+        adj = to_undirected(adj, reduce=undirected)
     y = None
     if have("label.npy"):
         lab = np.load(os.path.join(raw_dir, "label.npy"))

@@ -15,7 +15,16 @@ Deliberate differences from the reference under force_undirected (INTEGRATION.md
   * the decision is taken per unordered pair and every stored direction keeps its OWN value; the reference keeps the upper triangle
     and mirrors it, which also invents a lower entry for an upper entry whose mirror was never stored (here there is none);
   * a kept self-loop keeps its value; the reference stores it twice and csr_matrix sums the two.
-On a symmetric matrix with a zero diagonal the results are identical."""
+On a symmetric matrix with a zero diagonal the results are identical.
+
+The transforms that ADD entries -- add_edges, add_self_loops, and to_undirected of the reference's sgl/data/utils.py -- are the
+row-wise union of two canonical CSRs (device.csr_merge -> sgl_csr_merge_rowptr / sgl_csr_merge_fill): a merge of
+sorted rows, no sort of the entries already stored.  Under SUM the result is bit-equal to the reference's csr_matrix of the
+concatenated lists wherever a pair occurs at most twice in the concatenation; a pair that occurs three times or more is the stored
+value plus the storage-order float32 sum of the added duplicates, where scipy adds in whatever order its unstable in-row sort leaves.
+Deliberate difference under add_edges(del_repeated=True): the reference keeps whichever duplicate its unstable argsort puts first;
+here the STORED value always wins, and among duplicates of the added list their storage-order sum stands.
+delete_repeated_edges and sort_edges are not ported: a DeviceAdjacency is canonical by construction (rows sorted, pairs unique)."""
 from collections import namedtuple
 from fractions import Fraction
 
@@ -26,7 +35,7 @@ from . import device as dev
 from .io import DeviceAdjacency
 
 __all__ = ["Subgraph", "get_subgraph", "random_drop_nodes", "drop_edges", "biased_drop_edges", "random_drop_edges", "remove_self_loops",
-           "mask_features", "drop_threshold", "node_keep_mask"]
+           "mask_features", "drop_threshold", "node_keep_mask", "add_edges", "add_self_loops", "to_undirected"]
 
 Subgraph = namedtuple("Subgraph", ["adj", "x", "y", "node_ids"])      # node_ids: int64, the old ids of the kept nodes, ascending
 
@@ -34,6 +43,9 @@ EDGE_DROP_STREAM, NODE_DROP_STREAM = 103, 104
 _P_MESSAGE = "Dropout probability has to be between 0 and 1!"
 _NODE_MASK_MESSAGE = "the shape of node mask is wrong!"
 _EDGE_MASK_MESSAGE = "the shape of edge drop mask is wrong!"
+_ADD_SHAPE_MESSAGE = "add indices must be in shape of (2, x)!"
+_ADD_RANGE_MESSAGE = "indices must be in range of [0, num_node)!"
+_SELF_LOOP_MESSAGE = "add weights must be in shape of [num_node]!"
 
 
 def drop_threshold(p):
@@ -163,6 +175,92 @@ def random_drop_edges(adj, p=0.5, force_undirected=True, seed=0):
 def remove_self_loops(adj):
     """Without the stored diagonal entries."""
     return dev.csr_select(_adjacency(adj), drop_self=True)
+
+
+def _add_list(add_indices, add_weights, shape):
+    """the [2, x] index pairs as an integer tensor and the weights as a float32 [x] tensor (ones when None), wherever they live;
+    the reference's checks and messages"""
+    idx = add_indices if torch.is_tensor(add_indices) else torch.from_numpy(np.asarray(add_indices))
+    if idx.dim() != 2 or idx.shape[0] != 2:
+        raise ValueError(_ADD_SHAPE_MESSAGE)
+    x = int(idx.shape[1])
+    if x == 0:
+        return idx, None
+    if idx.dtype.is_floating_point or idx.dtype == torch.bool:
+        raise ValueError("add_edges: add indices must be integers")
+    lo, hi = torch.aminmax(idx, dim=1)             # one reduction per side
+    lo, hi = lo.tolist(), hi.tolist()
+    if hi[0] >= shape[0] or hi[1] >= shape[1] or lo[0] < 0 or lo[1] < 0:
+        raise ValueError(_ADD_RANGE_MESSAGE)
+    if add_weights is not None:
+        w = add_weights if torch.is_tensor(add_weights) else torch.from_numpy(np.asarray(add_weights))
+        if w.dim() != 1 or w.shape[0] != x:
+            raise ValueError("add_edges: add weights must be in shape of [x]")
+        add_weights = w.to(torch.float32)
+    return idx, add_weights
+
+
+@torch.no_grad()
+def add_edges(adj, add_indices, add_weights=None, del_repeated=False):
+    """The entries of `adj` and the pairs add_indices [2, x] (tensor, array or list, on the host or the device; weights default to
+    ones) as one canonical adjacency.  The added list goes through the ingest (io.coo_to_csr_device: a pair repeated inside the list
+    is summed in storage order) and is merged with `adj` by device.csr_merge: a pair that `adj` stores too gets the sum of the two
+    values (del_repeated=False; a zero sum stays stored, as in the reference's csr_matrix) or keeps the stored value
+    (del_repeated=True).  An empty list returns the input object."""
+    shape = adj.shape
+    idx, w = _add_list(add_indices, add_weights, shape)
+    if idx.shape[1] == 0:
+        return adj
+    adj = _adjacency(adj)
+    dv = adj.device
+    if w is None:
+        w = torch.ones(idx.shape[1], dtype=torch.float32, device=dv)
+    from .io import coo_to_csr_device
+    added = coo_to_csr_device(idx[0], idx[1], w, shape[0], device=dv, num_col=shape[1])
+    return dev.csr_merge(adj, added, mode="keep" if del_repeated else "sum")
+
+
+@torch.no_grad()
+def add_self_loops(adj, add_weights=None):
+    """`adj` plus the diagonal: add_weights [num_node] (ones when None) is ADDED to a stored diagonal entry and stored where there
+    was none -- a 0.0 in add_weights becomes a stored zero, as in the reference.  The diagonal is a canonical CSR as it stands, so
+    nothing is ingested."""
+    n = adj.shape[0]
+    if adj.shape[1] != n:
+        raise ValueError("add_self_loops: the adjacency must be square")
+    if add_weights is not None:
+        if not torch.is_tensor(add_weights):
+            add_weights = torch.from_numpy(np.asarray(add_weights))
+        if add_weights.dim() != 1 or add_weights.shape[0] != n:
+            raise ValueError(_SELF_LOOP_MESSAGE)
+    if n == 0:
+        return adj
+    adj = _adjacency(adj)
+    dv = adj.device
+    w = torch.ones(n, dtype=torch.float32, device=dv) if add_weights is None else add_weights.to(device=dv, dtype=torch.float32).contiguous()
+    eye = DeviceAdjacency(torch.arange(n + 1, dtype=torch.int64, device=dv), torch.arange(n, dtype=torch.int32, device=dv), w, (n, n))
+    return dev.csr_merge(adj, eye, mode="sum")
+
+
+@torch.no_grad()
+def to_undirected(adj, reduce="sum"):
+    """`adj` merged with its transpose (built as PreparedAdjacency.normalize builds it: rows and columns swapped through the ingest).
+    reduce="sum" is the reference -- its loaders stack the list with its mirror and Edge's csr_matrix sums: a pair stored both ways
+    and every diagonal entry come out DOUBLED (the weight 2.0 of dataset/ogbn.py:45).  reduce="keep" leaves every stored value as it
+    is and fills in only the missing direction."""
+    if reduce not in ("sum", "keep"):
+        raise ValueError('to_undirected: reduce must be "sum" or "keep"')
+    n = adj.shape[0]
+    if adj.shape[1] != n:
+        raise ValueError("to_undirected: the adjacency must be square")
+    adj = _adjacency(adj)
+    if adj.nnz == 0:
+        return adj
+    from .io import coo_to_csr_device
+    dv = adj.device
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dv), adj.rowptr[1:] - adj.rowptr[:-1])
+    mirror = coo_to_csr_device(adj.col.to(torch.int64), rows, adj.val, n, device=dv)
+    return dev.csr_merge(adj, mirror, mode=reduce)
 
 
 @torch.no_grad()
