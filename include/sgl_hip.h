@@ -78,7 +78,10 @@ extern "C" {
 int sgl_version(void);                /* 10000*major + 100*minor + patch */
 const char *sgl_last_error(void);     /* thread-local, never NULL */
 int sgl_device_count(int *count);     /* 0 and *count = 0 when there is no GPU: never aborts */
-/* integer tuning knobs for experiments ("spmm_unroll", "spmm_nt", "spmm_group", ...); unknown key -> SGL_ERR_INVALID */
+/* integer tuning knobs for experiments ("spmm_unroll", "spmm_nt", "spmm_group", ...); unknown key -> SGL_ERR_INVALID.
+ * Two of them exist for tests and change no result: "agg_blocks" > 0 caps the grid of the streaming aggregators, "loss_blocks" > 0 the
+ * grid of sgl_kmeans_assign_f32, sgl_cluster_loss_grad_f32, sgl_class_loss_grad_f32 and the fold of sgl_edge_loss_grad_f32, so that
+ * the workgroups stride over the work as they do at sizes beyond the kernels' own caps; 0 (default) = those caps */
 int sgl_set_tuning(const char *key, int64_t value);
 int sgl_get_tuning(const char *key, int64_t *value);
 

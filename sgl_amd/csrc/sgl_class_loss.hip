@@ -257,7 +257,7 @@ void launch_rows(hipStream_t st, const float *d_z, int64_t ldz, int64_t n, int c
     constexpr int U = rows_per_group(VEC, CH);
     const int64_t per_batch = (int64_t)(256 / LPR) * U;
     const int64_t n_batches = (n + per_batch - 1) / per_batch;
-    const int64_t blocks = n_batches < kMaxBlocks ? n_batches : kMaxBlocks;
+    const int64_t blocks = sgl::loss_grid(n_batches, kMaxBlocks);
     hipLaunchKernelGGL((class_loss_kernel<LPR, VEC, CH, U>), dim3((unsigned)blocks), dim3(256), 0, st, d_z, ldz, n, c, d_labels, w, d_dz, lddz,
                        d_row_loss, d_pred, n_batches);
 }
@@ -292,7 +292,7 @@ SGL_EXPORT int sgl_class_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n,
 #undef SGL_CLASS_LOSS_ARGS
     if (!launched) {
         if (in.ch != 0) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: no kernel instance is compiled for %d lanes x %d chunks", who, in.lpr, in.ch);
-        const int64_t blocks = (n + 3) / 4 < kMaxBlocks ? (n + 3) / 4 : kMaxBlocks;
+        const int64_t blocks = sgl::loss_grid((n + 3) / 4, kMaxBlocks);
         with_vec(vec4, [&](auto V) {
             hipLaunchKernelGGL((class_loss_stream_kernel<V>), dim3((unsigned)blocks), dim3(256), 0, st, d_z, ldz, n, ci, d_labels, w, d_dz, lddz,
                                d_row_loss, d_pred);

@@ -280,7 +280,7 @@ void launch_loss(hipStream_t st, const float *d_x, int64_t ldx, int64_t n, int d
     const int tile_k = k <= kTileFloats / dp ? k : kTileFloats / dp / kStep * kStep;   // whole steps per tile: a centre's slot is j % T
     const int64_t per_batch = (int64_t)(256 / LPR) * U;
     const int64_t n_batches = (n + per_batch - 1) / per_batch;
-    const int64_t blocks = n_batches < kMaxBlocks ? n_batches : kMaxBlocks;
+    const int64_t blocks = sgl::loss_grid(n_batches, kMaxBlocks);
     hipLaunchKernelGGL((cluster_loss_kernel<LPR, VEC, CH, U>), dim3((unsigned)blocks), dim3(256), (size_t)tile_k * dp * sizeof(float), st, d_x,
                        ldx, n, d, d_c, ldc, k, tile_k, dp, n_batches, d_labels, inv_k, w, d_dx, lddx, d_row_loss);
 }
@@ -324,7 +324,7 @@ SGL_EXPORT int sgl_cluster_loss_grad_f32(const float *d_x, int64_t ldx, int64_t 
     }
 #undef SGL_CLUSTER_LOSS_ARGS
     if (!launched) {
-        const int64_t blocks = (n + 3) / 4 < kMaxBlocks ? (n + 3) / 4 : kMaxBlocks;
+        const int64_t blocks = sgl::loss_grid((n + 3) / 4, kMaxBlocks);
         with_vec(vec4, [&](auto V) {
             hipLaunchKernelGGL((cluster_loss_stream_kernel<V>), dim3((unsigned)blocks), dim3(256), 0, st, d_x, ldx, n, di, d_centres, ldc, ki,
                                d_labels, inv_k, w, d_dx, lddx, d_row_loss);

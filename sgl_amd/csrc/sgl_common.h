@@ -69,6 +69,14 @@ int build_plan(Plan &plan, const int64_t *rowptr, int64_t n_rows, int32_t item_n
 // tuning knobs (sgl_set_tuning)
 int64_t tuning(const char *key, int64_t dflt);
 
+// grid of a loss-kernel launch (K9, K11's fold, K12, K14) that strides over `wanted` blocks of work: the kernel's own cap, or the
+// tuning key loss_blocks where it is > 0 -- the tests' way to the strided form at small sizes; read once per launch
+inline int64_t loss_grid(int64_t wanted, int64_t cap) {
+    const int64_t forced = tuning("loss_blocks", 0);
+    if (forced > 0 && forced < cap) cap = forced;
+    return wanted < cap ? wanted : cap;
+}
+
 // what sgl_csr_create takes for item_nnz <= 0 / long_row_nnz == 0: functions of the matrix's nnz only (sgl_core.cpp)
 int32_t default_item_nnz(int64_t nnz);
 int32_t default_long_row_nnz(int64_t nnz);

@@ -34,6 +34,7 @@ static std::map<std::string, int64_t> &tune_map() {
         {"spmm_xcd_remap", 1},   // contiguous row ranges per XCD
         {"spmm_heavy_first", 1}, // plan time: work items that end in a heavy row are issued first inside every XCD range
         {"agg_blocks", 0},       // 0 = one 16-byte element per thread (grid capped at 2^22 blocks); > 0 caps the grid of the streaming aggregators (grid-stride)
+        {"loss_blocks", 0},      // 0 = each kernel's own cap; > 0 caps the grid of the k-means / cluster-loss / class-loss kernels and the edge-loss fold (grid-stride)
         {"nafs_fused", 1},       // 0 = force the two-pass NAFS path
         {"row_lpr32x2", 1},      // row-wise kernels, 128 < d <= 256: 32 lanes x 2 chunks per row (2 rows per wavefront)
         {"row_whole_lines", 1},    // gate / NAFS / concat outputs: the pad columns of a row pitch (< one line beyond d) are written as zeros

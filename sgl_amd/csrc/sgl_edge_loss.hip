@@ -363,7 +363,7 @@ SGL_EXPORT int sgl_edge_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, 
         SGL_LAUNCH_CHECK(who);
     }
     if (n_fold > 0) {
-        const int64_t blocks = (n_fold + 3) / 4 < kMaxFoldBlocks ? (n_fold + 3) / 4 : kMaxFoldBlocks;
+        const int64_t blocks = sgl::loss_grid((n_fold + 3) / 4, kMaxFoldBlocks);
         hipLaunchKernelGGL(edge_fold_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_fold, n_fold, d_partial, ldp, (int)d, d_dz, lddz);
         SGL_LAUNCH_CHECK(who);
     }

@@ -205,7 +205,7 @@ void launch_assign(hipStream_t st, const float *d_x, int64_t ldx, int64_t n, int
     const int tile_k = k < kTileFloats / dp ? k : kTileFloats / dp;
     const int64_t per_batch = (int64_t)(256 / LPR) * U;
     const int64_t n_batches = (n + per_batch - 1) / per_batch;
-    const int64_t blocks = n_batches < kMaxBlocks ? n_batches : kMaxBlocks;
+    const int64_t blocks = sgl::loss_grid(n_batches, kMaxBlocks);
     hipLaunchKernelGGL((kmeans_assign_kernel<LPR, VEC, CH, U>), dim3((unsigned)blocks), dim3(256), (size_t)tile_k * dp * sizeof(float), st,
                        d_x, ldx, n, d, d_c, ldc, k, tile_k, dp, n_batches, d_labels, d_mindist);
 }
@@ -244,7 +244,7 @@ SGL_EXPORT int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, i
         launched = with_one_of<2, 4, 8, 16, 32>(ch, [&](auto C) { launch_assign<64, 1, C>(st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, d_mindist); });
     }
     if (!launched) {
-        const int64_t blocks = (n + 3) / 4 < kMaxBlocks ? (n + 3) / 4 : kMaxBlocks;
+        const int64_t blocks = sgl::loss_grid((n + 3) / 4, kMaxBlocks);
         with_vec(vec4, [&](auto V) {
             hipLaunchKernelGGL((kmeans_assign_stream_kernel<V>), dim3((unsigned)blocks), dim3(256), 0, st, d_x, ldx, n, di, d_centres, ldc, ki,
                                d_labels, d_mindist);

@@ -32,17 +32,17 @@ def cases():
 _IN, _REF = {}, {}
 
 
-def inputs(d, k, shift=0.0):
-    """(x [N_ROWS, d], centres [k, d], labels int64 [N_ROWS]): kmeans_common's matrices, the first min(3, k) centres overwritten with
+def inputs(d, k, shift=0.0, n=N_ROWS):
+    """(x [n, d], centres [k, d], labels int64 [n]): kmeans_common's matrices, the first min(3, k) centres overwritten with
     exact copies of seeded rows, labels from a seeded rng; shift: added to every column of x and of the centres IN FLOAT32 (the
     shifted float32 matrices are the inputs of that test: its references are recomputed from them)"""
-    key = (d, k, shift)
+    key = (d, k, shift, n)
     if key not in _IN:
         rng = np.random.default_rng(90000 + 131 * d + k)
-        x, c = host_x(d).copy(), host_centres(d, k).copy()
-        rows = rng.choice(N_ROWS, min(ZERO_CENTRES, k), replace=False)
+        x, c = host_x(d, n).copy(), host_centres(d, k, n).copy()
+        rows = rng.choice(n, min(ZERO_CENTRES, k), replace=False)
         c[:len(rows)] = x[rows]
-        y = rng.integers(0, k, N_ROWS).astype(np.int64)
+        y = rng.integers(0, k, n).astype(np.int64)
         if shift:
             x, c = (x + np.float32(shift)).astype(np.float32), (c + np.float32(shift)).astype(np.float32)
         _IN[key] = (x, c, y)
