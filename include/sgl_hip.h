@@ -51,7 +51,13 @@
  *   - pointers named d_* are DEVICE pointers owned by the caller (e.g. torch tensor data_ptr()); pointers named
  *     h_* are HOST pointers.  The library owns only what it allocates inside handles.
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  Calls are stream-ordered and do not
- *     synchronise the device unless documented.
+ *     synchronise the device unless documented.  Two kinds of wait are documented, entry point by entry point: "synchronises
+ *     `stream`" (the call returns when its own stream has drained; other streams are not waited for) and "synchronises the
+ *     DEVICE" (the call releases device temporaries with hipFree before it returns, and hipFree waits for every stream of the
+ *     device, the default stream included: sgl_coo_to_csr, sgl_csr_select_rowptr, sgl_csr_merge_rowptr, sgl_csr_permute_rows,
+ *     sgl_csr_set_rowmap, sgl_reorder_community, sgl_reorder_lpa_round without a counter, sgl_norm_prepare, sgl_norm_block_prepare,
+ *     sgl_norm_execute, sgl_norm_execute_lr, sgl_norm_block_build, sgl_norm_build_symcheck -- all of them plan-time calls, none on
+ *     the hop loop).
  *   - matrices are row-major float32 with an explicit leading dimension (elements).  Column indices are int32,
  *     row pointers int64, all element offsets are computed in 64 bits (the reference overflows `int` at
  *     N*d >= 2^31, matmul.c:29,33).
@@ -238,14 +244,15 @@ int sgl_download(void *h_dst, const void *d_src, int64_t bytes, void *stream);
  * round, all in the last -- followed by a stable sort of the nodes by label.  Deterministic.  h_info (optional, host):
  * [0] number of communities, [1] nodes that changed label in the last round.  Runs once per adjacency (tens of ms at
  * ogbn-products size); the caller relabels the problem (sgl_coo_to_csr on the relabelled COO) and permutes features / results.
- * Synchronises the stream. */
+ * Synchronises the stream; its temporaries are freed on return, so it synchronises the DEVICE. */
 int sgl_reorder_community(const int64_t *d_rowptr, const int32_t *d_col, int64_t n, int rounds, int64_t *d_order,
                           int64_t *h_info, void *stream);
 /* One round of that label propagation over a ROW BLOCK of a row-sharded matrix (rows [row0, row0 + n_local): local row pointers,
  * GLOBAL column ids): d_labels = the current labels of all n_global nodes (int32), d_out = the new labels of the block's nodes
  * (int32 [n_local]), *d_moved (optional, a zeroed 64-bit device word) += nodes whose label changed.  The caller all-gathers the
  * ranks' slices between rounds and passes last != 0 in the final round; the stable sort by label is the caller's.  Running it over
- * the blocks of a partition reproduces sgl_reorder_community's labels exactly (sgl_amd/dist/redistribute.py). */
+ * the blocks of a partition reproduces sgl_reorder_community's labels exactly (sgl_amd/dist/redistribute.py).  With d_moved the
+ * call is stream-ordered and does not wait; without it a scratch counter is freed on return and the call synchronises the DEVICE. */
 int sgl_reorder_lpa_round(const int64_t *d_rowptr, const int32_t *d_col, int64_t n_local, int64_t row0, int64_t n_global,
                           const int32_t *d_labels, int32_t *d_out, int round, int last, uint64_t *d_moved, void *stream);
 
@@ -254,12 +261,14 @@ int sgl_reorder_lpa_round(const int64_t *d_rowptr, const int32_t *d_col, int64_t
  * given the same array as its row map computes bit for bit the products of the original matrix -- X and Y keep the caller's node
  * order, only the order in which rows are processed (and with it the reuse of gathered rows in L2 / the Infinity Cache) changes.
  * With any of d_col / d_val / d_out_col / d_out_val NULL only d_out_rowptr is written.  n = 0: d_perm may be NULL.  d_perm is not
- * validated here (sgl_csr_set_rowmap validates the same array). */
+ * validated here (sgl_csr_set_rowmap validates the same array).  The temporaries are freed on return: this call synchronises
+ * the DEVICE. */
 int sgl_csr_permute_rows(const int64_t *d_rowptr, const int32_t *d_col, const float *d_val, int64_t n, const int32_t *d_perm,
                          int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val, void *stream);
 /* Storage row i of the handle is output row d_rowmap[i] (a permutation of 0..n_rows-1; NULL removes the map; the array must
  * outlive its use).  Applies to sgl_spmm_f32 / _chain / _acc / _axpb_clamp (outputs, residual and running aggregate are addressed
- * through the map); sgl_spmm_multi_f32 refuses a mapped handle. */
+ * through the map); sgl_spmm_multi_f32 refuses a mapped handle.  The map is validated on the device and the entries of split
+ * rows are read back; the scratch of the validation is freed on return: this call synchronises the DEVICE. */
 int sgl_csr_set_rowmap(sgl_csr_t *csr, const int32_t *d_rowmap, void *stream);
 
 /* ---- multi-GPU exchange (row-sharded layout): the all-gather of the feature block between hops ---------------- */
@@ -310,7 +319,8 @@ int sgl_shim_cache_stats(int64_t *hits, int64_t *misses);
  * zero of A, a_ii = -1, a degree of 0 whose inf factor is replaced by 0) is kept as a stored 0.0, where scipy -- the reference
  * -- stores nothing.  Values agree; 0 * inf = NaN reaches an SpMM output row only through such a stored zero.  The Python layer
  * (sgl_amd.device) drops the entries whose fp64 value is exactly 0 and so returns the reference's pattern; a C caller that feeds
- * such weights and needs it does the same with d_out_val64. */
+ * such weights and needs it does the same with d_out_val64.
+ * sgl_norm_prepare, sgl_norm_execute and sgl_norm_execute_lr free their temporaries on return: each of them synchronises the DEVICE. */
 int sgl_norm_prepare(int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_col, int64_t *nnz_out,
                      void *stream);
 int sgl_norm_execute(int64_t n, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_col, const float *d_val,
@@ -335,7 +345,9 @@ int sgl_norm_execute_lr(int64_t n, int64_t nnz, const int64_t *d_rowptr, const i
  *      (sgl_norm_block_colsum accumulates a block's share into a zeroed [n_cols] vector; all-reduce over the ranks)
  *   4. sgl_norm_block_scale   -> A_hat[j, i] = (T'[j, i] * L[j]) * R[i]  [then (1-alpha) A_hat + alpha I], rounded to fp32;
  *      d_left_local = deg^(r-1) of the block's rows, d_right_global = deg^(-r) of ALL n_cols nodes.
- * Same arithmetic and rounding as sgl_norm_execute; none of it needs the other ranks' rows. */
+ * Same arithmetic and rounding as sgl_norm_execute; none of it needs the other ranks' rows.
+ * sgl_norm_block_prepare, sgl_norm_block_build and sgl_norm_build_symcheck free their temporaries on return: each of them
+ * synchronises the DEVICE; the other sgl_norm_block_* calls are stream-ordered and do not wait. */
 int sgl_norm_block_prepare(int64_t n, int64_t row0, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_col,
                            int64_t *nnz_out, void *stream);
 int sgl_norm_block_build(int64_t n, int64_t row0, int64_t nnz, const int64_t *d_rowptr, const int32_t *d_col,
@@ -376,7 +388,8 @@ int sgl_norm_degree_powers(int64_t n, const double *d_deg, double r, double *d_l
  * structure of scipy's csr_matrix((data,(row,col))) everywhere (a sum that cancels to zero stays an entry) and its value
  * bits wherever a pair is stored at most twice -- scipy sorts a row with an unstable sort before it folds, so a pair stored
  * three times or more may be added in another order there.  Outputs: d_out_rowptr [n_rows+1]; d_out_col / d_out_val sized for nnz
- * entries, the first *h_nnz_out of them are valid.  Synchronises `stream`.  Fails on an out-of-range index. */
+ * entries, the first *h_nnz_out of them are valid.  Synchronises `stream`; the temporaries are freed on return, so the call
+ * synchronises the DEVICE.  Fails on an out-of-range index. */
 int sgl_coo_to_csr(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t *d_row, const int64_t *d_col,
                    const float *d_val, int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val, int64_t *h_nnz_out,
                    void *stream);
@@ -587,7 +600,7 @@ int sgl_edge_candidates(const int64_t *d_rowptr, const int32_t *d_col, int64_t n
  * the COO edge list, the boolean index and the new csr_matrix.  Two calls, because the size of the result is not known beforehand:
  *
  *   sgl_csr_select_rowptr   counts the kept entries of every output row, scans the counts into d_out_rowptr [n_rows_out + 1] and returns
- *                           the total in *h_nnz_out.  It allocates O(n_rows_out) scratch and SYNCHRONISES the stream, like sgl_coo_to_csr.
+ *                           the total in *h_nnz_out.  It allocates O(n_rows_out) scratch, frees it on return and so synchronises the DEVICE, like sgl_coo_to_csr.
  *   sgl_csr_select_fill     writes d_out_col, d_out_val and, when it is not NULL, d_out_pos [total]: int64, the position in the SOURCE of
  *                           every kept entry (to carry edge attributes along).  Stream-ordered, no synchronisation.  d_out_rowptr is
  *                           what the first call wrote; the outputs hold exactly *h_nnz_out entries (non-NULL pointers even when that is 0).
@@ -626,7 +639,7 @@ int sgl_csr_select_fill(const int64_t *d_rowptr, const int32_t *d_col, const flo
  * list and without a sort.  Two calls, shaped like the sgl_csr_select pair:
  *
  *   sgl_csr_merge_rowptr   counts the union of every row (len A + len B - common columns), scans the counts into d_out_rowptr
- *                          [n_rows + 1] and returns the total in *h_nnz_out.  O(n_rows) scratch; SYNCHRONISES the stream.
+ *                          [n_rows + 1] and returns the total in *h_nnz_out.  O(n_rows) scratch, freed on return: synchronises the DEVICE.
  *   sgl_csr_merge_fill     writes d_out_col, d_out_val and, when they are not NULL, d_out_pos_a and d_out_pos_b [total]: int64, the
  *                          position of output entry o in A and in B, or -1 where that side does not store the column (to carry edge
  *                          attributes along).  Stream-ordered, no synchronisation.  d_out_rowptr is what the first call wrote.

@@ -1898,7 +1898,7 @@ def csr_select(adj, row_map=None, col_map=None, n_rows_out=None, n_cols_out=None
     flag of the pair's upper entry decides both directions), not (drop_self and i == j), and h(seed, 103, i, j) >= drop_below (with
     symmetric: h of (min, max)).  Returns a DeviceAdjacency of shape (n_rows_out, n_cols_out) -- defaults: adj's when the map is None --
     and, with positions=True, also the int64 position in adj of every kept entry.  lanes: 0 = auto, or one of CSR_SELECT_LANES.
-    The first call synchronises the stream (the size of the result comes back through the host)."""
+    The first call synchronises the device (the size of the result comes back through the host and its scratch is freed with hipFree)."""
     from .io import DeviceAdjacency
     rowptr, col = _csr_arrays(adj, "csr_select")
     val = adj.val
@@ -1970,7 +1970,7 @@ def csr_merge(a, b, mode="sum", lanes=0, positions=False):
     sides gets a + b (one float32 addition; a zero sum stays stored) under mode="sum" and a's value under mode="keep"; a column
     stored on one side keeps that side's bits.  Returns a DeviceAdjacency and, with positions=True, also (pos_a, pos_b): the int64
     position of every output entry in `a` and in `b`, -1 where that side does not store it.  lanes: 0 = auto, or one of
-    CSR_MERGE_LANES.  The first call synchronises the stream (the size of the result comes back through the host)."""
+    CSR_MERGE_LANES.  The first call synchronises the device (the size of the result comes back through the host and its scratch is freed with hipFree)."""
     from .io import DeviceAdjacency
     rowptr_a, col_a = _csr_arrays(a, "csr_merge")
     rowptr_b, col_b = _csr_arrays(b, "csr_merge")

@@ -153,8 +153,10 @@ def test_nan_inf_stay_in_the_rows_that_reference_them(goldens, cuda):
 
 
 def test_spmm_on_a_side_stream(goldens, cuda):
-    """every entry point is stream-ordered on the caller's stream: results are correct when launched on a non-default
-    torch stream with the producer of X on that same stream"""
+    """sgl_spmm_f32 launched twice on a non-default torch stream, with the producer of X on that same stream, gives the oracle's
+    result.  This is a smoke check of one entry point: its producer takes microseconds and `.cpu()` reads through the null stream,
+    so a launch on the wrong stream would still pass.  That every entry point runs on the caller's stream is proven in
+    tests/test_gpu_stream_order.py (a delayed producer, decoy inputs, no device-wide synchronisation)."""
     n, ptr, col, val = norm_graph(goldens, "pl2000")
     csr = device_csr(ptr, col, val, (n, n), cuda, strict=True)
     xh = hash_matrix(n, 64, seed=3)
