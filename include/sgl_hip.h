@@ -267,8 +267,8 @@ int sgl_csr_permute_rows(const int64_t *d_rowptr, const int32_t *d_col, const fl
                          int64_t *d_out_rowptr, int32_t *d_out_col, float *d_out_val, void *stream);
 /* Storage row i of the handle is output row d_rowmap[i] (a permutation of 0..n_rows-1; NULL removes the map; the array must
  * outlive its use).  Applies to sgl_spmm_f32 / _chain / _acc / _axpb_clamp (outputs, residual and running aggregate are addressed
- * through the map); sgl_spmm_multi_f32 refuses a mapped handle.  The map is validated on the device and the entries of split
- * rows are read back; the scratch of the validation is freed on return: this call synchronises the DEVICE. */
+ * through the map); sgl_spmm_multi_f32 refuses a mapped handle from its second output on.  The map is validated on the device and
+ * the entries of split rows are read back; the scratch of the validation is freed on return: this call synchronises the DEVICE. */
 int sgl_csr_set_rowmap(sgl_csr_t *csr, const int32_t *d_rowmap, void *stream);
 
 /* ---- multi-GPU exchange (row-sharded layout): the all-gather of the feature block between hops ---------------- */
