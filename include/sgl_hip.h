@@ -728,7 +728,23 @@ int sgl_class_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, int64_t c,
 int sgl_col_signature_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, uint64_t *d_sig, void *stream);
 
 /* order-sensitive 64-bit hash of a HOST buffer, multi-threaded (what the reference-signature shims key their cached adjacency
- * on; the operator layer fingerprints scipy index / value arrays with it).  Host-only: works without a GPU. */
+ * on; the operator layer fingerprints scipy index / value arrays with it, the on-disk hop cache host features).  Host-only: works
+ * without a GPU.  Not cryptographic: it separates edits, moves, swaps and sign flips of ordinary data, not chosen collisions.
+ * The function, all arithmetic modulo 2^64:
+ *     step(h, v) = (t mod 2^64) ^ (t >> 64)  with the full 128-bit product  t = (h ^ v) * 0xBF58476D1CE4E5B9
+ *     fmix(h)    : h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9;  h = (h ^ (h >> 27)) * 0x94D049BB133111EB;  h ^ (h >> 31)
+ * The buffer is cut into blocks of 2^20 bytes (the last one shorter; none when bytes = 0).  Block b of `len` bytes runs four lanes
+ *     h0 = 0x9E3779B97F4A7C15 ^ b,  h1 = 0xC2B2AE3D27D4EB4F,  h2 = 0x165667B19E3779F9,  h3 = 0x27D4EB2F165667C5
+ * over its whole 32-byte groups in order: with w0 .. w3 the group's four 64-bit words as memcpy loads them (host byte order, any
+ * alignment), hk = step(hk, wk).  Each of the remaining len % 32 bytes, in order, goes to lane 0 alone: h0 = step(h0, byte).  Then
+ *     part[b] = fmix(step(step(step(step(0x2545F4914F6CDD1D, h0), h1), h2), h3))
+ * and the result is, with h = 0xCBF29CE484222325 ^ bytes and h = step(h, part[b]) for b = 0, 1, ... in order, fmix(h).  In the
+ * 128-bit product a changed bit k of a word moves t by 2^k * 0xBF58476D1CE4E5B9, so it reaches the whole state at once, by a
+ * difference that is dense and depends on the data: no edit of a few bits of a later word equals it.  (A 64-bit multiply alone only
+ * carries a difference upwards, and two sign flips in one lane cancel; folding its result by t >> 32 leaves a sign flip as the
+ * fixed pattern of bits 63 and 31, which two sign flips in the lane's next word cancel.)  step is not a bijection of h: two
+ * states meet with probability about 2^-64 per word, which is the price of the construction.  The blocks are fixed, so the result
+ * does not depend on how many threads computed it; the length is part of it. */
 int sgl_content_hash(const void *h_ptr, int64_t bytes, uint64_t *out);
 
 #ifdef __cplusplus

@@ -101,14 +101,31 @@ struct JoinThread {   // RAII join of one helper thread
     }
 };
 
+// One absorption step of the content hash: the full 128-bit product, its high half xor-ed onto its low half.  A 64-bit multiply
+// only ever carries a difference UP (a flipped sign bit stays in bit 63 for the rest of the block, and a second flip in the same
+// lane cancels it); folding that product's own high half down leaves a flipped sign bit as the FIXED pattern {63, 31}, which
+// sign flips in the next word of the lane cancel just as well.  In the 128-bit product a flipped bit k adds or subtracts
+// 2^k * multiplier: the high half moves by a dense, data-dependent amount for high k, the low half for low k, and no edit of a few
+// bits of the next word equals that difference.
+inline uint64_t hash_step(uint64_t h, uint64_t v) {
+    const unsigned __int128 t = (unsigned __int128)(h ^ v) * 0xBF58476D1CE4E5B9ull;
+    return (uint64_t)t ^ (uint64_t)(t >> 64);
+}
+
+inline uint64_t hash_fmix(uint64_t h) {   // the splitmix64 finaliser
+    h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+    h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+    return h ^ (h >> 31);
+}
+
 // order-sensitive 64-bit content hash, computed by a team of threads over fixed 1 MiB blocks (so the result does not
-// depend on the number of threads)
+// depend on the number of threads); the function is stated in full at sgl_content_hash in include/sgl_hip.h
 uint64_t content_hash(const void *p, size_t bytes, int threads) {
     constexpr size_t kBlock = (size_t)1 << 20;
     const size_t blocks = (bytes + kBlock - 1) / kBlock;
     std::vector<uint64_t> part(blocks, 0);
     std::atomic<size_t> next(0);
-    run_team(threads, [&](int) {
+    run_team((int)std::min<size_t>((size_t)threads, std::max<size_t>(blocks, 1)), [&](int) {
         for (;;) {
             const size_t b = next.fetch_add(1);
             if (b >= blocks) break;
@@ -119,20 +136,23 @@ uint64_t content_hash(const void *p, size_t bytes, int threads) {
             for (; i + 32 <= len; i += 32) {
                 uint64_t w[4];
                 memcpy(w, q + i, 32);
-                h0 = (h0 ^ w[0]) * 0x100000001B3ull;
-                h1 = (h1 ^ w[1]) * 0x100000001B3ull;
-                h2 = (h2 ^ w[2]) * 0x100000001B3ull;
-                h3 = (h3 ^ w[3]) * 0x100000001B3ull;
+                h0 = hash_step(h0, w[0]);
+                h1 = hash_step(h1, w[1]);
+                h2 = hash_step(h2, w[2]);
+                h3 = hash_step(h3, w[3]);
             }
-            for (; i < len; ++i) h0 = (h0 ^ q[i]) * 0x100000001B3ull;
-            uint64_t h = h0 ^ (h1 << 1 | h1 >> 63) ^ (h2 << 2 | h2 >> 62) ^ (h3 << 3 | h3 >> 61);
-            h ^= h >> 29;
-            part[b] = h * 0xBF58476D1CE4E5B9ull;
+            for (; i < len; ++i) h0 = hash_step(h0, q[i]);
+            uint64_t e = 0x2545F4914F6CDD1Dull;
+            e = hash_step(e, h0);
+            e = hash_step(e, h1);
+            e = hash_step(e, h2);
+            e = hash_step(e, h3);
+            part[b] = hash_fmix(e);
         }
     });
     uint64_t h = 0xCBF29CE484222325ull ^ (uint64_t)bytes;
-    for (size_t b = 0; b < blocks; ++b) h = (h ^ part[b]) * 0x100000001B3ull;
-    return h;
+    for (size_t b = 0; b < blocks; ++b) h = hash_step(h, part[b]);
+    return hash_fmix(h);
 }
 
 bool all_zero(const void *p, size_t bytes, int threads) {

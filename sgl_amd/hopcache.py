@@ -4,7 +4,7 @@ The reference never caches its propagated features: every run of a task, every s
 repeats the same k SpMMs on the same graph and features (sgl/tasks/node_classification.py:34-38,
 sgl/tasks/node_classification_with_label_use.py:79,104).  `GraphOp(hop_cache_dir=...)` (or SGL_AMD_HOP_CACHE) keeps the result
 of propagate() under a key made of the CONTENT of the adjacency and of the features (full hashes: sgl_content_hash for host
-arrays, a sum of non-linearly mixed (word, position) pairs of the raw bits for device tensors: _bits_digest) and of everything that shapes the result
+arrays -- lanes of folded 128-bit multiplies, include/sgl_hip.h; entries written under the earlier unfolded hash are never found again and simply miss --, a sum of non-linearly mixed (word, position) pairs of the raw bits for device tensors: _bits_digest) and of everything that shapes the result
 (operator class, r, alpha, prop_steps, strict_order, library version).  A hit loads the hop matrices straight to the device;
 anything unexpected (partial directory, shape mismatch) is a miss.  Files: <dir>/<key>/hop_<k>.npy + meta.json (written last)."""
 import json

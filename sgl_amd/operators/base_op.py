@@ -17,8 +17,11 @@ class AdjIdentity:
     """Identity of an adjacency for the normalised-adjacency caches: the cache hits only for the SAME object (held by
     weak reference and compared with `is`, so a recycled id() of a freed temporary can never match) whose contents
     are still the same -- FULL hashes of the row pointers, indices and values (sgl_content_hash: the library's team of host
-    threads, about a gigabyte in a few tens of milliseconds, no optional dependency), buffer addresses -- so any in-place edit
-    of a cached matrix is noticed."""
+    threads, about a gigabyte in a few tens of milliseconds, no optional dependency), buffer addresses -- so an in-place edit
+    of a cached matrix is noticed, up to the chance of a 64-bit hash: a single entry, and also sign flips or rescalings of several
+    entries next to each other (each word is absorbed by a 128-bit multiply folded onto itself, include/sgl_hip.h; under a bare
+    64-bit multiply two sign flips in one lane cancelled, and tests/test_content_hash_cpu.py holds every subset of sign flips over a
+    window of a lane).  It is a non-cryptographic hash: it separates the edits of ordinary use, not collisions somebody constructs."""
 
     def __init__(self, adj, on_death=None):
         import weakref
