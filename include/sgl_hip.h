@@ -80,6 +80,14 @@ extern "C" {
 
 #define SGL_MAX_HOPS 64 /* upper bound on the number of hop matrices one aggregator call accepts */
 
+/* The widest row an entry point takes: every width argument -- d, d + pad_cols, the k of the two centre kernels, the row of a bfloat16
+ * concat (n_hops * d + pad_cols) -- may be at most 2^31 - 1 - 4096.  A wider one is refused before any launch with SGL_ERR_UNSUPPORTED and
+ * the message "<entry point>: <argument>=<value> is wider than SGL_MAX_WIDTH=2147479551" (the kernels hold a column in 32 bits and step
+ * it by up to a tile of 1024; 2^31 - 1 and beyond stay SGL_ERR_INVALID, "bad sizes").  Narrower limits are documented where they apply:
+ * c <= 2^30 (sgl_class_loss_grad_f32), d <= 512 / 1024 for the register-resident row kernels.  The float32 concat takes ANY n_hops * d
+ * with d inside the limit: rows of n_hops * d + pad_cols > 2^31 - 1 - 1024 columns are copied by its 64-bit kernel. */
+#define SGL_MAX_WIDTH 2147479551
+
 /* ---- library ----------------------------------------------------------------------------------------------- */
 int sgl_version(void);                /* 10000*major + 100*minor + patch */
 const char *sgl_last_error(void);     /* thread-local, never NULL */
@@ -511,7 +519,8 @@ int sgl_hop_colsum_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx
  * the same for every adopted hop of a node).  U: [n_hops, ldu] on device, vec as above.  Same limits as sgl_hop_gate_f32. */
 int sgl_hop_rowdot2_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_u, int64_t ldu, uint64_t u_mask,
                         const float *d_vec, int h0, int h1, float *d_p, int64_t ldp, float *d_a, int64_t n, int64_t d, void *stream);
-/* out[i, :] = X[idx[i], :]   (idx: int64 on device; negative indices are NOT wrapped) */
+/* out[i, :] = X[idx[i], :]   (idx: int64 on device; negative indices count from the end, as in the other gathers; an index outside
+ * [-n_rows, n_rows) traps the kernel) */
 int sgl_gather_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t n_idx,
                         float *d_out, int64_t ldo, int64_t d, void *stream);
 /* the same with the destination rows' own padding declared (as in the other *_padded entry points): columns [d, d + pad_cols) of every
@@ -679,8 +688,10 @@ int sgl_csr_merge_fill(const int64_t *a_rowptr, const int32_t *a_col, const floa
  * whose distances are all NaN (a NaN in the row) gets label 0 and mindist NaN -- the kernel never traps.  Columns d .. pitch are
  * never used (they may hold NaN), nothing beyond column d of a matrix's last row is read.  16-byte aligned bases with pitches that are
  * multiples of 4 floats (X and C) get 16-byte lane accesses, everything else one float per lane; the summation order depends on d and
- * that layout alone: not on n, k, the tile or the row's position, and two runs are bit-equal (no atomics).  n = 0: nothing is done;
- * d = 0: labels 0, distances 0. */
+ * that layout alone: not on n, k, the tile or the row's position, and two runs are bit-equal (no atomics).  Rows beyond the register
+ * layouts (d > 2048) are streamed: a lane sums its chunks in blocks of 64, each block from zero, the blocks added in order, so that
+ * a row of 10^6 columns is not one running sum (a row of at most 16 384 columns in 16-byte lanes, 4 096 in 4-byte lanes, is one
+ * block).  sgl_cluster_loss_grad_f32 sums its distances the same way.  n = 0: nothing is done; d = 0: labels 0, distances 0. */
 int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_centres, int64_t ldc, int64_t k,
                           int64_t *d_labels, float *d_mindist, void *stream);
 

@@ -1139,8 +1139,16 @@ __global__ __launch_bounds__(256) void hop_concat_kernel(const Hops hx, const in
             *reinterpret_cast<V *>(out + row * ldo + (int64_t)n_hops * d + (rem - row_v) * VEC) = (V)(0.f);
             continue;
         }
-        const int h = (int)rem / dv;
-        const int col = ((int)rem - h * dv) * VEC;
+        // rem runs up to (d / VEC) * n_hops, which leaves 32 bits where H d >= 2^31 (the rows this kernel is the fallback for):
+        // h and the column are formed in 64 bits there; narrower rows keep the 32-bit division
+        int h, col;
+        if (row_v <= (int64_t)INT32_MAX) {
+            h = (int)rem / dv;
+            col = ((int)rem - h * dv) * VEC;
+        } else {
+            h = (int)(rem / dv);
+            col = (int)(rem - (int64_t)h * dv) * VEC;
+        }
         *reinterpret_cast<V *>(out + row * ldo + (int64_t)h * d + col) =
             *reinterpret_cast<const V *>(hx.p[h] + row * hx.ld[h] + col);
     }
@@ -1581,6 +1589,7 @@ SGL_EXPORT int sgl_hop_reduce_f32(int op, int n_hops, const float *const *h_x, c
                                   float *d_out, int64_t ldo, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(op >= SGL_REDUCE_SUM && op <= SGL_REDUCE_WSUM, "sgl_hop_reduce_f32: unknown op %d", op);
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_reduce_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_reduce_f32", "d", d);
     SGL_REQUIRE(op != SGL_REDUCE_WSUM || d_w, "sgl_hop_reduce_f32: WSUM needs device weights");
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldo % 4 == 0) && aligned_to(d_out, 16);
@@ -1603,6 +1612,7 @@ SGL_EXPORT int sgl_hop_reduce_f32(int op, int n_hops, const float *const *h_x, c
 static int wsum2d_impl(bool fma, int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_w, int64_t ldw,
                        float *d_out, int64_t ldo, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_wsum2d_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_wsum2d_f32", "d", d);
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldo % 4 == 0) && aligned_to(d_out, 16);
     int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
@@ -1654,6 +1664,7 @@ SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const
                                       int64_t ldw, const float *d_dout, int64_t lddo, float *d_dw, int64_t lddw,
                                       float *const *h_dx, const int64_t *h_lddx, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_wsum2d_bwd_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_wsum2d_bwd_f32", "d", d);
     Hops hx;
     bool hops4 = true;                                         // 16-byte row accesses possible (any d, masked tail)
     int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &hops4);
@@ -1700,6 +1711,7 @@ SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const
 SGL_EXPORT int sgl_hop_rowdot_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_vec,
                                   float *d_out, int64_t ldo, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_rowdot_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_rowdot_f32", "d", d);
     Hops hx;
     bool row4 = aligned_to(d_vec, 16);
     int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &row4);
@@ -1728,6 +1740,7 @@ SGL_EXPORT int64_t sgl_hop_wsum1d_bwd_scratch(int n_hops) { return (int64_t)kW1d
 SGL_EXPORT int sgl_hop_wsum1d_bwd_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_dout,
                                       int64_t lddo, float *d_dw, float *d_scratch, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_wsum1d_bwd_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_wsum1d_bwd_f32", "d", d);
     Hops hx;
     bool vec4 = false;
     int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
@@ -1766,6 +1779,7 @@ SGL_EXPORT int sgl_hop_select_bwd_f32(int op, int n_hops, const float *const *h_
                                      int64_t ldg, float *const *h_dx, const int64_t *h_lddx, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(op == SGL_REDUCE_MAX || op == SGL_REDUCE_MIN, "sgl_hop_select_bwd_f32: op must be SGL_REDUCE_MAX or SGL_REDUCE_MIN");
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_select_bwd_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_select_bwd_f32", "d", d);
     Hops hx;
     bool vec4 = (d % 4 == 0) && (ldg % 4 == 0) && aligned_to(d_gout, 16);
     int rc = fill_hops(nullptr, hx, n_hops, h_x, h_ldx, d, 4, &vec4);
@@ -1790,6 +1804,7 @@ SGL_EXPORT int sgl_hop_select_bwd_f32(int op, int n_hops, const float *const *h_
 SGL_EXPORT int sgl_hop_lincomb_f32(int n_in, const float *const *h_x, const int64_t *h_ldx, int n_out, float *const *h_out,
                                    const int64_t *h_ldo, const float *d_w, int64_t ldw, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_lincomb_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_lincomb_f32", "d", d);
     SGL_REQUIRE(n_in >= 1 && n_in <= 16, "sgl_hop_lincomb_f32: between 1 and 16 input matrices (n_in=%d)", n_in);
     SGL_REQUIRE(n_out >= 1 && n_out <= SGL_MAX_HOPS, "sgl_hop_lincomb_f32: between 1 and %d outputs", SGL_MAX_HOPS);
     SGL_REQUIRE(d_w && ldw >= n_in && ldw < INT32_MAX, "sgl_hop_lincomb_f32: the [n_out, ldw] weight matrix is required (ldw >= n_in)");
@@ -1818,6 +1833,7 @@ SGL_EXPORT int sgl_hop_lincomb_f32(int n_in, const float *const *h_x, const int6
 SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, float *d_out, int64_t ldo,
                                          int64_t pad_cols, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_hop_concat_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_hop_concat_f32", "d", d);
     {
         const int prc = sgl::check_pad("sgl_hop_concat_padded_f32", d * (n_hops > 0 ? n_hops : 0), pad_cols, ldo);
         if (prc != SGL_OK) return prc;
@@ -1829,7 +1845,9 @@ SGL_EXPORT int sgl_hop_concat_padded_f32(int n_hops, const float *const *h_x, co
     if (n == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_out && ldo >= d * n_hops, "sgl_hop_concat_f32: bad output");
     hipStream_t st = sgl::as_stream(stream);
-    const bool out16 = (ldo % 4 == 0) && aligned_to(d_out, 16) && d * n_hops < INT32_MAX;
+    // the three 16-byte-store kernels below hold output columns in int and step them by a tile (o0 + kConcatTile, c + 4, width_w + 3):
+    // rows within a tile of 2^31 columns, pad included, take the 64-bit fallback at the end instead
+    const bool out16 = (ldo % 4 == 0) && aligned_to(d_out, 16) && d * n_hops + pad_cols <= (int64_t)INT32_MAX - kConcatTile;
     if (vec4) {
         // d % 4 == 0 and (check_pad) H d + pad_cols a multiple of 4: the pad is whole vectors
         const int grid = stream_grid(n * ((d / 4) * n_hops + pad_cols / 4));
@@ -1880,6 +1898,7 @@ SGL_EXPORT int sgl_hop_concat_f32(int n_hops, const float *const *h_x, const int
 SGL_EXPORT int sgl_nafs_padded_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, float *d_out, int64_t ldo,
                                    int64_t pad_cols, float *d_w_out, int64_t ldw, int64_t n, int64_t d, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_nafs_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_nafs_f32", "d", d);
     {
         const int prc = sgl::check_pad("sgl_nafs_padded_f32", d, d_out ? pad_cols : 0, d_out ? ldo : d);
         if (prc != SGL_OK) return prc;
@@ -1914,7 +1933,11 @@ SGL_EXPORT int sgl_nafs_padded_f32(int n_hops, const float *const *h_x, const in
     SGL_LAUNCH_CHECK("sgl_nafs_f32(weights)");
     if (!d_out) return SGL_OK;  // weights only
     // out = sum_h W[:,h] * X_h accumulated in hop order from 0 with rounded products (over_smooth_distance_op.py:27-31)
-    return wsum2d_impl(false, n_hops, h_x, h_ldx, d_w_out, ldw, d_out, ldo, n, d, stream);
+    rc = wsum2d_impl(false, n_hops, h_x, h_ldx, d_w_out, ldw, d_out, ldo, n, d, stream);
+    // the weighted sum writes the d data columns only: the declared pad columns are zeroed here, as the fused kernel's store_row does
+    if (rc == SGL_OK && pad_cols > 0 && sgl::tuning("row_whole_lines", 1) != 0)
+        SGL_HIP_CHECK(hipMemset2DAsync(d_out + d, (size_t)ldo * sizeof(float), 0, (size_t)pad_cols * sizeof(float), (size_t)n, st));
+    return rc;
 }
 
 SGL_EXPORT int sgl_nafs_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, float *d_out, int64_t ldo,
@@ -1958,6 +1981,7 @@ SGL_EXPORT int sgl_nafs_prefix_f32(int n_hops, const float *const *h_x, const in
 static int copy_rows(const char *who, const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, const int64_t *d_dst,
                      int64_t n_out, int64_t n_idx, float *d_out, int64_t ldo, int64_t dz, int64_t pad, void *stream) {
     SGL_REQUIRE(n_idx >= 0 && dz >= 0 && pad >= 0 && dz + pad < INT32_MAX && n_rows >= 0 && n_out >= 0, "%s: bad sizes", who);
+    SGL_REQUIRE_WIDTH(who, "d + pad_cols", dz + pad);
     if (n_idx == 0 || dz == 0) return SGL_OK;
     const int64_t d = dz + pad;                     // columns written: the data, then the destination's own padding as zeros
     SGL_REQUIRE(d_x && d_idx && d_out && ldx >= dz && ldo >= d, "%s: bad arguments", who);
@@ -2006,6 +2030,7 @@ SGL_EXPORT int sgl_gather_rows_padded_f32(const float *d_x, int64_t ldx, int64_t
 SGL_EXPORT int sgl_gather_hops_padded_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, int64_t n_rows, const int64_t *d_idx,
                                           int64_t n_idx, float *const *h_out, const int64_t *h_ldo, int64_t d, int64_t pad_cols, void *stream) {
     SGL_REQUIRE(n_idx >= 0 && d >= 0 && pad_cols >= 0 && d + pad_cols < INT32_MAX && n_rows >= 0, "sgl_gather_hops_padded_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_gather_hops_padded_f32", "d + pad_cols", d + pad_cols);
     if (n_idx == 0 || d == 0) return SGL_OK;
     SGL_REQUIRE(d_idx && h_out && h_ldo, "sgl_gather_hops_padded_f32: NULL arguments");
     Hops hx;
@@ -2124,6 +2149,7 @@ __global__ __launch_bounds__(256) void col_signature_kernel(const float *__restr
 // alloc_rows gives; the up-to-3 pad columns behind d are signed with the rest)
 SGL_EXPORT int sgl_col_signature_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, uint64_t *d_sig, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX, "sgl_col_signature_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_col_signature_f32", "d", d);
     const int64_t dw = (d + 3) / 4 * 4;
     if (dw == 0) return SGL_OK;
     SGL_REQUIRE(d_sig != nullptr, "sgl_col_signature_f32: NULL output");

@@ -360,6 +360,7 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fu
 // what every entry checks before anything touches a device; the hop table for the kernels
 int fill_hops_bf16(const char *who, HopsB &hx, int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, int64_t n, int64_t d) {
     if (n < 0 || d <= 0 || d >= INT32_MAX) return sgl::fail(SGL_ERR_INVALID, "%s: bad sizes (n=%lld, d=%lld)", who, (long long)n, (long long)d);
+    SGL_REQUIRE_WIDTH(who, "d", d);
     return fill_hops(who, hx, n_hops, h_x, h_ldx, d, 2, nullptr);
 }
 
@@ -377,6 +378,7 @@ int concat_impl(const char *who, int ob, int n_hops, const uint16_t *const *h_x,
     if (rc != SGL_OK) return rc;
     const int64_t width = d * n_hops;
     if (width >= INT32_MAX || pad_cols >= INT32_MAX - width) return sgl::fail(SGL_ERR_INVALID, "%s: rows of %lld columns are too wide", who, (long long)width);
+    if (pad_cols >= 0) SGL_REQUIRE_WIDTH(who, "n_hops * d + pad_cols", width + pad_cols);
     if (pad_cols < 0 || width + pad_cols > ldo) return sgl::fail(SGL_ERR_INVALID, "%s: pad_cols=%lld does not fit the output pitch", who, (long long)pad_cols);
     if (!d_out || !aligned_to(d_out, (size_t)ob)) return sgl::fail(SGL_ERR_INVALID, "%s: bad output", who);
     for (int h = 0; h < n_hops; ++h)
@@ -406,6 +408,7 @@ SGL_EXPORT int sgl_hop_reduce_bf16_f32(int op, int n_hops, const uint16_t *const
     SGL_REQUIRE(op != SGL_REDUCE_WSUM || d_w, "%s: WSUM needs device weights", who);
     SGL_REQUIRE(pad_cols >= 0 && pad_cols < INT32_MAX - d && d + pad_cols <= ldo, "%s: pad_cols=%lld does not fit the output pitch", who, (long long)pad_cols);
     SGL_REQUIRE(d_out && aligned_to(d_out, 4), "%s: bad output", who);
+    SGL_REQUIRE_WIDTH(who, "d + pad_cols", d + pad_cols);
     if (n == 0) return SGL_OK;
     const int64_t dw = d + pad_cols;
     // lane width from alignment alone: the lane that straddles column d masks what lies beyond it

@@ -26,6 +26,7 @@ struct Sq<4> {
         a = __builtin_elementwise_fma(lo, lo, a);
         a = __builtin_elementwise_fma(hi, hi, a);
     }
+    __device__ __forceinline__ void merge(const Sq &o) { a += o.a; }
     __device__ __forceinline__ float total() const { return a[0] + a[1]; }
 };
 template <>
@@ -39,8 +40,18 @@ struct Sq<1> {
         const float t = x + nc;
         a = fmaf(t, t, a);
     }
+    __device__ __forceinline__ void merge(const Sq &o) { a += o.a; }
     __device__ __forceinline__ float total() const { return a; }
 };
+
+// The streaming kernels (rows beyond the register layouts) sum a lane's chunks in blocks of kStreamBlock: each block from zero, the
+// blocks added in order (Sq::merge).  One running sum per lane over the 4 096 chunks of a row of 10^6 columns loses the low bits of
+// every term added to a sum that is already large -- measured at d = 1 048 580 on the k-means test rows, whose columns 0 .. 7 (the
+// FIRST chunk of lanes 0 and 1) carry four fifths of the energy: 1.3e-5 of the squared distance, biased low, 4.5e-6 of dX, against
+// 5e-7 / 3.6e-7 for numpy's pairwise float32 sum; in blocks 2.4e-7 (restated on the CPU: tests/test_wide_cpu.py).  A row of at most
+// kStreamBlock chunks per lane (16 384 columns in 16-byte lanes, 4 096 in 4-byte lanes) is one block, and 0 + s = s: its bits are
+// what they were.
+constexpr int kStreamBlock = 64;
 
 constexpr int kTileFloats = 16384;                   // 64 KiB of centres per tile
 

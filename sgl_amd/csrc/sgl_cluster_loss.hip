@@ -252,7 +252,13 @@ __global__ __launch_bounds__(256) void cluster_loss_stream_kernel(const float *_
             const float *crow = cen + (int64_t)j * ldc;
             const bool last_c = j == k - 1;
             Sq<VEC> sq;
-            for (int col = l * VEC; col < d; col += 64 * VEC) sq.add(edge_load<VEC>(p, col, d, last), edge_load<VEC>(crow, col, d, last_c));
+            for (int64_t c0 = (int64_t)l * VEC; c0 < d; c0 += (int64_t)kStreamBlock * 64 * VEC) {   // blocks of kStreamBlock chunks (sgl_centres.h)
+                const int64_t c1 = min((int64_t)d, c0 + (int64_t)kStreamBlock * 64 * VEC);
+                Sq<VEC> part;
+                for (int64_t col = c0; col < c1; col += 64 * VEC)
+                    part.add(edge_load<VEC>(p, (int)col, d, last), edge_load<VEC>(crow, (int)col, d, last_c));
+                sq.merge(part);
+            }
             float dist, a;
             dist_coef(group_sum<64>(sq.total()), j == y, inv_k, dist, a);
             sums.take(dist, j == y);
@@ -291,6 +297,8 @@ SGL_EXPORT int sgl_cluster_loss_grad_f32(const float *d_x, int64_t ldx, int64_t 
                                          const int64_t *d_labels, float w, float *d_dx, int64_t lddx, float *d_row_loss, void *stream) {
     const char *who = "sgl_cluster_loss_grad_f32";
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX && k >= 1 && k < INT32_MAX, "%s: bad sizes (n >= 0, d >= 0, k >= 1)", who);
+    SGL_REQUIRE_WIDTH(who, "d", d);
+    SGL_REQUIRE_WIDTH(who, "k", k);
     // (a matrix without rows or without columns has no storage, no rows have no labels and no losses: such a pointer is never used)
     SGL_REQUIRE(d_dx || d_row_loss || n == 0, "%s: at least one of d_dx and d_row_loss is needed", who);
     SGL_REQUIRE((d_x || n == 0 || d == 0) && (d_centres || d == 0) && (d_labels || n == 0), "%s: NULL arguments", who);

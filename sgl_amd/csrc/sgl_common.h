@@ -43,6 +43,15 @@ inline int fail(int code, const char *fmt, ...) {
         if (!(cond)) return ::sgl::fail(SGL_ERR_INVALID, __VA_ARGS__); \
     } while (0)
 
+// A row width (d, c, k, d + pad_cols) beyond SGL_MAX_WIDTH (include/sgl_hip.h): the kernels hold a column in `int` and step it by up
+// to a tile (lanes x floats per lane, c + 4, d + 3), which would wrap in the last columns below 2^31 -- refused by name, before any launch
+#define SGL_REQUIRE_WIDTH(who, what, v)                                                                                          \
+    do {                                                                                                                         \
+        if ((int64_t)(v) > (int64_t)SGL_MAX_WIDTH)                                                                               \
+            return ::sgl::fail(SGL_ERR_UNSUPPORTED, "%s: %s=%lld is wider than SGL_MAX_WIDTH=%lld", who, what, (long long)(v),   \
+                               (long long)SGL_MAX_WIDTH);                                                                        \
+    } while (0)
+
 // ---- execution plan (host) ---------------------------------------------------------------------------------
 struct Piece {
     int64_t begin;  // first non-zero (absolute)

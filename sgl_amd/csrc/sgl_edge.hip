@@ -100,6 +100,7 @@ constexpr int kEdgesPerGroup = 4;                    // U: 8 row vectors per lan
 SGL_EXPORT int sgl_edge_dot_f32(const float *d_a, int64_t lda, int64_t n_a, const float *d_b, int64_t ldb, int64_t n_b,
                                 const int64_t *d_edges, int64_t n_edges, int64_t d, float *d_out, void *stream) {
     SGL_REQUIRE(n_edges >= 0 && d >= 0 && d < INT32_MAX && n_a >= 0 && n_b >= 0, "sgl_edge_dot_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_edge_dot_f32", "d", d);
     // (a matrix without rows or without columns has no storage: its pointer is never used)
     SGL_REQUIRE((d_a || n_a == 0 || d == 0) && (d_b || n_b == 0 || d == 0) && d_edges && d_out, "sgl_edge_dot_f32: NULL arguments");
     SGL_REQUIRE(lda >= d && ldb >= d, "sgl_edge_dot_f32: row pitch smaller than d");

@@ -317,6 +317,7 @@ SGL_EXPORT int sgl_edge_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, 
     const char *who = "sgl_edge_loss_grad_f32";
     SGL_REQUIRE(n >= 0 && n < INT32_MAX && d >= 0 && d < INT32_MAX && n_pieces >= 0 && n_inc >= 0 && n_edges >= 0 && n_partial >= 0 && n_fold >= 0,
                 "%s: bad sizes", who);
+    SGL_REQUIRE_WIDTH(who, "d", d);
     SGL_REQUIRE(n_inc == 2 * n_edges, "%s: the incidence list must hold every edge twice", who);
     SGL_REQUIRE(mode == MODE_SIGMOID_LOGITS || mode == MODE_LOGITS || mode == MODE_GIVEN, "%s: unknown mode %d", who, mode);
     SGL_REQUIRE(d_z || n == 0 || d == 0, "%s: NULL z", who);

@@ -181,8 +181,13 @@ __global__ __launch_bounds__(256) void kmeans_assign_stream_kernel(const float *
         for (int j = 0; j < k; ++j) {
             const float *crow = cen + (int64_t)j * ldc;
             Sq<VEC> acc;
-            for (int64_t col = (int64_t)l * VEC; col < d; col += 64 * VEC)
-                acc.add(edge_load<VEC>(p, (int)col, d, row == n - 1), edge_load<VEC>(crow, (int)col, d, j == k - 1));
+            for (int64_t c0 = (int64_t)l * VEC; c0 < d; c0 += (int64_t)kStreamBlock * 64 * VEC) {   // blocks of kStreamBlock chunks (sgl_centres.h)
+                const int64_t c1 = min((int64_t)d, c0 + (int64_t)kStreamBlock * 64 * VEC);
+                Sq<VEC> part;
+                for (int64_t col = c0; col < c1; col += 64 * VEC)
+                    part.add(edge_load<VEC>(p, (int)col, d, row == n - 1), edge_load<VEC>(crow, (int)col, d, j == k - 1));
+                acc.merge(part);
+            }
             best.take(group_sum<64>(acc.total()), j);
         }
         if (l == 0) {
@@ -215,6 +220,8 @@ void launch_assign(hipStream_t st, const float *d_x, int64_t ldx, int64_t n, int
 SGL_EXPORT int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_centres, int64_t ldc, int64_t k,
                                      int64_t *d_labels, float *d_mindist, void *stream) {
     SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX && k >= 0 && k < INT32_MAX && (k >= 1 || n == 0), "sgl_kmeans_assign_f32: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_kmeans_assign_f32", "d", d);
+    SGL_REQUIRE_WIDTH("sgl_kmeans_assign_f32", "k", k);
     // (a matrix without rows or without columns has no storage, no rows have no labels: such a pointer is never used)
     SGL_REQUIRE((d_x || n == 0 || d == 0) && (d_centres || k == 0 || d == 0) && (d_labels || n == 0), "sgl_kmeans_assign_f32: NULL arguments");
     SGL_REQUIRE(ldx >= d && ldc >= d, "sgl_kmeans_assign_f32: row pitch smaller than d");

@@ -514,6 +514,7 @@ static int spmm_impl(sgl_csr_t *h, const float *d_x, int64_t ldx, float *d_y, in
                      void *stream, EpiHost eh, const char *who) {
     if (!h) return sgl::fail(SGL_ERR_INVALID, "%s: NULL handle", who);
     SGL_REQUIRE(d >= 0 && d < INT32_MAX, "%s: bad d", who);
+    SGL_REQUIRE_WIDTH(who, "d", d);
     if (d == 0 || h->n_rows == 0) return SGL_OK;
     SGL_REQUIRE(d_x && d_y, "%s: NULL X or Y", who);
     if (h->d_rowmap && eh.n_more > 0)
@@ -604,6 +605,7 @@ SGL_EXPORT int sgl_chain_graph_create(sgl_graph_t **out, sgl_csr_t *h, int n_hop
     if (!out) return sgl::fail(SGL_ERR_INVALID, "sgl_chain_graph_create: NULL out");
     *out = nullptr;
     SGL_REQUIRE(h && n_hops >= 1 && h_y && h_ldy, "sgl_chain_graph_create: bad arguments");
+    SGL_REQUIRE_WIDTH("sgl_chain_graph_create", "d", d);   // under its own name: every other argument is checked by the eager chain below
     // everything that may allocate or synchronise happens BEFORE the capture: one eager run sizes the split-row
     // workspace (and validates the arguments)
     int rc = sgl_spmm_chain_f32(h, n_hops, d_x0, ldx0, h_y, h_ldy, d, nullptr);

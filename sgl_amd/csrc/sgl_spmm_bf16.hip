@@ -444,6 +444,7 @@ int spmm_impl(sgl_csr_t *h, const uint16_t *d_x, int64_t ldx, uint16_t *d_y, int
               const char *who) {
     if (!h) return sgl::fail(SGL_ERR_INVALID, "%s: NULL handle", who);
     SGL_REQUIRE(d >= 0 && d < INT32_MAX, "%s: bad d", who);
+    SGL_REQUIRE_WIDTH(who, "d", d);
     if (d == 0 || h->n_rows == 0) return SGL_OK;
     SGL_REQUIRE(d_x && d_y, "%s: NULL X or Y", who);
     SGL_REQUIRE(ldx >= d && ldy >= d, "%s: leading dimension smaller than d", who);
@@ -549,6 +550,7 @@ __global__ __launch_bounds__(256) void gather_bf16_kernel(const GIn hx, const GO
 int gather_impl(const char *who, int n_hops, const uint16_t *const *h_x, const int64_t *h_ldx, int64_t n_rows, const int64_t *d_idx,
                 int64_t n_idx, float *const *h_out, const int64_t *h_ldo, int64_t d, int64_t pad, void *stream) {
     SGL_REQUIRE(n_idx >= 0 && d >= 0 && pad >= 0 && n_rows >= 0 && d + pad < INT32_MAX, "%s: bad sizes", who);
+    SGL_REQUIRE_WIDTH(who, "d + pad_cols", d + pad);
     SGL_REQUIRE(n_hops >= 1 && h_x && h_ldx && h_out && h_ldo, "%s: NULL hop arrays or n_hops < 1", who);
     if (n_hops > kGatherMaxHops)
         return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: at most %d hop matrices per launch (gather hop by hop)", who, kGatherMaxHops);

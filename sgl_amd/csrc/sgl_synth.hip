@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void synth_features_kernel(uint64_t seed, int6
     const int64_t total = n_rows * ld;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = t / ld;
-        const int k = (int)(t - i * ld);
+        const int64_t k = t - i * ld;   // up to the PITCH, which is not bounded by 2^31 like d: held in 64 bits
         float v = 0.f;   // pad columns are zero
         if (k < d) {
             const int64_t q = (int64_t)(hash4(seed, 3, (uint64_t)(row0 + i), (uint64_t)k) >> 40) - (1 << 23);
@@ -114,6 +114,7 @@ SGL_EXPORT int sgl_synth_fill(uint64_t seed, int64_t row0, int64_t n_rows, int64
 
 SGL_EXPORT int sgl_synth_features(uint64_t seed, int64_t row0, int64_t n_rows, int64_t d, int64_t ld, float *d_x, void *stream) {
     SGL_REQUIRE(n_rows >= 0 && row0 >= 0 && d >= 0 && ld >= d && d < INT32_MAX, "sgl_synth_features: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_synth_features", "d", d);
     if (n_rows == 0 || ld == 0) return SGL_OK;
     SGL_REQUIRE(d_x != nullptr, "sgl_synth_features: NULL output");
     hipLaunchKernelGGL(synth_features_kernel, dim3(blocks_for(n_rows * ld)), dim3(256), 0, sgl::as_stream(stream), seed, row0, n_rows,
