@@ -220,11 +220,7 @@ __global__ __launch_bounds__(256) void hop_rowdot_kernel(const Hops hx, const in
                                                          const int64_t ldg, float *__restrict__ dw, const int64_t lddw,
                                                          const int64_t n, const int d) {
     using V = typename Vt<VEC>::type;
-    constexpr int RPB = 256 / LPR;  // rows per block
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     for (int h = 0; h < n_hops; ++h) {
         float acc = 0.f;
         if (live) {
@@ -254,16 +250,12 @@ template <int LPR, int CH, int HMAX, bool GU = false>
 __global__ __launch_bounds__(256) void hop_rowdot_reg_kernel(const Hops hx, const int n_hops, const float *__restrict__ g,
                                                              const int64_t ldg, float *__restrict__ dw, const int64_t lddw,
                                                              const int64_t n, const int d) {
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     f4 gv[CH], xv[HMAX][CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
         const int col = (c * LPR + l) * 4;
-        const bool on = live && col < d;
+        const bool on = chunk_on<LPR>(c, l, live, d);
         if constexpr (GU) {
             gv[c] = (f4){0.f, 0.f, 0.f, 0.f};
             if (on) {
@@ -286,13 +278,7 @@ __global__ __launch_bounds__(256) void hop_rowdot_reg_kernel(const Hops hx, cons
     }
     float acc[HMAX];
 #pragma unroll
-    for (int h = 0; h < HMAX; ++h) {
-        acc[h] = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[h] = __builtin_fmaf(gv[c][e], xv[h][c][e], acc[h]);
-    }
+    for (int h = 0; h < HMAX; ++h) acc[h] = dot_chunks(gv, xv[h]);
 #pragma unroll
     for (int h = 0; h < HMAX; ++h) acc[h] = group_sum<LPR>(acc[h]);   // independent chains: the scheduler interleaves them
     if (live && l == 0) {
@@ -307,11 +293,7 @@ template <int LPR, int VEC>
 __global__ __launch_bounds__(256) void nafs_weight_kernel(const Hops hx, const int n_hops, float *__restrict__ wout,
                                                           const int64_t ldw, const int64_t n, const int d) {
     using V = typename Vt<VEC>::type;
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     float n0 = 0.f;
     float run_max = -INFINITY;
     // pass A: c_h for every hop (kept in the W row), running max
@@ -380,16 +362,13 @@ template <int LPR, int CH>
 __global__ __launch_bounds__(256) void nafs_prefix_kernel(const Hops hx, const int n_hops, const uint64_t emit, const HopsOut outs,
                                                           const int combine, const float divisor, const int64_t n, const int d,
                                                           const int dw) {
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     f4 x0[CH], acc[CH];
     bool on[CH];
 #pragma unroll
+    for (int c = 0; c < CH; ++c) on[c] = chunk_on<LPR>(c, l, live, d);
+#pragma unroll
     for (int c = 0; c < CH; ++c) {
-        on[c] = live && ((c * LPR + l) * 4 < d);
         x0[c] = (f4){0.f, 0.f, 0.f, 0.f};
         acc[c] = (f4){0.f, 0.f, 0.f, 0.f};
         if (on[c]) x0[c] = load_masked<4, true>(hx.p[0] + r * hx.ld[0], (c * LPR + l) * 4, d);
@@ -409,14 +388,8 @@ __global__ __launch_bounds__(256) void nafs_prefix_kernel(const Hops hx, const i
         for (int u = 0; u < kPrefixUnroll; ++u) {
             const int h = hb + u;
             if (h >= n_hops) break;
-            float dot = 0.f, sq = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    dot = __builtin_fmaf(x0[c][e], x[u][c][e], dot);
-                    sq = __builtin_fmaf(x[u][c][e], x[u][c][e], sq);
-                }
+            float dot, sq;
+            dot_sq_chunks(x0, x[u], dot, sq);
             dot = group_sum<LPR>(dot);
             sq = group_sum<LPR>(sq);
             const float nh = __fadd_rn(__fsqrt_rn(sq), 1e-10f);
@@ -424,9 +397,7 @@ __global__ __launch_bounds__(256) void nafs_prefix_kernel(const Hops hx, const i
             const float ex = expf(__fdiv_rn(__fdiv_rn(dot, nh), n0));
             den += ex;
 #pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[c][e] = __builtin_fmaf(ex, x[u][c][e], acc[c][e]);
+            for (int c = 0; c < CH; ++c) acc[c] = fma4(acc[c], ex, x[u][c]);
             if ((emit >> h) & 1ull) {
                 const int k = __popcll(emit & ((1ull << h) - 1ull));
                 float *__restrict__ orow = outs.p[k] + r * outs.ld[k];
@@ -458,23 +429,12 @@ template <int LPR, int CH, int HMAX>
 __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_fused_kernel(const Hops hx, const int n_hops, float *__restrict__ out,
                                                          const int64_t ldo, float *__restrict__ wout, const int64_t ldw,
                                                          const int64_t n, const int d, const int dw) {
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     f4 x[HMAX][CH];
     bool on[CH];
 #pragma unroll
-    for (int c = 0; c < CH; ++c) on[c] = live && ((c * LPR + l) * 4 < d);
-#pragma unroll
-    for (int h = 0; h < HMAX; ++h) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            x[h][c] = (f4){0.f, 0.f, 0.f, 0.f};
-            if (h < n_hops && on[c]) x[h][c] = load_masked<4, true>(hx.p[h] + r * hx.ld[h], (c * LPR + l) * 4, d);
-        }
-    }
+    for (int c = 0; c < CH; ++c) on[c] = chunk_on<LPR>(c, l, live, d);
+    load_hop_rows<load_masked<4, true>, LPR>(x, hx, n_hops, r, on, l, d);
     f4 acc[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) acc[c] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -484,14 +444,8 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_fused_k
 #pragma unroll
         for (int h = 0; h < HMAX; ++h)
             if (h < n_hops) {
-                float dot = 0.f, sq = 0.f;
-#pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        dot = __builtin_fmaf(x[0][c][e], x[h][c][e], dot);
-                        sq = __builtin_fmaf(x[h][c][e], x[h][c][e], sq);
-                    }
+                float dot, sq;
+                dot_sq_chunks(x[0], x[h], dot, sq);
                 dot = group_sum<LPR>(dot);
                 sq = group_sum<LPR>(sq);
                 dl = (l == h) ? dot : dl;
@@ -514,9 +468,7 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_fused_k
             if (h < n_hops) {
                 const float w = from_lane<LPR>(wl, h);
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __fadd_rn(acc[c][e], __fmul_rn(w, x[h][c][e]));
+                for (int c = 0; c < CH; ++c) acc[c] = mul_add4(acc[c], w, x[h][c]);
             }
     } else {
         float score[HMAX];
@@ -525,14 +477,8 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_fused_k
         for (int h = 0; h < HMAX; ++h) {
             score[h] = -INFINITY;
             if (h < n_hops) {
-                float dot = 0.f, sq = 0.f;
-#pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        dot = __builtin_fmaf(x[0][c][e], x[h][c][e], dot);
-                        sq = __builtin_fmaf(x[h][c][e], x[h][c][e], sq);
-                    }
+                float dot, sq;
+                dot_sq_chunks(x[0], x[h], dot, sq);
                 dot = group_sum<LPR>(dot);
                 sq = group_sum<LPR>(sq);
                 const float nh = __fadd_rn(__fsqrt_rn(sq), 1e-10f);
@@ -554,9 +500,7 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_fused_k
                 const float w = __fdiv_rn(score[h], sum);
                 if (wout && live && l == 0) wout[r * ldw + h] = w;
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __fadd_rn(acc[c][e], __fmul_rn(w, x[h][c][e]));
+                for (int c = 0; c < CH; ++c) acc[c] = mul_add4(acc[c], w, x[h][c]);
             }
     }
     store_row<LPR, CH>(out + r * ldo, acc, l, live, d, dw);
@@ -574,28 +518,18 @@ __global__ __launch_bounds__(256, GATE_MIN_BLOCKS(LPR, HMAX, CH)) void gate_fuse
                                                          float *__restrict__ out, const int64_t ldo,
                                                          float *__restrict__ wout, const int64_t ldw, float *__restrict__ gout,
                                                          const int64_t ldg, const int64_t n, const int d, const int dw) {
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     const float bias = bias_ptr ? *bias_ptr : bias_arg;       // a bias that lives on the device is read here: no host round trip
     f4 x[HMAX][CH], vv[CH];
     bool on[CH];
 #pragma unroll
+    for (int c = 0; c < CH; ++c) on[c] = chunk_on<LPR>(c, l, live, d);
+#pragma unroll
     for (int c = 0; c < CH; ++c) {
         const int col = (c * LPR + l) * 4;
-        on[c] = live && col < d;
         vv[c] = (col < d) ? load_masked<4>(vec, col, d) : (f4){0.f, 0.f, 0.f, 0.f};
     }
-#pragma unroll
-    for (int h = 0; h < HMAX; ++h) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            x[h][c] = (f4){0.f, 0.f, 0.f, 0.f};
-            if (h < n_hops && on[c]) x[h][c] = load_masked<4, true>(hx.p[h] + r * hx.ld[h], (c * LPR + l) * 4, d);
-        }
-    }
+    load_hop_rows<load_masked<4, true>, LPR>(x, hx, n_hops, r, on, l, d);
     f4 acc[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) acc[c] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -604,12 +538,7 @@ __global__ __launch_bounds__(256, GATE_MIN_BLOCKS(LPR, HMAX, CH)) void gate_fuse
         float sl = 0.f;
 #pragma unroll
         for (int h = 0; h < HMAX; ++h) {
-            float sc = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sc = __builtin_fmaf(vv[c][e], x[h][c][e], sc);
-            sc = group_sum<LPR>(sc);
+            const float sc = group_sum<LPR>(dot_chunks(vv, x[h]));
             sl = (l == h) ? sc : sl;
         }
         const bool mine = l < n_hops;
@@ -630,20 +559,12 @@ __global__ __launch_bounds__(256, GATE_MIN_BLOCKS(LPR, HMAX, CH)) void gate_fuse
             if (h < n_hops) {
                 const float w = from_lane<LPR>(wl, h);
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __builtin_fmaf(w, x[h][c][e], acc[c][e]);
+                for (int c = 0; c < CH; ++c) acc[c] = fma4(acc[c], w, x[h][c]);
             }
     } else {
         float score[HMAX];
 #pragma unroll
-        for (int h = 0; h < HMAX; ++h) {
-            score[h] = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) score[h] = __builtin_fmaf(vv[c][e], x[h][c][e], score[h]);
-        }
+        for (int h = 0; h < HMAX; ++h) score[h] = dot_chunks(vv, x[h]);
 #pragma unroll
         for (int h = 0; h < HMAX; ++h) score[h] = group_sum<LPR>(score[h]);   // independent chains: interleaved by the scheduler
         float run_max = -INFINITY;
@@ -668,9 +589,7 @@ __global__ __launch_bounds__(256, GATE_MIN_BLOCKS(LPR, HMAX, CH)) void gate_fuse
                 const float w = __fdiv_rn(score[h], sum);
                 if (wout && live && l == 0) wout[r * ldw + h] = w;
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __builtin_fmaf(w, x[h][c][e], acc[c][e]);
+                for (int c = 0; c < CH; ++c) acc[c] = fma4(acc[c], w, x[h][c]);
             }
     }
     store_row<LPR, CH>(out + r * ldo, acc, l, live, d, dw);
@@ -695,29 +614,19 @@ __global__ __launch_bounds__(256, RECUR_MIN_BLOCKS(LPR, HMAX, CH)) void recursiv
                                                               float *__restrict__ wout, const int64_t ldw, float *__restrict__ aout,
                                                               const int64_t lda, float *__restrict__ cout, const int64_t ldc,
                                                               const int64_t n, const int d, const int dw) {
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     const float bias = bias_ptr ? *bias_ptr : bias_arg;
     f4 x[HMAX][CH], vx[CH], va[CH];
     bool on[CH];
 #pragma unroll
+    for (int c = 0; c < CH; ++c) on[c] = chunk_on<LPR>(c, l, live, d);
+#pragma unroll
     for (int c = 0; c < CH; ++c) {
         const int col = (c * LPR + l) * 4;
-        on[c] = live && col < d;
         vx[c] = (col < d) ? load_masked<4>(vec, col, d) : (f4){0.f, 0.f, 0.f, 0.f};
         va[c] = (col < d) ? load_masked<4>(vec + dv, col, d) : (f4){0.f, 0.f, 0.f, 0.f};
     }
-#pragma unroll
-    for (int h = 0; h < HMAX; ++h) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            x[h][c] = (f4){0.f, 0.f, 0.f, 0.f};
-            if (h < n_hops && on[c]) x[h][c] = load_masked<4, true>(hx.p[h] + r * hx.ld[h], (c * LPR + l) * 4, d);
-        }
-    }
+    load_hop_rows<load_masked<4, true>, LPR>(x, hx, n_hops, r, on, l, d);
     f4 acc[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) acc[c] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -726,14 +635,8 @@ __global__ __launch_bounds__(256, RECUR_MIN_BLOCKS(LPR, HMAX, CH)) void recursiv
         float al = 0.f, cl = 0.f;
 #pragma unroll
         for (int h = 0; h < HMAX; ++h) {
-            float sa = 0.f, sc = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    sa = __builtin_fmaf(vx[c][e], x[h][c][e], sa);
-                    sc = __builtin_fmaf(va[c][e], x[h][c][e], sc);
-                }
+            float sa, sc;
+            dot2_chunks(vx, va, x[h], sa, sc);
             sa = group_sum<LPR>(sa);
             sc = group_sum<LPR>(sc);
             al = (l == h) ? sa : al;
@@ -764,22 +667,14 @@ __global__ __launch_bounds__(256, RECUR_MIN_BLOCKS(LPR, HMAX, CH)) void recursiv
             if (h < n_hops) {
                 const float w = from_lane<LPR>(wl, h);
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __builtin_fmaf(w, x[h][c][e], acc[c][e]);
+                for (int c = 0; c < CH; ++c) acc[c] = fma4(acc[c], w, x[h][c]);
             }
     } else {
         float a[HMAX], cc[HMAX], w[HMAX];
 #pragma unroll
         for (int h = 0; h < HMAX; ++h) {
-            float sa = 0.f, sc = 0.f;
-#pragma unroll
-            for (int c = 0; c < CH; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    sa = __builtin_fmaf(vx[c][e], x[h][c][e], sa);
-                    sc = __builtin_fmaf(va[c][e], x[h][c][e], sc);
-                }
+            float sa, sc;
+            dot2_chunks(vx, va, x[h], sa, sc);
             a[h] = group_sum<LPR>(sa);
             cc[h] = group_sum<LPR>(sc);
             w[h] = 0.f;
@@ -813,9 +708,7 @@ __global__ __launch_bounds__(256, RECUR_MIN_BLOCKS(LPR, HMAX, CH)) void recursiv
                     if (cout) cout[r * ldc + h] = cc[h];
                 }
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __builtin_fmaf(w[h], x[h][c][e], acc[c][e]);
+                for (int c = 0; c < CH; ++c) acc[c] = fma4(acc[c], w[h], x[h][c]);
             }
     }
     store_row<LPR, CH>(out + r * ldo, acc, l, live, d, dw);
@@ -906,7 +799,6 @@ __global__ __launch_bounds__(256) void hop_rowdot2_reg_kernel(const Hops hx, con
                                                               const float *__restrict__ vec, const int h0, const int h1,
                                                               float *__restrict__ p, const int64_t ldp, float *__restrict__ a,
                                                               const int64_t n, const int d) {
-    constexpr int RPB = 256 / LPR;
     constexpr int SLOTS = LPR * CH;                 // 16-byte slots of a row this layout reaches
     // U is the same for every row: staged in LDS once per block (H x SLOTS vectors, a few KB) instead of H x CH global loads per
     // lane -- those doubled the kernel's L1 accesses and made it the slowest of the row kernels (jk scores at d = 147: 0.48 of
@@ -917,15 +809,12 @@ __global__ __launch_bounds__(256) void hop_rowdot2_reg_kernel(const Hops hx, con
         us[h][i - h * SLOTS] = (h < n_hops && ((u_mask >> h) & 1ull) && col < d) ? load_masked<4>(u + (int64_t)h * ldu, col, d)
                                                                                   : (f4){0.f, 0.f, 0.f, 0.f};
     }
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     f4 x[HMAX][CH], vv[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
         const int col = (c * LPR + l) * 4;
-        const bool on = live && col < d;
+        const bool on = chunk_on<LPR>(c, l, live, d);
         vv[c] = (col < d) ? load_masked<4>(vec, col, d) : (f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int h = 0; h < HMAX; ++h)
@@ -936,18 +825,10 @@ __global__ __launch_bounds__(256) void hop_rowdot2_reg_kernel(const Hops hx, con
     float shared = 0.f;
 #pragma unroll
     for (int h = 0; h < HMAX; ++h) {
-        acc[h] = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[h] = __builtin_fmaf(vv[c][e], x[h][c][e], acc[h]);
+        acc[h] = dot_chunks(vv, x[h]);
         if (h < n_hops && ((u_mask >> h) & 1ull)) {
 #pragma unroll
-            for (int c = 0; c < CH; ++c) {
-                const f4 uv = us[h][c * LPR + l];   // zeros beyond d
-#pragma unroll
-                for (int e = 0; e < 4; ++e) shared = __builtin_fmaf(uv[e], x[h][c][e], shared);
-            }
+            for (int c = 0; c < CH; ++c) shared = dot4(us[h][c * LPR + l], x[h][c], shared);   // U: zeros beyond d
         }
     }
 #pragma unroll
@@ -1636,28 +1517,26 @@ SGL_EXPORT int sgl_hop_wsum2d_f32(int n_hops, const float *const *h_x, const int
     return wsum2d_impl(true, n_hops, h_x, h_ldx, d_w, ldw, d_out, ldo, n, d, stream);
 }
 
-// dW / gate scores of `who`: the register-resident kernel where the row's H hop vectors fit, else the general row-dot
+// dW / gate scores of `who`: the register-resident kernel where the row's H hop vectors fit, else the general row-dot; `check`
+// names the launch in "kernel launch failed"
 template <int VEC>
-static int launch_rowdot(const char *who, int lpr, bool g_unaligned, hipStream_t st, const Hops &hx, int n_hops, const float *g,
-                         int64_t ldg, float *dw, int64_t lddw, int64_t n, int d) {
+static int launch_rowdot(const char *who, const char *check, int lpr, bool g_unaligned, hipStream_t st, const Hops &hx, int n_hops,
+                         const float *g, int64_t ldg, float *dw, int64_t lddw, int64_t n, int d) {
     if constexpr (VEC == 4) {
         // the row's H hop vectors fit in registers: one load of dOut, all loads in flight, interleaved butterflies
         const sgl::RowInstance in = sgl::row_instance(d, n_hops);
-        if (n_hops <= 16 && d <= in.lpr * 4 * in.ch) {
-            const unsigned grid = (unsigned)((n + (256 / in.lpr) - 1) / (256 / in.lpr));
-            const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
+        if (n_hops <= 16 && d <= in.lpr * 4 * in.ch)
+            return launch_row_instance({who, who, check}, in, n_hops, n, [&](dim3 grid, auto L, auto C, auto HM) {
                 with_bool(g_unaligned, [&](auto GU) {
-                    hipLaunchKernelGGL((hop_rowdot_reg_kernel<L, C, HM, GU>), dim3(grid), dim3(256), 0, st, hx, n_hops, g, ldg, dw, lddw, n, d);
+                    hipLaunchKernelGGL((hop_rowdot_reg_kernel<L, C, HM, GU>), grid, dim3(256), 0, st, hx, n_hops, g, ldg, dw, lddw, n, d);
                 });
             });
-            return ok ? SGL_OK : no_row_instance(who, in.lpr, in.ch, n_hops);
-        }
     }
     with_lpr(lpr, [&](auto L) {
         hipLaunchKernelGGL((hop_rowdot_kernel<L, VEC>), dim3((unsigned)((n + (256 / L) - 1) / (256 / L))), dim3(256), 0, st, hx, n_hops, g,
                            ldg, dw, lddw, n, d);
     });
-    return SGL_OK;
+    return launch_check(check);
 }
 
 SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_w,
@@ -1682,10 +1561,10 @@ SGL_EXPORT int sgl_hop_wsum2d_bwd_f32(int n_hops, const float *const *h_x, const
         SGL_REQUIRE(lddw >= n_hops, "sgl_hop_wsum2d_bwd_f32: lddw < n_hops");
         const int lpr = sgl::pick_lpr(d, row4 ? 4 : 1);
         SGL_REQUIRE((n + (256 / lpr) - 1) / (256 / lpr) < INT32_MAX, "sgl_hop_wsum2d_bwd_f32: too many rows");
-        rc = row4 ? launch_rowdot<4>("sgl_hop_wsum2d_bwd_f32", lpr, g_unaligned, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d)
-                  : launch_rowdot<1>("sgl_hop_wsum2d_bwd_f32", lpr, false, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d);
+        static const char *who = "sgl_hop_wsum2d_bwd_f32", *check = "sgl_hop_wsum2d_bwd_f32(dW)";
+        rc = row4 ? launch_rowdot<4>(who, check, lpr, g_unaligned, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d)
+                  : launch_rowdot<1>(who, check, lpr, false, st, hx, n_hops, d_dout, lddo, d_dw, lddw, n, (int)d);
         if (rc != SGL_OK) return rc;
-        SGL_LAUNCH_CHECK("sgl_hop_wsum2d_bwd_f32(dW)");
     }
     if (h_dx) {
         SGL_REQUIRE(d_w && ldw >= n_hops, "sgl_hop_wsum2d_bwd_f32: dX needs W");
@@ -1728,11 +1607,9 @@ SGL_EXPORT int sgl_hop_rowdot_f32(int n_hops, const float *const *h_x, const int
     // (callers pass a zero-padded copy), the masked tail ignores what lies beyond d
     const int lpr = sgl::pick_lpr(d, row4 ? 4 : 1);
     SGL_REQUIRE((n + (256 / lpr) - 1) / (256 / lpr) < INT32_MAX, "sgl_hop_rowdot_f32: too many rows");
-    rc = row4 ? launch_rowdot<4>("sgl_hop_rowdot_f32", lpr, false, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d)
-              : launch_rowdot<1>("sgl_hop_rowdot_f32", lpr, false, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d);
-    if (rc != SGL_OK) return rc;
-    SGL_LAUNCH_CHECK("sgl_hop_rowdot_f32");
-    return SGL_OK;
+    static const char *who = "sgl_hop_rowdot_f32";
+    return row4 ? launch_rowdot<4>(who, who, lpr, false, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d)
+                : launch_rowdot<1>(who, who, lpr, false, st, hx, n_hops, d_vec, 0, d_out, ldo, n, (int)d);
 }
 
 SGL_EXPORT int64_t sgl_hop_wsum1d_bwd_scratch(int n_hops) { return (int64_t)kW1dBlocks * (n_hops > 0 ? n_hops : 1); }
@@ -1917,15 +1794,11 @@ SGL_EXPORT int sgl_nafs_padded_f32(int n_hops, const float *const *h_x, const in
     // single-pass kernel: the H hop rows of a node fit in registers (H <= 16, d <= 512, 16-byte lanes)
     const bool out_vec4 = d_out && (ldo % 4 == 0) && aligned_to(d_out, 16);
     if (vec4 && out_vec4 && n_hops <= 16 && d <= 512 && sgl::tuning("nafs_fused", 1) != 0) {
-        const sgl::RowInstance in = sgl::row_instance(d, n_hops);
-        const int64_t nblocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
-        const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
-            hipLaunchKernelGGL((nafs_fused_kernel<L, C, HM>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n,
-                               (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+        return launch_row_instance({"row-wise kernel", "sgl_nafs_f32", "sgl_nafs_f32(fused)"}, sgl::row_instance(d, n_hops), n_hops, n,
+                                   [&](dim3 grid, auto L, auto C, auto HM) {
+            hipLaunchKernelGGL((nafs_fused_kernel<L, C, HM>), grid, dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n, (int)d,
+                               sgl::out_cols(d, pad_cols, L * C * 4));
         });
-        if (!ok) return no_row_instance("sgl_nafs_f32", in.lpr, in.ch, n_hops);
-        SGL_LAUNCH_CHECK("sgl_nafs_f32(fused)");
-        return SGL_OK;
     }
     with_lpr_vec(lpr, vec4, [&](auto L, auto V) {
         hipLaunchKernelGGL((nafs_weight_kernel<L, V>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_w_out, ldw, n, (int)d);
@@ -1966,16 +1839,11 @@ SGL_EXPORT int sgl_nafs_prefix_f32(int n_hops, const float *const *h_x, const in
     if (rc != SGL_OK) return rc;
     if (n == 0 || d == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
-    const sgl::RowLayout lay = sgl::row_layout(d, 1);
-    const int64_t nblocks = (n + (256 / lay.lpr) - 1) / (256 / lay.lpr);
-    if (!sgl::launch_fits(nblocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "row-wise kernel: too many rows for one launch (shard the matrix)");
-    const bool ok = with_row_layout<false>(lay.lpr, lay.ch, [&](auto L, auto C) {
-        hipLaunchKernelGGL((nafs_prefix_kernel<L, C>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, emit_mask, outs, combine, divisor, n,
-                           (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    return launch_row_layout({"row-wise kernel", "sgl_nafs_prefix_f32", "sgl_nafs_prefix_f32"}, sgl::row_layout(d, 1), n_hops, n,
+                             [&](dim3 grid, auto L, auto C) {
+        hipLaunchKernelGGL((nafs_prefix_kernel<L, C>), grid, dim3(256), 0, st, hx, n_hops, emit_mask, outs, combine, divisor, n, (int)d,
+                           sgl::out_cols(d, pad_cols, L * C * 4));
     });
-    if (!ok) return no_row_instance("sgl_nafs_prefix_f32", lay.lpr, lay.ch, n_hops);
-    SGL_LAUNCH_CHECK("sgl_nafs_prefix_f32");
-    return SGL_OK;
 }
 
 static int copy_rows(const char *who, const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, const int64_t *d_dst,
@@ -2193,21 +2061,16 @@ static int hop_gate_impl(bool device_bias_sentinel, int n_hops, const float *con
     if (!(vec4 && n_hops <= 16 && d <= 512 && ldo % 4 == 0 && aligned_to(d_out, 16)))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_gate_f32: needs <= 16 hops, d <= 512 and 16-byte aligned rows (use the two-pass route)");
     hipStream_t st = sgl::as_stream(stream);
-    const sgl::RowInstance in = sgl::row_instance(d, n_hops);
-    const int64_t blocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
-    if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_gate_f32: too many rows for one launch (shard the matrix)");
     // bias = NaN: the bias is the float that follows the padded vector on the device (d_vec[round_up(d, 4)]) -- a caller whose
     // bias is a device tensor (a torch parameter) needs neither a device-to-host synchronisation nor a new value per launch
     // Only the *_padded entry point reads it that way: a caller of the un-suffixed sgl_hop_gate_f32 whose d_vec holds exactly
     // round_up(d, 4) floats and whose (diverged) bias is NaN gets NaN outputs, as the scalar semantics say, not a read past its vector.
     const float *bias_ptr = (device_bias_sentinel && bias != bias) ? d_vec + (d + 3) / 4 * 4 : nullptr;
-    const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
-        hipLaunchKernelGGL((gate_fused_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_vec, bias, bias_ptr, d_out, ldo,
-                           d_w_out, ldw, d_g_out, ldg, n, (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    static const char *who = "sgl_hop_gate_f32";
+    return launch_row_instance({who, who, who}, sgl::row_instance(d, n_hops), n_hops, n, [&](dim3 grid, auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((gate_fused_kernel<L, C, HM>), grid, dim3(256), 0, st, hx, n_hops, d_vec, bias, bias_ptr, d_out, ldo, d_w_out, ldw,
+                           d_g_out, ldg, n, (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
     });
-    if (!ok) return no_row_instance("sgl_hop_gate_f32", in.lpr, in.ch, n_hops);
-    SGL_LAUNCH_CHECK("sgl_hop_gate_f32");
-    return SGL_OK;
 }
 
 SGL_EXPORT int sgl_hop_gate_padded_f32(int n_hops, const float *const *h_x, const int64_t *h_ldx, const float *d_vec, float bias,
@@ -2244,18 +2107,13 @@ SGL_EXPORT int sgl_hop_recursive_f32(int n_hops, const float *const *h_x, const 
     if (!(vec4 && n_hops <= 16 && d <= 512 && ldo % 4 == 0 && aligned_to(d_out, 16)))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_recursive_f32: needs <= 16 hops, d <= 512 and 16-byte aligned rows (use the step-by-step route)");
     hipStream_t st = sgl::as_stream(stream);
-    const sgl::RowInstance in = sgl::row_instance(d, n_hops);
-    const int64_t blocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
-    if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_recursive_f32: too many rows for one launch (shard the matrix)");
     const int dv = (int)((d + 3) / 4 * 4);
     const float *bias_ptr = (bias != bias) ? d_vec + 2 * dv : nullptr;
-    const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
-        hipLaunchKernelGGL((recursive_fused_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_vec, dv, bias, bias_ptr, d_out,
-                           ldo, d_w_out, ldw, d_a_out, lda, d_c_out, ldc, n, (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    static const char *who = "sgl_hop_recursive_f32";
+    return launch_row_instance({who, who, who}, sgl::row_instance(d, n_hops), n_hops, n, [&](dim3 grid, auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((recursive_fused_kernel<L, C, HM>), grid, dim3(256), 0, st, hx, n_hops, d_vec, dv, bias, bias_ptr, d_out, ldo, d_w_out,
+                           ldw, d_a_out, lda, d_c_out, ldc, n, (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
     });
-    if (!ok) return no_row_instance("sgl_hop_recursive_f32", in.lpr, in.ch, n_hops);
-    SGL_LAUNCH_CHECK("sgl_hop_recursive_f32");
-    return SGL_OK;
 }
 
 // backward of the [n, H] recursion of sgl_hop_recursive_f32 (recursive_scalar_bwd_kernel): dA, dC [n, H] and the per-row bias
@@ -2296,17 +2154,12 @@ SGL_EXPORT int sgl_hop_rowdot2_f32(int n_hops, const float *const *h_x, const in
     if (!(vec4 && n_hops <= 16 && d <= 512 && d > 0))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_rowdot2_f32: needs <= 16 hops, 0 < d <= 512 and 16-byte aligned rows");
     hipStream_t st = sgl::as_stream(stream);
-    const sgl::RowInstance in = sgl::row_instance(d, n_hops, true);
-    const int64_t blocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
-    if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_hop_rowdot2_f32: too many rows for one launch (shard the matrix)");
     float *a_out = u_mask ? d_a : nullptr;
-    const bool ok = with_row_instance<true>(in, [&](auto L, auto C, auto HM) {
-        hipLaunchKernelGGL((hop_rowdot2_reg_kernel<L, C, HM>), dim3((unsigned)blocks), dim3(256), 0, st, hx, n_hops, d_u, ldu,
-                           (unsigned long long)u_mask, d_vec, h0, h1, d_p, ldp, a_out, n, (int)d);
+    static const char *who = "sgl_hop_rowdot2_f32";
+    return launch_row_instance<true>({who, who, who}, sgl::row_instance(d, n_hops, true), n_hops, n, [&](dim3 grid, auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((hop_rowdot2_reg_kernel<L, C, HM>), grid, dim3(256), 0, st, hx, n_hops, d_u, ldu, (unsigned long long)u_mask, d_vec,
+                           h0, h1, d_p, ldp, a_out, n, (int)d);
     });
-    if (!ok) return no_row_instance("sgl_hop_rowdot2_f32", in.lpr, in.ch, n_hops);
-    SGL_LAUNCH_CHECK("sgl_hop_rowdot2_f32");
-    return SGL_OK;
 }
 
 // ---- weight gradients of the row-dots ----------------------------------------------------------------------------------------

@@ -252,23 +252,12 @@ template <int LPR, int CH, int HMAX>
 __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fused_kernel(const HopsB hx, const int n_hops, float *__restrict__ out,
                                                          const int64_t ldo, float *__restrict__ wout, const int64_t ldw,
                                                          const int64_t n, const int d, const int dw) {
-    constexpr int RPB = 256 / LPR;
-    const int l = threadIdx.x % LPR;
-    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-    const bool live = row < n;
-    const int64_t r = live ? row : 0;
+    const auto [l, r, live] = row_lane<LPR>(n);
     f4 x[HMAX][CH];
     bool on[CH];
 #pragma unroll
-    for (int c = 0; c < CH; ++c) on[c] = live && ((c * LPR + l) * 4 < d);
-#pragma unroll
-    for (int h = 0; h < HMAX; ++h) {
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            x[h][c] = (f4){0.f, 0.f, 0.f, 0.f};
-            if (h < n_hops && on[c]) x[h][c] = load_bf16x4_masked(hx.p[h] + r * hx.ld[h], (c * LPR + l) * 4, d);
-        }
-    }
+    for (int c = 0; c < CH; ++c) on[c] = chunk_on<LPR>(c, l, live, d);
+    load_hop_rows<load_bf16x4_masked, LPR>(x, hx, n_hops, r, on, l, d);
     f4 acc[CH];
 #pragma unroll
     for (int c = 0; c < CH; ++c) acc[c] = (f4){0.f, 0.f, 0.f, 0.f};
@@ -278,14 +267,8 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fu
 #pragma unroll
         for (int h = 0; h < HMAX; ++h)
             if (h < n_hops) {
-                float dot = 0.f, sq = 0.f;
-#pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        dot = __builtin_fmaf(x[0][c][e], x[h][c][e], dot);
-                        sq = __builtin_fmaf(x[h][c][e], x[h][c][e], sq);
-                    }
+                float dot, sq;
+                dot_sq_chunks(x[0], x[h], dot, sq);
                 dot = group_sum<LPR>(dot);
                 sq = group_sum<LPR>(sq);
                 dl = (l == h) ? dot : dl;
@@ -308,9 +291,7 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fu
             if (h < n_hops) {
                 const float w = from_lane<LPR>(wl, h);
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __fadd_rn(acc[c][e], __fmul_rn(w, x[h][c][e]));
+                for (int c = 0; c < CH; ++c) acc[c] = mul_add4(acc[c], w, x[h][c]);
             }
     } else {
         float score[HMAX];
@@ -319,14 +300,8 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fu
         for (int h = 0; h < HMAX; ++h) {
             score[h] = -INFINITY;
             if (h < n_hops) {
-                float dot = 0.f, sq = 0.f;
-#pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        dot = __builtin_fmaf(x[0][c][e], x[h][c][e], dot);
-                        sq = __builtin_fmaf(x[h][c][e], x[h][c][e], sq);
-                    }
+                float dot, sq;
+                dot_sq_chunks(x[0], x[h], dot, sq);
                 dot = group_sum<LPR>(dot);
                 sq = group_sum<LPR>(sq);
                 const float nh = __fadd_rn(__fsqrt_rn(sq), 1e-10f);
@@ -348,9 +323,7 @@ __global__ __launch_bounds__(256, ROWREG_MIN_BLOCKS(HMAX, CH)) void nafs_bf16_fu
                 const float w = __fdiv_rn(score[h], sum);
                 if (wout && live && l == 0) wout[r * ldw + h] = w;
 #pragma unroll
-                for (int c = 0; c < CH; ++c)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[c][e] = __fadd_rn(acc[c][e], __fmul_rn(w, x[h][c][e]));
+                for (int c = 0; c < CH; ++c) acc[c] = mul_add4(acc[c], w, x[h][c]);
             }
     }
     store_row<LPR, CH>(out + r * ldo, acc, l, live, d, dw);
@@ -461,15 +434,9 @@ SGL_EXPORT int sgl_nafs_bf16_f32(int n_hops, const uint16_t *const *h_x, const i
         return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the output needs 16-byte aligned rows on a pitch that is a multiple of 4: widen the hops and use sgl_nafs_padded_f32", who);
     if (sgl::tuning("nafs_fused", 1) == 0)
         return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the fused kernel is switched off (nafs_fused = 0): widen the hops and use sgl_nafs_padded_f32", who);
-    const sgl::RowInstance in = sgl::row_instance(d, n_hops);
-    const int64_t nblocks = (n + (256 / in.lpr) - 1) / (256 / in.lpr);
-    if (!sgl::launch_fits(nblocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: too many rows for one launch (shard the matrix)", who);
     hipStream_t st = sgl::as_stream(stream);
-    const bool ok = with_row_instance<false>(in, [&](auto L, auto C, auto HM) {
-        hipLaunchKernelGGL((nafs_bf16_fused_kernel<L, C, HM>), dim3((unsigned)nblocks), dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n,
-                           (int)d, sgl::out_cols(d, pad_cols, L * C * 4));
+    return launch_row_instance({who, who, who}, sgl::row_instance(d, n_hops), n_hops, n, [&](dim3 grid, auto L, auto C, auto HM) {
+        hipLaunchKernelGGL((nafs_bf16_fused_kernel<L, C, HM>), grid, dim3(256), 0, st, hx, n_hops, d_out, ldo, d_w_out, ldw, n, (int)d,
+                           sgl::out_cols(d, pad_cols, L * C * 4));
     });
-    if (!ok) return no_row_instance(who, in.lpr, in.ch, n_hops);
-    SGL_LAUNCH_CHECK("sgl_nafs_bf16_f32");
-    return SGL_OK;
 }

@@ -168,6 +168,102 @@ __device__ __forceinline__ void store_row(float *__restrict__ orow, const f4 (&a
     }
 }
 
+// ---- the steps of a row kernel: LPR lanes per row, 256 / LPR rows per workgroup, CH 16-byte chunks per lane -------------------------
+// Each step is written once, here.  The register-resident kernels sit at register boundaries that the source layout disturbs, and a
+// forced-inline helper is optimised on its own before it is inlined, so the shape of each one was chosen against the per-kernel
+// register table of the hand-written loops: the mask and the accumulate work on ONE chunk by value (filling
+// `bool (&on)[CH]` in a helper moved 48 instances, `acc[CH]` by reference in mul_add 19), the hop table is passed by value.
+struct RowLane {
+    int l;         // this lane's place in the row's group of LPR lanes
+    int64_t r;     // the group's row; row 0 where the group lies beyond the matrix, so that every address formed from it is valid
+    bool live;     // the group has a row
+};
+template <int LPR>
+__device__ __forceinline__ RowLane row_lane(const int64_t n) {
+    constexpr int RPB = 256 / LPR;  // rows per block
+    const int l = threadIdx.x % LPR;
+    const int64_t row = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+    const bool live = row < n;
+    return {l, live ? row : 0, live};
+}
+
+// chunk c of this lane (the four columns from (c * LPR + l) * 4) belongs to a row and starts inside its d columns
+template <int LPR>
+__device__ __forceinline__ bool chunk_on(const int c, const int l, const bool live, const int d) {
+    return live && ((c * LPR + l) * 4 < d);
+}
+
+// x[h][c] = chunk c of row r of hop h for the first n_hops hops of the table, zeros elsewhere.  LOAD(row, col, d): the masked 16-byte
+// access of the table's element type (load_masked<4, NT>; sgl_aggregate_bf16.hip has the widening one).  The row address is formed
+// under `h < n_hops` only: formed for every h < HMAX it cost 21 instances occupancy and put 3 into scratch.  hop_rowdot_reg_kernel
+// and hop_rowdot2_reg_kernel keep their own chunk-outer loop: this hop-outer one raised their registers in every instance.
+template <auto LOAD, int LPR, int CH, int HMAX, typename Table>
+__device__ __forceinline__ void load_hop_rows(f4 (&x)[HMAX][CH], const Table hx, const int n_hops, const int64_t r, const bool (&on)[CH],
+                                              const int l, const int d) {
+#pragma unroll
+    for (int h = 0; h < HMAX; ++h) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            x[h][c] = (f4){0.f, 0.f, 0.f, 0.f};
+            if (h < n_hops && on[c]) x[h][c] = LOAD(hx.p[h] + r * hx.ld[h], (c * LPR + l) * 4, d);
+        }
+    }
+}
+
+// this lane's part of <a, b> on top of s: one FMA chain in chunk and element order (the group_sum over the row's lanes follows)
+__device__ __forceinline__ float dot4(const f4 a, const f4 b, float s) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s = __builtin_fmaf(a[e], b[e], s);
+    return s;
+}
+template <int CH>
+__device__ __forceinline__ float dot_chunks(const f4 (&a)[CH], const f4 (&b)[CH]) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c) s = dot4(a[c], b[c], s);
+    return s;
+}
+// dot = <a, b> and sq = <b, b>, the two chains interleaved element by element
+template <int CH>
+__device__ __forceinline__ void dot_sq_chunks(const f4 (&a)[CH], const f4 (&b)[CH], float &dot, float &sq) {
+    dot = 0.f;
+    sq = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            dot = __builtin_fmaf(a[c][e], b[c][e], dot);
+            sq = __builtin_fmaf(b[c][e], b[c][e], sq);
+        }
+}
+// s0 = <a0, b> and s1 = <a1, b>: two vectors against one row, interleaved
+template <int CH>
+__device__ __forceinline__ void dot2_chunks(const f4 (&a0)[CH], const f4 (&a1)[CH], const f4 (&b)[CH], float &s0, float &s1) {
+    s0 = 0.f;
+    s1 = 0.f;
+#pragma unroll
+    for (int c = 0; c < CH; ++c)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s0 = __builtin_fmaf(a0[c][e], b[c][e], s0);
+            s1 = __builtin_fmaf(a1[c][e], b[c][e], s1);
+        }
+}
+
+// acc + w x on one chunk, in the two forms the operators define -- they round differently and are not interchangeable:
+// one FMA per element (the learnable gates: the chain of hop_wsum2d_kernel) ...
+__device__ __forceinline__ f4 fma4(f4 acc, const float w, const f4 x) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(w, x[e], acc[e]);
+    return acc;
+}
+// ... or a rounded product, then the add (NAFS, by contract: over_smooth_distance_op.py:27-31 multiplies, then sums)
+__device__ __forceinline__ f4 mul_add4(f4 acc, const float w, const f4 x) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = __fadd_rn(acc[e], __fmul_rn(w, x[e]));
+    return acc;
+}
+
 // ---- host side: run-time values as compile-time arguments of a generic lambda ----------------------------------------------------
 // Each helper calls f with std::integral_constant arguments (usable as template arguments inside the lambda) and returns whether it
 // called it: a value with no compiled instance launches nothing and the entry point reports it.
@@ -272,5 +368,32 @@ inline int launch_check(const char *who) {
         const int _rc = launch_check(who);  \
         if (_rc != SGL_OK) return _rc;      \
     } while (0)
+
+// The launch of a register-resident row kernel over n rows, from the instance (or layout) that sgl_core.cpp picked to the checked
+// launch: grid of 256 / lpr rows per workgroup, launch_fits, typed dispatch, no_row_instance, launch check.  launch(grid, LPR, CH[,
+// HMAX]) starts the kernel.  The texts are the entry point's own: `rows` names it in "too many rows", `who` in "no kernel instance",
+// `check` in "kernel launch failed".
+struct RowLaunchNames {
+    const char *rows, *who, *check;
+};
+template <typename Dispatch>
+int launch_rows_with(const RowLaunchNames &names, int lpr, int ch, int n_hops, int64_t n, Dispatch &&dispatch) {
+    const int64_t blocks = (n + (256 / lpr) - 1) / (256 / lpr);
+    if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: too many rows for one launch (shard the matrix)", names.rows);
+    if (!dispatch(dim3((unsigned)blocks))) return no_row_instance(names.who, lpr, ch, n_hops);
+    return launch_check(names.check);
+}
+template <bool HAS_8X5 = false, typename F>
+int launch_row_instance(const RowLaunchNames &names, const sgl::RowInstance &in, int n_hops, int64_t n, F &&launch) {
+    return launch_rows_with(names, in.lpr, in.ch, n_hops, n, [&](dim3 grid) {
+        return with_row_instance<HAS_8X5>(in, [&](auto L, auto C, auto HM) { launch(grid, L, C, HM); });
+    });
+}
+template <typename F>
+int launch_row_layout(const RowLaunchNames &names, const sgl::RowLayout &lay, int n_hops, int64_t n, F &&launch) {
+    return launch_rows_with(names, lay.lpr, lay.ch, n_hops, n, [&](dim3 grid) {
+        return with_row_layout<false>(lay.lpr, lay.ch, [&](auto L, auto C) { launch(grid, L, C); });
+    });
+}
 
 }  // namespace
