@@ -162,6 +162,18 @@ PROTOTYPES = {
 }
 
 
+# include/sgl_ensemble.h: K16, the sub-graph ensemble aggregators of the heterogeneous models -- a header and a table of their own, bound on
+# the handle lib() returns (the symbols live in libsgl_hip.so)
+SGL_ENSEMBLE_MAX_GROUP, SGL_ENSEMBLE_MAX_MEMBERS = 64, 256
+ENSEMBLE_PROTOTYPES = {
+    "sgl_ensemble_combine_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_float,
+                                         c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "sgl_ensemble_combine_bwd_scratch": (c_int64, [c_int, c_int, c_int64, c_int64, c_int]),
+    "sgl_ensemble_combine_bwd_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int, c_float,
+                                             c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+}
+
+
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
 PROBE_PROTOTYPES = {
@@ -190,7 +202,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m sgl_amd.csrc.build` (needs hipcc). "
                 "sgl_amd has no CPU fallback for the propagation hot path.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

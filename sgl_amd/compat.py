@@ -14,6 +14,8 @@ What is registered in sys.modules (the modules a reference model file imports, s
 
     sgl.operators, sgl.operators.base_op, sgl.operators.utils, sgl.operators.graph_op, sgl.operators.message_op   -> sgl_amd.operators.*
     sgl.models.base_model, sgl.models.simple_models                                                                 -> sgl_amd.models.*
+    sgl.models.hetero                      with reference_root a shell like sgl.models.homo (the reference's nars_sign.py and
+                                           fast_nars_sgc.py run unchanged); without one sgl_amd.models.hetero itself
     sgl, sgl.models, sgl.models.homo       namespace shells (created only if the name is not imported yet); with reference_root their
                                            __path__ points INTO the reference checkout, so `sgl.models.homo.<file>` is found there --
                                            without running the reference's package __init__ files (sgl/__init__.py pulls in the
@@ -37,6 +39,10 @@ _ALIASES = {
     "sgl.models.simple_models": "sgl_amd.models.simple_models",
 }
 _SHELLS = {"sgl": "sgl", "sgl.models": os.path.join("sgl", "models"), "sgl.models.homo": os.path.join("sgl", "models", "homo")}
+# sgl.models.hetero: with reference_root a shell like sgl.models.homo (the reference's nars_sign.py / fast_nars_sgc.py are found there and
+# build on the aliased base_model / simple_models); without one the sgl_amd package itself, so `from sgl.models.hetero import NARS_SIGN` works
+_HETERO = ("sgl.models.hetero", os.path.join("sgl", "models", "hetero"), "sgl_amd.models.hetero")
+_FILE_PACKAGES = ("sgl.models.homo", "sgl.models.hetero")
 _installed = []           # names this module put into sys.modules
 
 
@@ -52,7 +58,10 @@ def install(reference_root=None, force=False):
     if real is not None and not getattr(real, "__sgl_amd_shell__", False) and not force:
         raise RuntimeError("a real `sgl` package is already imported; call install() before importing it, or install(force=True) to "
                            "replace its operator / base-model modules with the sgl_amd ones")
-    for name, rel in _SHELLS.items():
+    shells = dict(_SHELLS)
+    if reference_root is not None:
+        shells[_HETERO[0]] = _HETERO[1]
+    for name, rel in shells.items():
         mod = sys.modules.get(name)
         if mod is None:
             mod = types.ModuleType(name)
@@ -77,22 +86,33 @@ def install(reference_root=None, force=False):
         parent, _, leaf = alias.rpartition(".")
         setattr(sys.modules[parent], leaf, mod)
         done.append(alias)
+    if reference_root is None and _HETERO[0] not in sys.modules:
+        mod = importlib.import_module(_HETERO[2])
+        sys.modules[_HETERO[0]] = mod
+        _installed.append(_HETERO[0])
+        sys.modules["sgl.models"].hetero = mod
+        done.append(_HETERO[0])
     return done
 
 
 def uninstall():
     """remove what install() registered (modules imported THROUGH the aliases, e.g. sgl.models.homo.sgc, go too)"""
     for name in list(sys.modules):
-        if name.startswith("sgl.models.homo.") and getattr(sys.modules.get("sgl.models.homo"), "__sgl_amd_shell__", False):
-            del sys.modules[name]
+        for pkg in _FILE_PACKAGES:
+            if name.startswith(pkg + ".") and getattr(sys.modules.get(pkg), "__sgl_amd_shell__", False):
+                del sys.modules[name]
     for name in reversed(_installed):
         sys.modules.pop(name, None)
     _installed.clear()
 
 
 def load_reference_model(name, reference_root):
-    """the class `name` (e.g. "GAMLP") of the reference's sgl/models/homo/<file>.py, executed unchanged on top of the sgl_amd
-    operators.  File names follow the reference: lower-case class name (GAMLPRecursive -> gamlp_recursive)."""
+    """the class `name` (e.g. "GAMLP") of the reference's sgl/models/homo/<file>.py (NARS_SIGN, Fast_NARS_SGC_WithLearnableWeights:
+    sgl/models/hetero/<file>.py), executed unchanged on top of the sgl_amd operators.  File names follow the reference: lower-case
+    class name (GAMLPRecursive -> gamlp_recursive)."""
     install(reference_root)
+    hetero = {"NARS_SIGN": "nars_sign", "Fast_NARS_SGC_WithLearnableWeights": "fast_nars_sgc"}
+    if name in hetero:
+        return getattr(importlib.import_module(f"sgl.models.hetero.{hetero[name]}"), name)
     fname = {"GAMLPRecursive": "gamlp_recursive", "PASCA_V1": "pasca_v1", "PASCA_V2": "pasca_v2", "PASCA_V3": "pasca_v3"}.get(name, name.lower())
     return getattr(importlib.import_module(f"sgl.models.homo.{fname}"), name)

@@ -14,11 +14,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libsgl_hip.so")
-SOURCES = ["sgl_core.cpp", "sgl_csr.hip", "sgl_spmm.hip", "sgl_spmm_bf16.hip", "sgl_aggregate.hip", "sgl_aggregate_bf16.hip", "sgl_normalize.hip", "sgl_ingest.hip", "sgl_shims.hip", "sgl_exchange.hip", "sgl_reorder.hip", "sgl_edge.hip", "sgl_edge_loss.hip", "sgl_kmeans.hip", "sgl_cluster_loss.hip", "sgl_class_loss.hip", "sgl_edge_split.hip", "sgl_csr_select.hip", "sgl_csr_merge.hip"]
+SOURCES = ["sgl_core.cpp", "sgl_csr.hip", "sgl_spmm.hip", "sgl_spmm_bf16.hip", "sgl_aggregate.hip", "sgl_aggregate_bf16.hip", "sgl_normalize.hip", "sgl_ingest.hip", "sgl_shims.hip", "sgl_exchange.hip", "sgl_reorder.hip", "sgl_edge.hip", "sgl_edge_loss.hip", "sgl_kmeans.hip", "sgl_cluster_loss.hip", "sgl_class_loss.hip", "sgl_edge_split.hip", "sgl_csr_select.hip", "sgl_csr_merge.hip", "sgl_ensemble.hip"]
 # measurement / test support, a library of its own (include/sgl_probe.h): memory probes, placed allocations, synthetic workloads
 PROBE_LIB = os.path.join(HERE, "libsgl_probe.so")
 PROBE_SOURCES = ["sgl_probe_core.cpp", "sgl_probe.hip", "sgl_synth.hip", "sgl_mem.hip"]
-HEADERS = ["sgl_common.h", "sgl_csr.h", "sgl_spmm_common.h", "sgl_rows.h", "sgl_centres.h", "sgl_hash.h", "sgl_csr_search.h", os.path.join(ROOT, "include", "sgl_hip.h"), os.path.join(ROOT, "include", "sgl_probe.h")]
+HEADERS = ["sgl_common.h", "sgl_csr.h", "sgl_spmm_common.h", "sgl_rows.h", "sgl_centres.h", "sgl_hash.h", "sgl_csr_search.h", os.path.join(ROOT, "include", "sgl_hip.h"), os.path.join(ROOT, "include", "sgl_probe.h"), os.path.join(ROOT, "include", "sgl_ensemble.h")]
 ARCH = "gfx950"
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",

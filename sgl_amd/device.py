@@ -19,7 +19,7 @@ __all__ = [
     "normalize_block", "degree_powers", "PreparedAdjacency", "PreparedBlock",
     "placed_empty", "MEM_MODES",
     "hop_reduce", "hop_concat", "hop_reduce_grad", "hop_concat_grad", "hop_lincomb", "hop_wsum1d", "hop_wsum2d", "hop_scores", "hop_scores2", "hop_gate", "gate_fusable", "nafs_aggregate", "nafs_prefix",
-    "gather_rows", "edge_dot",
+    "gather_rows", "edge_dot", "ensemble_combine",
 ]
 
 
@@ -50,7 +50,7 @@ def _esize(dtype):
 
 # entry points whose last argument is not a stream
 _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
-                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch"})
+                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2128,3 +2128,145 @@ def gather_rows(x, idx, out=None):
         if out.shape != (idx.numel(), x.shape[1]):
             raise ValueError("gather_rows: `out` must be [len(idx), d]")
     return _gather([x], idx, None if out is None else [out])[0]
+
+
+# ---- K16: the sub-graph ensemble aggregators of the heterogeneous models (include/sgl_ensemble.h) -----------------------------------
+def _ensemble_members(groups):
+    """(flat member-major list, n_groups, group_size) of a list of equally long lists of [n_rows, d] float32 CUDA matrices"""
+    groups = [list(g) for g in groups]
+    if not groups or not groups[0] or any(len(g) != len(groups[0]) for g in groups):
+        raise ValueError("ensemble_combine: `groups` must be a non-empty list of equally long, non-empty lists of matrices")
+    flat = [x for g in groups for x in g]
+    for i, x in enumerate(flat):
+        if torch.is_tensor(x) and x.dtype == torch.bfloat16:
+            raise TypeError("ensemble_combine has no bfloat16 form: the propagated matrices of the heterogeneous models are float32")
+        _check_mat(x, f"groups[{i // len(groups[0])}][{i % len(groups[0])}]")
+        if x.requires_grad:
+            raise TypeError("ensemble_combine: the matrices are constants of the model (there is no dX); detach them")
+        if x.shape != flat[0].shape or x.device != flat[0].device:
+            raise ValueError("ensemble_combine: all matrices must have the same shape and device")
+    return flat, len(groups), len(groups[0])
+
+
+def _ensemble_weight_mode(weights, m_total, d):
+    """cs of a member-major weight table: 1 for [M, d] (one weight per matrix and column), 0 for [M] / [M, 1] (one per matrix)"""
+    if not (torch.is_tensor(weights) and weights.is_floating_point()):
+        raise TypeError("ensemble_combine: `weights` must be a floating-point tensor")
+    if weights.dim() == 1 and weights.shape[0] == m_total:
+        return 0
+    if weights.dim() == 2 and weights.shape[0] == m_total and weights.shape[1] == 1 and d != 1:
+        return 0
+    if weights.dim() == 2 and weights.shape == (m_total, d):
+        return 1
+    raise ValueError(f"ensemble_combine: `weights` must be [{m_total}] / [{m_total}, 1] (one per matrix) or [{m_total}, {d}] (one per matrix "
+                     f"and column), not {tuple(weights.shape)}")
+
+
+def _ensemble_outs(out, n_groups, m, d, device):
+    """(the n_groups [m, d] outputs, pad_cols): our own padded buffers, or the caller's -- a list, or one [m, n_groups * d] slab"""
+    if out is None:
+        made = [_alloc_out(m, d, device) for _ in range(n_groups)]
+        return [o for o, _ in made], made[0][1]
+    if torch.is_tensor(out):
+        _check_mat(out, "out")
+        if out.shape != (m, n_groups * d) or out.device != device:
+            raise ValueError("ensemble_combine: a slab `out` must be [len(idx), n_groups * d] on the matrices' device")
+        return [out[:, g * d:(g + 1) * d] for g in range(n_groups)], 0
+    outs = list(out)
+    if len(outs) != n_groups:
+        raise ValueError("ensemble_combine: `out` must hold one matrix per group")
+    for g, o in enumerate(outs):
+        _check_mat(o, f"out[{g}]")
+        if o.shape != (m, d) or o.device != device:
+            raise ValueError("ensemble_combine: every `out` matrix must be [len(idx), d] on the matrices' device")
+    return outs, 0
+
+
+def _ensemble_forward(flat, n_groups, gs, w, cs, idx, divisor, outs, pad):
+    """the launches of sgl_ensemble_combine_f32: one, or one per run of whole groups when there are more matrices than a call takes"""
+    n_rows, d = flat[0].shape
+    device = flat[0].device
+    m = n_rows if idx is None else int(idx.numel())
+    if m == 0 or d == 0:
+        return outs
+    w = w.detach().to(device=device, dtype=torch.float32)
+    if cs:                                   # rows of 16-byte vectors: the kernel then loads a member's weights as it loads its columns
+        w = F.pad(w, (0, round_up(d, 4) - d)) if d % 4 else w.contiguous()
+    else:
+        w = w.reshape(-1, 1).contiguous()
+    ldw = w.stride(0)
+
+    def one(lo, cnt):
+        ptrs, lds = _lib.hop_arrays(flat[lo * gs:(lo + cnt) * gs])
+        optrs, olds = _lib.hop_arrays(outs[lo:lo + cnt])
+        return _call(device, "sgl_ensemble_combine_f32", cnt, gs, ptrs, lds, n_rows, _opt_ptr(idx), m, c_void_p(w.data_ptr() + 4 * ldw * lo * gs),
+                     ldw, cs, float(divisor), optrs, olds, pad, d, raw=True)
+
+    _split_calls("sgl_ensemble_combine_f32", n_groups, one)
+    _wrote(*outs)
+    return outs
+
+
+def _ensemble_backward(flat, n_groups, gs, cs, idx, divisor, gouts):
+    """dW [M, d] (cs = 1) or [M] (cs = 0) of sgl_ensemble_combine_bwd_f32, split like the forward"""
+    n_rows, d = flat[0].shape
+    device = flat[0].device
+    m = n_rows if idx is None else int(idx.numel())
+    dw = torch.zeros((n_groups * gs, d) if cs else (n_groups * gs,), dtype=torch.float32, device=device)
+    if m == 0 or d == 0:
+        return dw
+    gs_rows = [_grad_rows(g, m, d) for g in gouts]
+    lddw = d if cs else 1
+
+    def one(lo, cnt):
+        size = int(_call(None, "sgl_ensemble_combine_bwd_scratch", cnt, gs, m, d, cs, raw=True))
+        scratch = torch.empty(size, dtype=torch.float32, device=device)
+        ptrs, lds = _lib.hop_arrays(flat[lo * gs:(lo + cnt) * gs])
+        gptrs, glds = _lib.hop_arrays(gs_rows[lo:lo + cnt])
+        return _call(device, "sgl_ensemble_combine_bwd_f32", cnt, gs, ptrs, lds, n_rows, _opt_ptr(idx), m, gptrs, glds, cs, float(divisor),
+                     c_void_p(dw.data_ptr() + 4 * lddw * lo * gs), lddw, ptr(scratch), d, raw=True)
+
+    _split_calls("sgl_ensemble_combine_bwd_f32", n_groups, one)
+    return dw
+
+
+class _EnsembleCombine(torch.autograd.Function):
+    """out_g = sum_s X_{g,s}[idx] * W[g,s] / divisor with the weight gradient of sgl_ensemble_combine_bwd_f32; the matrices carry none"""
+
+    @staticmethod
+    def forward(ctx, w, spec, *flat):
+        n_groups, gs, cs, idx, divisor, outs, pad = spec
+        ctx.spec = (n_groups, gs, cs, idx, divisor)
+        ctx.w_shape = w.shape
+        ctx.save_for_backward(*flat)
+        return tuple(_ensemble_forward(list(flat), n_groups, gs, w, cs, idx, divisor, outs, pad))
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        n_groups, gs, cs, idx, divisor = ctx.spec
+        flat = list(ctx.saved_tensors)
+        dw = _ensemble_backward(flat, n_groups, gs, cs, idx, divisor, gouts) if ctx.needs_input_grad[0] else None
+        return (None if dw is None else dw.reshape(ctx.w_shape), None, *([None] * len(flat)))
+
+
+def ensemble_combine(groups, weights, idx=None, divisor=1.0, out=None):
+    """[ sum_s groups[g][s][idx] * weights[g * S + s] / divisor  for g ] in one launch (sgl_ensemble_combine_f32): the aggregators of
+    the heterogeneous models (the reference's *OneDimConvolution, models/simple_models.py:5-84) without the gathered copies, the
+    stack and the product tensor.  groups: n_groups lists of S float32 CUDA matrices [n_rows, d] (row views of padded hop buffers are
+    read in place); weights: member-major, [M, d] (one weight per matrix and column) or [M] / [M, 1] (one per matrix), M = n_groups *
+    S; idx: row indices of any kind (None: all rows; a DEVICE index outside the matrices gives a NaN row, host indices raise
+    IndexError); divisor: a true division of every sum (1: none).  out: None, a list of n_groups [len(idx), d] matrices, or one
+    [len(idx), n_groups * d] slab.  Returns the list of the n_groups results.  Where `weights` requires a gradient it gets one
+    (sgl_ensemble_combine_bwd_f32: a fixed two-level reduction, the same bits in every run); the matrices never do.  More matrices
+    than one call takes are split by group."""
+    flat, n_groups, gs = _ensemble_members(groups)
+    n_rows, d = flat[0].shape
+    device = flat[0].device
+    cs = _ensemble_weight_mode(weights, n_groups * gs, d)
+    if idx is not None:
+        idx = _device_index(idx, n_rows, device)
+    m = n_rows if idx is None else int(idx.numel())
+    outs, pad = _ensemble_outs(out, n_groups, m, d, device)
+    if weights.requires_grad and torch.is_grad_enabled():
+        return list(_EnsembleCombine.apply(weights, (n_groups, gs, cs, idx, divisor, outs, pad), *flat))
+    return _ensemble_forward(flat, n_groups, gs, weights, cs, idx, divisor, outs, pad)

@@ -1,4 +1,6 @@
-from .base_model import BaseSGAPModel
-from .simple_models import IdenticalMapping, LogisticRegression, MultiLayerPerceptron, ResMultiLayerPerceptron
+from .base_model import BaseHeteroSGAPModel, BaseSGAPModel, FastBaseHeteroSGAPModel
+from .simple_models import (FastOneDimConvolution, IdenticalMapping, LogisticRegression, MultiLayerPerceptron, OneDimConvolution,
+                            OneDimConvolutionWeightSharedAcrossFeatures, ResMultiLayerPerceptron)
 
-__all__ = ["BaseSGAPModel", "IdenticalMapping", "LogisticRegression", "MultiLayerPerceptron", "ResMultiLayerPerceptron"]
+__all__ = ["BaseSGAPModel", "BaseHeteroSGAPModel", "FastBaseHeteroSGAPModel", "IdenticalMapping", "LogisticRegression", "MultiLayerPerceptron",
+           "ResMultiLayerPerceptron", "OneDimConvolution", "OneDimConvolutionWeightSharedAcrossFeatures", "FastOneDimConvolution"]

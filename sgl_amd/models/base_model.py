@@ -208,3 +208,89 @@ class BaseSGAPModel(nn.Module):
                     processed_feature.untyped_storage().data_ptr() == feat.untyped_storage().data_ptr():
                 processed_feature = processed_feature.clone()     # no head (NAFS): never hand out a view of the stored matrix
         return self._base_model(processed_feature)
+
+
+# ---- heterogeneous models (sgl/models/base_model.py:69-222): NARS ----------------------------------------------------------------------
+class _HeteroSGAPBase(nn.Module):
+    """What BaseHeteroSGAPModel and FastBaseHeteroSGAPModel share: S relation sub-graphs are propagated K times on the device and the
+    rows of the predict class are kept as row VIEWS of the hop matrices (start_pos rows down, the hop buffer's pitch).  A training
+    step reads x[idx] from all S * (K + 1) of them in ONE launch of device.ensemble_combine (K16) through the aggregator's `combine`
+    -- the reference gathers every matrix on the host, copies it over and stacks."""
+
+    def __init__(self, prop_steps, feat_dim, output_dim):
+        super().__init__()
+        self._prop_steps = prop_steps
+        self._feat_dim = feat_dim
+        self._output_dim = output_dim
+
+        self._pre_graph_op, self._pre_msg_op = None, None
+        self._aggregator = None
+        self._base_model = None
+
+        self._propagated_feat_list_list = None
+        self._processed_feature_list = None
+        self._pre_msg_learnable = False
+
+    # Either subgraph_list or (random_subgraph_num, subgraph_edge_type_num) should be provided.
+    def preprocess(self, dataset, predict_class, random_subgraph_num=-1, subgraph_edge_type_num=-1, subgraph_list=None):
+        from ..hetero import HeteroNodeDataset, edge_type_ends
+        if subgraph_list is None and (random_subgraph_num == -1 or subgraph_edge_type_num == -1):
+            raise ValueError("Either subgraph_list or (random_subgraph_num, subgraph_edge_type_num) should be provided!")
+        if subgraph_list is not None and (random_subgraph_num != -1 or subgraph_edge_type_num != -1):
+            raise ValueError("subgraph_list is provided, random_subgraph_num and subgraph_edge_type_num will be ignored!")
+        if not isinstance(dataset, HeteroNodeDataset):
+            raise TypeError("Dataset must be an instance of HeteroNodeDataset!")
+        if predict_class not in dataset.node_types:
+            raise ValueError("Please input valid node class for prediction!")
+        if hasattr(self._pre_graph_op, "_bf16_hops") and self._pre_graph_op._bf16_hops():
+            raise TypeError("the heterogeneous models have no bfloat16 form: hop_dtype='bfloat16' is not supported (ensemble_combine "
+                            "reads float32 hop matrices)")
+        first_id = dataset.data.node_id_dict[predict_class][0]
+        n_predict = dataset.data.num_node[predict_class]
+        if subgraph_list is None:
+            subgraph_dict = dataset.nars_preprocess(dataset.edge_types, predict_class, random_subgraph_num, subgraph_edge_type_num)
+            subgraph_list = [(key, subgraph_dict[key]) for key in subgraph_dict]
+
+        hops = [[] for _ in range(self._prop_steps + 1)]
+        for key, value in subgraph_list:
+            if predict_class not in {t for edge_type in key for t in edge_type_ends(edge_type)}:
+                continue                                         # a sub-graph that does not touch the predict class says nothing about it
+            adj, feature, node_id = value
+            propagated = self._pre_graph_op.propagate(adj, feature)
+            at = (torch.as_tensor(node_id).reshape(-1) == first_id).nonzero()
+            if at.numel() == 0:
+                raise ValueError(f"the sub-graph {key!r} does not hold the nodes of {predict_class!r}")
+            start_pos = int(at[0])
+            for i, x in enumerate(propagated):
+                hops[i].append(x[start_pos:start_pos + n_predict])
+        expected = getattr(self._aggregator, "num_subgraphs", None)
+        if expected is not None and len(hops[0]) != expected:
+            raise ValueError(f"{len(hops[0])} of the given sub-graphs touch {predict_class!r}, but the model was built for "
+                             f"random_subgraph_num={expected}")
+        self._propagated_feat_list_list = hops
+
+    # a wrapper of the forward function
+    def model_forward(self, idx, device):
+        return self.forward(idx, device)
+
+    def _rows(self, idx):
+        """the index as ensemble_combine takes it: a whole-range `range` means all rows, in place"""
+        n = self._propagated_feat_list_list[0][0].shape[0]
+        if isinstance(idx, range) and idx.step == 1 and idx.start == 0 and idx.stop == n:
+            return None
+        return idx
+
+
+class BaseHeteroSGAPModel(_HeteroSGAPBase):
+    def forward(self, idx, device):
+        aggregated_feat_list = [x.to(device) for x in self._aggregator.combine(self._propagated_feat_list_list, self._rows(idx))]
+        combined_feat = self._pre_msg_op.aggregate(aggregated_feat_list)
+        return self._base_model(combined_feat)
+
+
+class FastBaseHeteroSGAPModel(_HeteroSGAPBase):
+    # (the reference stacks the S * (K + 1) matrices into one [n, d, S * (K + 1)] tensor after propagating; here they stay where the
+    # propagation wrote them and the aggregator walks them in that tensor's order)
+    def forward(self, idx, device):
+        aggregated = self._aggregator.combine(self._propagated_feat_list_list, self._rows(idx)).to(device)
+        return self._base_model(aggregated)

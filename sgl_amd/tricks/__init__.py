@@ -4,10 +4,11 @@ NAFS clustering / link-prediction tasks (reference: sgl/tasks/node_clustering.py
 end the link-prediction task (sgl/tasks/link_prediction.py:282-283, without the N x N matrix); the k-means and the three
 scores that end the clustering task (sgl/tasks/node_clustering.py:254-257); the loss, the step and the loop of the trainable clustering
 task (sgl/tasks/utils.py:101-136, node_clustering.py:12-119); the loss, the accuracy, the steps and the loop of node classification
-(sgl/tasks/utils.py:12-98, node_classification.py:11-112; sgl/tricks/utils.py:7-10); and the label use / label reuse
+(sgl/tasks/utils.py:12-98, node_classification.py:11-112; sgl/tricks/utils.py:7-10) and of its heterogeneous form
+(node_classification.py:115-217); and the label use / label reuse
 loop around `model.preprocess` (reference: sgl/tasks/node_classification_with_label_use.py:58-137)."""
-from .classification import (NodeClassificationResult, accuracy, cross_entropy, epoch_batches, evaluate, loge_cross_entropy,
-                             mini_batch_evaluate, mini_batch_train, node_classification, predict, train)
+from .classification import (HeteroNodeClassification, HeteroNodeClassificationResult, NodeClassificationResult, accuracy, cross_entropy, epoch_batches, evaluate, loge_cross_entropy,
+                             hetero_node_classification, mini_batch_evaluate, mini_batch_train, node_classification, predict, train)
 from .clustering import (KMeansResult, NodeClusteringResult, NodeClusteringTrainResult, cluster_loss, clustering_scores, clustering_train,
                          kmeans, nafs_node_clustering, node_clustering)
 from .correct_and_smooth import CorrectAndSmooth
@@ -25,4 +26,5 @@ __all__ = ["CorrectAndSmooth", "label_propagation", "nafs_ensemble_features", "n
            "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult",
            "cluster_loss", "clustering_train", "node_clustering", "NodeClusteringTrainResult",
            "cross_entropy", "loge_cross_entropy", "predict", "accuracy", "train", "mini_batch_train", "evaluate", "mini_batch_evaluate",
-           "node_classification", "NodeClassificationResult", "epoch_batches"]
+           "node_classification", "NodeClassificationResult", "epoch_batches",
+           "hetero_node_classification", "HeteroNodeClassification", "HeteroNodeClassificationResult"]

@@ -23,7 +23,8 @@ import torch.nn.functional as F
 from .. import device as dev
 
 __all__ = ["cross_entropy", "loge_cross_entropy", "predict", "accuracy", "train", "mini_batch_train", "evaluate", "mini_batch_evaluate",
-           "node_classification", "NodeClassificationResult", "epoch_batches"]
+           "node_classification", "NodeClassificationResult", "epoch_batches",
+           "hetero_node_classification", "HeteroNodeClassification", "HeteroNodeClassificationResult"]
 
 FUSED_DEFAULT = True
 LOGE_EPSILON = 1.0 - math.log(2)
@@ -342,3 +343,68 @@ def node_classification(model, adj, x, y, train_idx, val_idx, test_idx, epochs, 
     if acc_val > best_val:
         best_val, best_test = acc_val, acc_test
     return NodeClassificationResult(best_val, best_test, history)
+
+
+HeteroNodeClassificationResult = namedtuple("HeteroNodeClassificationResult", ["best_val", "best_test", "subgraph_weight", "history"])
+HeteroNodeClassificationResult.__doc__ = """hetero_node_classification's result: the best validation accuracy, the test accuracy that came
+with it (HeteroNodeClassification's test_acc), the model's subgraph_weight at that epoch (None unless record_subgraph_weight), and
+history = one dict per epoch (epoch, loss, acc_train, acc_val, acc_test)"""
+
+
+def hetero_node_classification(model, dataset, predict_class, epochs, lr, weight_decay, loss_fn="cross_entropy", seed=42,
+                               train_batch_size=None, eval_batch_size=None, random_subgraph_num=-1, subgraph_edge_type_num=-1,
+                               subgraph_list=None, record_subgraph_weight=False, device="cuda"):
+    """HeteroNodeClassification._execute of the reference (sgl/tasks/node_classification.py:115-217) on the device: torch.manual_seed,
+    model.preprocess(dataset, predict_class, ...), Adam, `epochs` times train + evaluate (the mini-batch forms when train_batch_size
+    is given; batches as in node_classification), a strictly greater validation accuracy takes its test accuracy -- and, with
+    record_subgraph_weight, a copy of model.subgraph_weight -- with it.  The labels are dataset.data[predict_class].y; the index sets
+    dataset.train_idx / val_idx / test_idx count inside the predict class.  There is no post-processing step."""
+    _check_loss_fn(loss_fn)
+    if subgraph_list is None and (random_subgraph_num == -1 or subgraph_edge_type_num == -1):
+        raise ValueError("Either subgraph_list or (random_subgraph_num, subgraph_edge_type_num) should be provided!")
+    if subgraph_list is not None and (random_subgraph_num != -1 or subgraph_edge_type_num != -1):
+        raise ValueError("subgraph_list is provided, random_subgraph_num and subgraph_edge_type_num will be ignored!")
+    mini = train_batch_size is not None
+    if mini and eval_batch_size is None:
+        raise ValueError("hetero_node_classification: mini-batch training needs eval_batch_size")
+    device = torch.device(device)
+    y = dataset.data[predict_class].y
+    y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(-1).to(device=device, dtype=torch.int64)
+    train_idx, val_idx, test_idx = dataset.train_idx, dataset.val_idx, dataset.test_idx
+    torch.manual_seed(seed)
+    model.preprocess(dataset, predict_class, random_subgraph_num, subgraph_edge_type_num, subgraph_list)
+    model = model.to(device)
+    optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
+    if mini:
+        val_loader, test_loader = (epoch_batches(idx, eval_batch_size, None, device) for idx in (val_idx, test_idx))
+    best_val, best_test, history = 0., 0., []
+    best_weight = model.subgraph_weight.detach().clone() if record_subgraph_weight else None
+    for epoch in range(epochs):
+        if not mini:
+            loss, acc = train(model, train_idx, y, device, optimizer, loss_fn)
+            acc_val, acc_test = evaluate(model, val_idx, test_idx, y, device)
+        else:
+            loader = epoch_batches(train_idx, train_batch_size, seed + epoch, device)
+            loss, acc = mini_batch_train(model, train_idx, loader, y, device, optimizer, loss_fn)
+            acc_val, acc_test = mini_batch_evaluate(model, val_idx, val_loader, test_idx, test_loader, y, device)
+        history.append(dict(epoch=epoch, loss=loss, acc_train=acc, acc_val=acc_val, acc_test=acc_test))
+        if acc_val > best_val:
+            best_val, best_test = acc_val, acc_test
+            if record_subgraph_weight:
+                best_weight = model.subgraph_weight.detach().clone()
+    return HeteroNodeClassificationResult(best_val, best_test, best_weight, history)
+
+
+class HeteroNodeClassification:
+    """the reference's task object: runs on construction, then test_acc and subgraph_weight"""
+
+    def __init__(self, dataset, predict_class, model, lr, weight_decay, epochs, device, loss_fn="cross_entropy", seed=42,
+                 train_batch_size=None, eval_batch_size=None, random_subgraph_num=-1, subgraph_edge_type_num=-1, subgraph_list=None,
+                 record_subgraph_weight=False):
+        self.result = hetero_node_classification(model, dataset, predict_class, epochs, lr, weight_decay, loss_fn=loss_fn, seed=seed,
+                                                 train_batch_size=train_batch_size, eval_batch_size=eval_batch_size,
+                                                 random_subgraph_num=random_subgraph_num, subgraph_edge_type_num=subgraph_edge_type_num,
+                                                 subgraph_list=subgraph_list, record_subgraph_weight=record_subgraph_weight, device=device)
+
+    test_acc = property(lambda self: self.result.best_test)
+    subgraph_weight = property(lambda self: self.result.subgraph_weight)
