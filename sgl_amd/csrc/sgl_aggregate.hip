@@ -657,6 +657,10 @@ __global__ __launch_bounds__(256, RECUR_MIN_BLOCKS(LPR, HMAX, CH)) void recursiv
                                                          // in the lanes that take the arm, and a butterfly with idle lanes is wrong
                 wl = (l <= i) ? __fmul_rn(ex, __builtin_amdgcn_rcpf(sum)) : 0.f;   // (lanes beyond the first DPP row sum zeros)
             }
+        // ... which is 1 unless that score is NaN (x_0 holds +-inf where w_x and w_acc disagree in sign: inf - inf): the reference's
+        // soft-max of the one NaN is NaN and its row stays NaN.  Decided here, after the steps, from the a_0, c_0 lane 0 still holds.
+        const float z0 = from_lane<LPR>(__fadd_rn(__fadd_rn(al, cl), bias), 0);
+        wl = (z0 != z0) ? z0 : wl;
         if (live && l < n_hops) {
             if (wout) wout[r * ldw + l] = wl;
             if (aout) aout[r * lda + l] = al;
@@ -699,9 +703,11 @@ __global__ __launch_bounds__(256, RECUR_MIN_BLOCKS(LPR, HMAX, CH)) void recursiv
 #pragma unroll
                 for (int j = 0; j <= i; ++j) w[j] = __fmul_rn(w[j], inv);
             }
+        const float z0 = __fadd_rn(__fadd_rn(a[0], cc[0]), bias);     // a NaN score of step 0: the row is NaN (see above)
 #pragma unroll
         for (int h = 0; h < HMAX; ++h)
             if (h < n_hops) {
+                w[h] = (z0 != z0) ? z0 : w[h];
                 if (live && l == 0) {
                     if (wout) wout[r * ldw + h] = w[h];
                     if (aout) aout[r * lda + h] = a[h];
@@ -740,6 +746,12 @@ __global__ __launch_bounds__(256) void recursive_scalar_bwd_kernel(const int n_h
         gw[h] = in ? g[r * ldg + h] : 0.f;
         dcv[h] = 0.f;
         sv[h] = 0.f;
+    }
+    // the forward's step 0 gives NaN weights where its one score a_0 + c_0 + b is NaN (inf - inf): every gradient of such a row is
+    // NaN, which a NaN in gw_0 brings about (it enters every step's dot below); a_0 is needed for nothing else
+    {
+        const float z0 = __fadd_rn(__fadd_rn(av[0], cv[0]), bias);
+        gw[0] = (z0 != z0) ? z0 : gw[0];
     }
     hist[0][0] = 1.f;
 #pragma unroll
@@ -781,7 +793,10 @@ __global__ __launch_bounds__(256) void recursive_scalar_bwd_kernel(const int n_h
                 gw[j] = gz + p * cv[j];
             }
         }
-    if (da) da[r * ldda] = 0.f;                           // step 0 is the soft-max of ONE score: a_0 never reaches the weights
+    // step 0 is the soft-max of ONE score: a_0 never reaches the weights, da_0 = w (gw_0 - gw_0 w) with w = 1.  That is 0 unless gw_0
+    // is NaN by now, for ANY reason (the NaN score of step 0 folded in above, or a NaN that came down from a later step through
+    // p c_0): then it is NaN, as autograd's one-element soft-max backward 1 (NaN - NaN) is.  Intended.
+    if (da) da[r * ldda] = (gw[0] != gw[0]) ? gw[0] : 0.f;
 #pragma unroll
     for (int h = 0; h < HMAX; ++h)
         if (dc && h < n_hops) dc[r * lddc + h] = dcv[h];

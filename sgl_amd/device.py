@@ -1182,9 +1182,11 @@ def hop_colsum(feats, w, shared=False):
         ptrs, lds = _lib.hop_arrays(feats)
         _call(out.device, "sgl_hop_colsum_f32", H, ptrs, lds, ptr(w), 1 if shared else H, 0 if shared else 1, ptr(out), d, ptr(scratch), n, d)
         return out
+    # products, then the column sums: a transposed matrix-vector product of the BLAS library returns NaN for a column that holds
+    # one +-inf, where the sum (and sgl_hop_colsum_f32) is +-inf
     if shared:
-        return torch.stack([f.t() @ w.view(-1) for f in feats])
-    return torch.stack([f.t() @ w[:, h] for h, f in enumerate(feats)])
+        return torch.stack([(f * w.view(-1, 1)).sum(0) for f in feats])
+    return torch.stack([(f * w[:, h:h + 1]).sum(0) for h, f in enumerate(feats)])
 
 
 class _HopScores(torch.autograd.Function):
