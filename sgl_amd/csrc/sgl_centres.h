@@ -1,7 +1,8 @@
 // Device helpers shared by the kernels that hold rows of X in registers against centres staged in LDS: sgl_kmeans.hip (K9, the
 // assignment step) and sgl_cluster_loss.hip (K12, the clustering loss and its gradient).  A lane's sum of squared differences in the
-// DIRECT form, and the staging of a tile of NEGATED centres; the lane sums (group_sum) and the row loads that never read beyond column d
-// of a last row (edge_load) are sgl_rows.h's.  Not part of the ABI.
+// DIRECT form (Sq), and the staging of a tile of NEGATED centres (stage_centres, restage_centres);
+// the lane sums (group_sum), the row loads that never read beyond column d of a last row (edge_load) and the column
+// helpers (vzero, store_cols, load_cols) are sgl_rows.h's.  Not part of the ABI.
 #pragma once
 #include "sgl_rows.h"
 
@@ -67,6 +68,18 @@ __device__ __forceinline__ void stage_centres(float *__restrict__ tile, const fl
         const bool last = j0 + jj == k - 1;
         for (int col = lane * VEC; col < dp; col += 64 * VEC)
             *reinterpret_cast<V *>(tile + jj * dp + col) = -edge_load<VEC>(crow, col, d, last);
+    }
+}
+// the same between the barriers that the tile's readers need; a tile that holds every centre (tile_k >= k) is staged once per
+// workgroup (`staged`), not once per batch
+template <int VEC>
+__device__ __forceinline__ void restage_centres(bool &staged, float *__restrict__ tile, const float *__restrict__ cen, const int64_t ldc,
+                                                const int k, const int j0, const int kt, const int tile_k, const int d, const int dp) {
+    if (!(staged && tile_k >= k)) {
+        __syncthreads();                             // the tile's last readers are done
+        stage_centres<VEC>(tile, cen, ldc, k, j0, kt, d, dp);
+        __syncthreads();
+        staged = true;
     }
 }
 

@@ -8,7 +8,7 @@
 //   pred_i = the lowest index of the row's maximum; a NaN counts as the maximum and the first NaN wins (torch's CPU max)
 // pred does not depend on the label; when it is the only output no exp is evaluated and the labels are not read.
 //
-// Layout: LPR lanes (sgl::class_loss_instance, sgl_core.cpp) own a row and keep their slice of it in registers, CH vectors of VEC floats,
+// Layout: LPR lanes (sgl::slice_instance, sgl_core.cpp) own a row and keep their slice of it in registers, CH vectors of VEC floats,
 // lane l of the group holds columns (c * LPR + l) * VEC ..; 64 / LPR consecutive rows per wavefront, so a wavefront reads one
 // contiguous piece of the matrix, and U such pieces per step (rows_per_group), all loaded before the first is reduced.  The maximum
 // is taken first (group_max), the exponentials replace the logits in the registers, their sum is group_sum; lane 0 of the group finishes the row's loss (one logf, z_{i, y_i} re-read from the line the group just loaded).
@@ -65,22 +65,6 @@ __device__ __forceinline__ void set_elem(typename Vt<VEC>::type &v, const int e,
     else v = x;
 }
 
-// columns col .. col + VEC - 1 of an output row, never beyond column c (VEC = 4: the row is made of 16-byte vectors)
-template <int VEC>
-__device__ __forceinline__ void put_cols(float *__restrict__ orow, const int col, const int c, const typename Vt<VEC>::type v) {
-    if constexpr (VEC == 4) {
-        if (col + 4 <= c) {
-            *reinterpret_cast<f4 *>(orow + col) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (col + e < c) orow[col + e] = v[e];
-        }
-    } else {
-        orow[col] = v;
-    }
-}
-
 // A lane's candidates for the row's arg-max, its columns taken in ascending order: the largest entry that is not NaN with the first
 // column that holds it, and the first column that holds a NaN
 struct Best {
@@ -126,19 +110,18 @@ __global__ __launch_bounds__(256) void class_loss_kernel(const float *__restrict
         V v[U][CH];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t row = (b * U + u) * GPB + g;
+            const int64_t row = (b * U + u) * GPB + g;   // (batch_row of sgl_rows.h, written out: the helper moved class_loss_kernel<64, 4, 4, 1>)
             const float *p = z + (row < n ? row : 0) * ldz;
 #pragma unroll
             for (int k = 0; k < CH; ++k) {
                 const int col = (k * LPR + l) * VEC;
-                if constexpr (VEC == 4) v[u][k] = f4{0.f, 0.f, 0.f, 0.f};
-                else v[u][k] = 0.f;
+                v[u][k] = vzero<VEC>();
                 if (row < n && col < c) v[u][k] = edge_load<VEC>(p, col, c, row == n - 1);
             }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t row = (b * U + u) * GPB + g;
+            const int64_t row = (b * U + u) * GPB + g;   // (batch_row of sgl_rows.h, written out: the helper moved class_loss_kernel<64, 4, 4, 1>)
             const bool in = row < n;
             Best best;
 #pragma unroll
@@ -180,7 +163,7 @@ __global__ __launch_bounds__(256) void class_loss_kernel(const float *__restrict
                             V o;
 #pragma unroll
                             for (int e = 0; e < VEC; ++e) set_elem<VEC>(o, e, grad_of(elem<VEC>(v[u][k], e), s, col + e == y, live, w));
-                            put_cols<VEC>(orow, col, c, o);
+                            store_cols<VEC>(orow, col, c, o);
                         }
                     }
                 }
@@ -240,7 +223,7 @@ __global__ __launch_bounds__(256) void class_loss_stream_kernel(const float *__r
                 V o;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) set_elem<VEC>(o, e, grad_of(expf(elem<VEC>(v, e) - m), s, col + e == y, live, w));
-                put_cols<VEC>(orow, col, c, o);
+                store_cols<VEC>(orow, col, c, o);
             }
         }
     }
@@ -255,11 +238,9 @@ template <int LPR, int VEC, int CH>
 void launch_rows(hipStream_t st, const float *d_z, int64_t ldz, int64_t n, int c, const int64_t *d_labels, float w, float *d_dz, int64_t lddz,
                  float *d_row_loss, int64_t *d_pred) {
     constexpr int U = rows_per_group(VEC, CH);
-    const int64_t per_batch = (int64_t)(256 / LPR) * U;
-    const int64_t n_batches = (n + per_batch - 1) / per_batch;
-    const int64_t blocks = sgl::loss_grid(n_batches, kMaxBlocks);
-    hipLaunchKernelGGL((class_loss_kernel<LPR, VEC, CH, U>), dim3((unsigned)blocks), dim3(256), 0, st, d_z, ldz, n, c, d_labels, w, d_dz, lddz,
-                       d_row_loss, d_pred, n_batches);
+    const sgl::BatchGrid grid = sgl::loss_batch_grid(n, 256 / LPR, U, kMaxBlocks);
+    hipLaunchKernelGGL((class_loss_kernel<LPR, VEC, CH, U>), dim3((unsigned)grid.blocks), dim3(256), 0, st, d_z, ldz, n, c, d_labels, w, d_dz,
+                       lddz, d_row_loss, d_pred, grid.n_batches);
 }
 
 }  // namespace
@@ -278,18 +259,11 @@ SGL_EXPORT int sgl_class_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n,
     if (n == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
     const bool vec4 = ldz % 4 == 0 && aligned_to(d_z, 16) && (!d_dz || (lddz % 4 == 0 && aligned_to(d_dz, 16)));
-    const sgl::ClassLossInstance in = sgl::class_loss_instance(c, vec4 ? 4 : 1);
+    const int vec = vec4 ? 4 : 1;
+    const sgl::SliceInstance in = sgl::slice_instance(c, vec, sgl::ClassLossSlices::chunks(vec));
     const int ci = (int)c;
-    bool launched = false;
-#define SGL_CLASS_LOSS_ARGS st, d_z, ldz, n, ci, d_labels, w, d_dz, lddz, d_row_loss, d_pred
-    if (in.ch == 1) {
-        launched = with_lpr_vec(in.lpr, vec4, [&](auto L, auto V) { launch_rows<L, V, 1>(SGL_CLASS_LOSS_ARGS); });
-    } else if (vec4 && in.ch > 1) {                  // 64 lanes from here on
-        launched = with_one_of<2, 4>(in.ch, [&](auto C) { launch_rows<64, 4, C>(SGL_CLASS_LOSS_ARGS); });
-    } else if (in.ch > 1) {
-        launched = with_one_of<2, 4, 8, 16>(in.ch, [&](auto C) { launch_rows<64, 1, C>(SGL_CLASS_LOSS_ARGS); });
-    }
-#undef SGL_CLASS_LOSS_ARGS
+    const bool launched = with_slice_instance<sgl::ClassLossSlices>(
+        in, vec4, [&](auto L, auto V, auto C) { launch_rows<L, V, C>(st, d_z, ldz, n, ci, d_labels, w, d_dz, lddz, d_row_loss, d_pred); });
     if (!launched) {
         if (in.ch != 0) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: no kernel instance is compiled for %d lanes x %d chunks", who, in.lpr, in.ch);
         const int64_t blocks = sgl::loss_grid((n + 3) / 4, kMaxBlocks);

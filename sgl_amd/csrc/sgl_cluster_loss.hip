@@ -7,7 +7,7 @@
 // The centres and the labels carry no gradient.
 //
 // DIRECT form only: the difference x - c is taken first, for the distance and for the gradient (translation-invariant; the expansion
-// x sum a - sum a c is not).  Layout: K9's (sgl_kmeans.hip) -- LPR lanes (sgl::pick_lpr) own a row and keep their slice of it in
+// x sum a - sum a c is not).  Layout: K9's (sgl_kmeans.hip) -- LPR lanes (sgl::slice_instance) own a row and keep their slice of it in
 // registers across all k centres, CH vectors of VEC floats, U rows per lane group; next to it the slice of dX, summed in registers.
 // The centres are staged NEGATED in LDS tiles of at most 64 KiB; the running sums of the loss and of dX cross the tiles: any k x d.
 //
@@ -34,12 +34,6 @@ namespace {
 
 constexpr int kStep = 4;                             // T: centres per step (<= 8, the smallest lane group: one centre per lane)
 
-template <int VEC>
-__device__ __forceinline__ typename Vt<VEC>::type vzero() {
-    if constexpr (VEC == 4) return f4{0.f, 0.f, 0.f, 0.f};
-    else return 0.f;
-}
-
 // acc + a (x + nc), the difference first
 template <int VEC>
 __device__ __forceinline__ typename Vt<VEC>::type scaled_diff(const float a, const typename Vt<VEC>::type x, const typename Vt<VEC>::type nc,
@@ -51,34 +45,6 @@ __device__ __forceinline__ typename Vt<VEC>::type scaled_diff(const float a, con
         return acc;
     } else {
         return fmaf(a, x + nc, acc);
-    }
-}
-
-// columns col .. col + VEC - 1 of an output row, never beyond column d (VEC = 4: the row is made of 16-byte vectors)
-template <int VEC>
-__device__ __forceinline__ void store_cols(float *__restrict__ orow, const int col, const int d, const typename Vt<VEC>::type v) {
-    if constexpr (VEC == 4) {
-        if (col + 4 <= d) {
-            *reinterpret_cast<f4 *>(orow + col) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (col + e < d) orow[col + e] = v[e];
-        }
-    } else {
-        orow[col] = v;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ typename Vt<VEC>::type load_cols(const float *orow, const int col, const int d) {
-    if constexpr (VEC == 4) {
-        if (col + 4 <= d) return *reinterpret_cast<const f4 *>(orow + col);
-        f4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? orow[col + e] : 0.f;
-        return v;
-    } else {
-        return orow[col];
     }
 }
 
@@ -107,7 +73,6 @@ __global__ __launch_bounds__(256) void cluster_loss_kernel(const float *__restri
                                                            float *__restrict__ dx, const int64_t lddx, float *__restrict__ row_loss) {
     using V = typename Vt<VEC>::type;
     extern __shared__ __attribute__((aligned(16))) float tile[];
-    constexpr int GPB = 256 / LPR;                   // row groups per workgroup
     constexpr int T = kStep;
     constexpr int PER = U * T < LPR ? U * T : LPR;  // (row, centre) pairs of a step that are finished at once, one per lane
     constexpr int ROUNDS = U * T / PER;
@@ -119,7 +84,7 @@ __global__ __launch_bounds__(256) void cluster_loss_kernel(const float *__restri
         int y[U];                                    // the label, -1 when it names no centre
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t row = b * (GPB * U) + u * GPB + g;
+            const int64_t row = batch_row<LPR, U>(b, u, g);
             const float *p = x + (row < n ? row : 0) * ldx;
             const int64_t label = row < n ? labels[row] : -1;
             y[u] = (label >= 0 && label < k) ? (int)label : -1;
@@ -135,12 +100,7 @@ __global__ __launch_bounds__(256) void cluster_loss_kernel(const float *__restri
         RowSums sums[ROUNDS];                        // of the (row, slot) pairs this lane takes: pair r * PER + l in round r
         for (int j0 = 0; j0 < k; j0 += tile_k) {     // (tile_k is a multiple of T unless it is k: centre j is in slot j % T, whatever the tile)
             const int kt = (k - j0 < tile_k) ? k - j0 : tile_k;
-            if (!(staged && tile_k >= k)) {          // a tile that holds every centre is staged once per workgroup
-                __syncthreads();                     // the tile's last readers are done
-                stage_centres<VEC>(tile, cen, ldc, k, j0, kt, d, dp);
-                __syncthreads();
-                staged = true;
-            }
+            restage_centres<VEC>(staged, tile, cen, ldc, k, j0, kt, tile_k, d, dp);
             for (int jj = 0; jj < kt; jj += T) {     // T centres at a time; slots beyond the tile repeat its last centre and are not taken
                 Sq<VEC> sq[U][T];
 #pragma unroll
@@ -216,7 +176,7 @@ __global__ __launch_bounds__(256) void cluster_loss_kernel(const float *__restri
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t row = b * (GPB * U) + u * GPB + g;
+            const int64_t row = batch_row<LPR, U>(b, u, g);
             if (row < n) {
                 if (dx) {
                     float *orow = dx + row * lddx;
@@ -284,11 +244,9 @@ void launch_loss(hipStream_t st, const float *d_x, int64_t ldx, int64_t n, int d
     constexpr int U = rows_per_group(VEC, CH);
     const int dp = (d + VEC - 1) / VEC * VEC;
     const int tile_k = k <= kTileFloats / dp ? k : kTileFloats / dp / kStep * kStep;   // whole steps per tile: a centre's slot is j % T
-    const int64_t per_batch = (int64_t)(256 / LPR) * U;
-    const int64_t n_batches = (n + per_batch - 1) / per_batch;
-    const int64_t blocks = sgl::loss_grid(n_batches, kMaxBlocks);
-    hipLaunchKernelGGL((cluster_loss_kernel<LPR, VEC, CH, U>), dim3((unsigned)blocks), dim3(256), (size_t)tile_k * dp * sizeof(float), st, d_x,
-                       ldx, n, d, d_c, ldc, k, tile_k, dp, n_batches, d_labels, inv_k, w, d_dx, lddx, d_row_loss);
+    const sgl::BatchGrid grid = sgl::loss_batch_grid(n, 256 / LPR, U, kMaxBlocks);
+    hipLaunchKernelGGL((cluster_loss_kernel<LPR, VEC, CH, U>), dim3((unsigned)grid.blocks), dim3(256), (size_t)tile_k * dp * sizeof(float), st,
+                       d_x, ldx, n, d, d_c, ldc, k, tile_k, dp, grid.n_batches, d_labels, inv_k, w, d_dx, lddx, d_row_loss);
 }
 
 }  // namespace
@@ -314,24 +272,14 @@ SGL_EXPORT int sgl_cluster_loss_grad_f32(const float *d_x, int64_t ldx, int64_t 
     const bool vec4 = ldx % 4 == 0 && ldc % 4 == 0 && aligned_to(d_x, 16) && aligned_to(d_centres, 16) &&
                       (!d_dx || (lddx % 4 == 0 && aligned_to(d_dx, 16)));
     const int vec = vec4 ? 4 : 1;
-    const int lpr = sgl::pick_lpr(d, vec);
-    const int64_t chunks = (d + (int64_t)lpr * vec - 1) / ((int64_t)lpr * vec);
+    const sgl::SliceInstance in = sgl::slice_instance(d, vec, sgl::ClusterLossSlices::chunks(vec));
     if (!sgl::launch_fits(kMaxBlocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
     const int di = (int)d, ki = (int)k;
     const float inv_k = 1.f / (float)ki;
-    bool launched = false;
-#define SGL_CLUSTER_LOSS_ARGS st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, inv_k, w, d_dx, lddx, d_row_loss
-    if (chunks == 1) {
-        launched = with_lpr_vec(lpr, vec4, [&](auto L, auto V) { launch_loss<L, V, 1>(SGL_CLUSTER_LOSS_ARGS); });
-    } else if (vec4 && chunks <= 8) {                // lpr = 64 from here on; the capacity is the next compiled one
-        const int ch = chunks <= 2 ? 2 : (chunks <= 4 ? 4 : 8);
-        launched = with_one_of<2, 4, 8>(ch, [&](auto C) { launch_loss<64, 4, C>(SGL_CLUSTER_LOSS_ARGS); });
-    } else if (!vec4 && chunks <= 32) {
-        const int ch = chunks <= 2 ? 2 : (chunks <= 8 ? 8 : 32);
-        launched = with_one_of<2, 8, 32>(ch, [&](auto C) { launch_loss<64, 1, C>(SGL_CLUSTER_LOSS_ARGS); });
-    }
-#undef SGL_CLUSTER_LOSS_ARGS
-    if (!launched) {
+    const bool launched = with_slice_instance<sgl::ClusterLossSlices>(in, vec4, [&](auto L, auto V, auto C) {
+        launch_loss<L, V, C>(st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, inv_k, w, d_dx, lddx, d_row_loss);
+    });
+    if (!launched) {                                 // ch = 0: rows beyond the register layouts
         const int64_t blocks = sgl::loss_grid((n + 3) / 4, kMaxBlocks);
         with_vec(vec4, [&](auto V) {
             hipLaunchKernelGGL((cluster_loss_stream_kernel<V>), dim3((unsigned)blocks), dim3(256), 0, st, d_x, ldx, n, di, d_centres, ldc, ki,

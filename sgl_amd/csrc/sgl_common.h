@@ -85,6 +85,16 @@ inline int64_t loss_grid(int64_t wanted, int64_t cap) {
     if (forced > 0 && forced < cap) cap = forced;
     return wanted < cap ? wanted : cap;
 }
+// the same for a register kernel of K9, K12, K14 that strides over batches of n rows: `groups` lane groups per workgroup (256 / LPR)
+// x `u` rows per group make one batch
+struct BatchGrid {
+    int64_t n_batches, blocks;
+};
+inline BatchGrid loss_batch_grid(int64_t n, int groups, int u, int64_t cap) {
+    const int64_t per_batch = (int64_t)groups * u;
+    const int64_t n_batches = (n + per_batch - 1) / per_batch;
+    return {n_batches, loss_grid(n_batches, cap)};
+}
 
 // what sgl_csr_create takes for item_nnz <= 0 / long_row_nnz == 0: functions of the matrix's nnz only (sgl_core.cpp)
 int32_t default_item_nnz(int64_t nnz);
@@ -113,10 +123,33 @@ struct RowInstance {
     int lpr, ch, hmax;   // hmax: the even hop capacity of the compiled instance; 0 = the layout has none for this hop count
 };
 int pick_lpr(int64_t d, int vec);                                    // the smallest of 8 / 16 / 32 / 64 lanes that covers ceil(d / vec)
-struct ClassLossInstance {
-    int lpr, ch;         // lanes per row x vectors per lane; ch = 0: the streaming kernel (64 lanes)
+
+// ---- slice rule (host, sgl_core.cpp): the instance of a loss / k-means kernel (K9, K11, K12, K14) whose lanes keep a slice of a row ----
+// The 64-lane instances of a family are compiled for these numbers of vectors per lane, one list per lane size; the rule
+// (slice_instance) and the typed dispatch (with_slice_instance, sgl_rows.h) both read them here and nowhere else.
+struct ChunkList {
+    const int *values;
+    int count;
 };
-ClassLossInstance class_loss_instance(int64_t c, int vec);           // sgl_class_loss_grad_f32's kernel for rows of c logits
+template <int... Cs>
+struct Chunks {
+    static constexpr int values[] = {Cs...};
+    static constexpr ChunkList list() { return {values, (int)sizeof...(Cs)}; }
+};
+template <typename V4, typename V1>
+struct SliceFamily {
+    using Vec4 = V4;     // lanes of 16 bytes
+    using Vec1 = V1;     // lanes of one float
+    static constexpr ChunkList chunks(int vec) { return vec == 4 ? V4::list() : V1::list(); }
+};
+using KmeansSlices = SliceFamily<Chunks<2, 3, 4, 6, 8>, Chunks<2, 4, 8, 16, 32>>;   // K9: rows of up to 2048 floats
+using EdgeLossSlices = SliceFamily<Chunks<2, 4, 8>, Chunks<2, 8, 32>>;              // K11
+using ClusterLossSlices = SliceFamily<Chunks<2, 4, 8>, Chunks<2, 8, 32>>;           // K12
+using ClassLossSlices = SliceFamily<Chunks<2, 4>, Chunks<2, 4, 8, 16>>;             // K14: up to 1024 logits in at most 16 registers
+struct SliceInstance {
+    int lpr, ch;         // lanes per row x vectors per lane; ch = 0: beyond the register layouts (64 lanes)
+};
+SliceInstance slice_instance(int64_t width, int vec, ChunkList compiled);
 RowLayout row_layout(int64_t d, int n_hops, bool allow_8x5 = false);  // reads the tuning keys row_lpr32x2, row_narrow_groups
 RowInstance row_instance(int64_t d, int n_hops, bool allow_8x5 = false);
 int out_cols(int64_t d, int64_t pad, int64_t room);                  // columns a row kernel writes; reads row_whole_lines

@@ -133,18 +133,16 @@ int pick_lpr(int64_t d, int vec) {
     return lpr;
 }
 
-// The instance of class_loss_kernel (sgl_class_loss.hip) that serves rows of c logits read `vec` floats at a time: the narrowest lane
-// group that covers the row with one vector per lane; beyond 64 lanes the next compiled number of vectors per lane -- 2 / 4 of 16
-// bytes, 2 / 4 / 8 / 16 of one float, so both lane sizes keep rows of up to 1024 logits in at most 16 registers; beyond: ch = 0,
-// the streaming kernel.
-ClassLossInstance class_loss_instance(int64_t c, int vec) {
-    ClassLossInstance r;
-    r.lpr = pick_lpr(c, vec);
-    const int64_t chunks = (c + (int64_t)r.lpr * vec - 1) / ((int64_t)r.lpr * vec);
-    const int most = vec == 4 ? 4 : 16;
-    r.ch = 0;
-    for (int ch = 1; ch <= most && r.ch == 0; ch <<= 1)
-        if (chunks <= ch) r.ch = ch;
+// The instance of a loss / k-means kernel (K9, K11, K12, K14) that serves rows of `width` floats read `vec` floats at a time: the
+// narrowest lane group that covers the row with one vector per lane; beyond 64 lanes the next number of vectors per lane the family
+// compiles (`compiled`, ascending: a list of sgl_common.h); beyond the last: ch = 0 -- the streaming kernel, K11's in-place form.
+SliceInstance slice_instance(int64_t width, int vec, ChunkList compiled) {
+    SliceInstance r;
+    r.lpr = pick_lpr(width, vec);
+    const int64_t chunks = (width + (int64_t)r.lpr * vec - 1) / ((int64_t)r.lpr * vec);
+    r.ch = chunks <= 1 ? 1 : 0;
+    for (int i = 0; i < compiled.count && r.ch == 0; ++i)
+        if (chunks <= compiled.values[i]) r.ch = compiled.values[i];
     return r;
 }
 

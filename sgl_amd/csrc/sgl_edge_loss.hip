@@ -5,7 +5,7 @@
 // tricks/link_prediction.py: EdgePlan), and while row i is in registers every incident edge (i, j) gathers z_j once, forms the score,
 // turns it into the loss coefficient c and accumulates c z_j into dZ[i].  2 E row gathers for loss and gradient together.
 //
-// Layout.  LPR lanes (sgl::pick_lpr) own one PIECE: at most max_piece consecutive incidences of one row.  A lane keeps its slice of z_i
+// Layout.  LPR lanes (sgl::slice_instance) own one PIECE: at most max_piece consecutive incidences of one row.  A lane keeps its slice of z_i
 // and of the piece's dZ sum in registers, CH vectors of VEC floats each (vector (c LPR + l) of the row for lane l, chunk c: K9's
 // layout); CH = 0 is the instance for rows beyond the register layouts, which re-reads z_i per chunk and keeps the sum in the output
 // row it owns.  The piece's entries are walked U at a time: per chunk the U row loads are issued before any arithmetic (K8's unroll).
@@ -53,12 +53,6 @@ __device__ __forceinline__ void loss_coef(const float s, const float y, const fl
 }
 
 template <int VEC>
-__device__ __forceinline__ typename Vt<VEC>::type vzero() {
-    if constexpr (VEC == 4) return f4{0.f, 0.f, 0.f, 0.f};
-    else return 0.f;
-}
-
-template <int VEC>
 __device__ __forceinline__ float dot_step(const typename Vt<VEC>::type x, const typename Vt<VEC>::type y, float acc) {
     if constexpr (VEC == 4) {
 #pragma unroll
@@ -77,34 +71,6 @@ __device__ __forceinline__ typename Vt<VEC>::type axpy_step(const float c, const
         return acc;
     } else {
         return fmaf(c, y, acc);
-    }
-}
-
-// columns col .. col + VEC - 1 of an output row, never beyond column d; `ovec`: the row is made of 16-byte vectors
-template <int VEC>
-__device__ __forceinline__ void store_cols(float *__restrict__ orow, const int col, const int d, const typename Vt<VEC>::type v, const bool ovec) {
-    if constexpr (VEC == 4) {
-        if (ovec && col + 4 <= d) {
-            *reinterpret_cast<f4 *>(orow + col) = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (col + e < d) orow[col + e] = v[e];
-        }
-    } else {
-        orow[col] = v;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ typename Vt<VEC>::type load_cols(const float *orow, const int col, const int d, const bool ovec) {
-    if constexpr (VEC == 4) {
-        if (ovec && col + 4 <= d) return *reinterpret_cast<const f4 *>(orow + col);
-        f4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? orow[col + e] : 0.f;
-        return v;
-    } else {
-        return orow[col];
     }
 }
 
@@ -294,19 +260,6 @@ __global__ __launch_bounds__(256) void edge_fold_kernel(const int64_t *__restric
 
 constexpr int kMaxFoldBlocks = 2048;
 
-template <int MODE>
-bool launch_mode(int lpr, bool vec4, int ch, dim3 grid, hipStream_t st, const float *z, int64_t ldz, int64_t n, int d, const int64_t *pieces,
-                 int64_t n_pieces, const int32_t *inc_other, const int64_t *inc_edge, const float *labels, const float *given, float w,
-                 float *dz, int64_t lddz, float *partial, int64_t ldp, int ovec, float *score, float *coef, float *piece_loss) {
-    auto go = [&](auto L, auto V, auto C) {
-        hipLaunchKernelGGL((edge_loss_grad_kernel<L, V, MODE, C>), grid, dim3(256), 0, st, z, ldz, n, d, pieces, n_pieces, inc_other, inc_edge,
-                           labels, given, w, dz, lddz, partial, ldp, ovec, score, coef, piece_loss);
-    };
-    if (ch == 1) return with_lpr_vec(lpr, vec4, [&](auto L, auto V) { go(L, V, Int<1>{}); });
-    if (vec4) return with_one_of<0, 2, 4, 8>(ch, [&](auto C) { go(Int<64>{}, Int<4>{}, C); });
-    return with_one_of<0, 2, 8, 32>(ch, [&](auto C) { go(Int<64>{}, Int<1>{}, C); });
-}
-
 }  // namespace
 
 SGL_EXPORT int sgl_edge_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, int64_t d, const int64_t *d_pieces, int64_t n_pieces,
@@ -343,24 +296,26 @@ SGL_EXPORT int sgl_edge_loss_grad_f32(const float *d_z, int64_t ldz, int64_t n, 
     }
     const bool vec4 = ldz % 4 == 0 && aligned_to(d_z, 16);
     const int vec = vec4 ? 4 : 1;
-    const int lpr = sgl::pick_lpr(d, vec);
-    const int64_t chunks = (d + (int64_t)lpr * vec - 1) / ((int64_t)lpr * vec);
     // chunks per lane of the compiled instance: 1 (any lane count), then 64 lanes with 2 / 4 / 8 vectors or 2 / 8 / 32 floats; 0 beyond
-    const int ch = chunks == 1 ? 1 : vec4 ? (chunks <= 2 ? 2 : chunks <= 4 ? 4 : chunks <= 8 ? 8 : 0) : (chunks <= 2 ? 2 : chunks <= 8 ? 8 : chunks <= 32 ? 32 : 0);
+    const sgl::SliceInstance in = sgl::slice_instance(d, vec, sgl::EdgeLossSlices::chunks(vec));
     const int ovec = (lddz % 4 == 0 && aligned_to(d_dz, 16) && (n_partial == 0 || (ldp % 4 == 0 && aligned_to(d_partial, 16)))) ? 1 : 0;
     if (n_pieces > 0) {
-        const int64_t per_block = 256 / lpr;
+        const int64_t per_block = 256 / in.lpr;
         const int64_t blocks = (n_pieces + per_block - 1) / per_block;
         if (!sgl::launch_fits(blocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: too many pieces for one launch (split the table)", who);
         const dim3 grid((unsigned)blocks);
         const int di = (int)d;
-        bool launched = false;
-#define SGL_EDGE_LOSS_ARGS lpr, vec4, ch, grid, st, d_z, ldz, n, di, d_pieces, n_pieces, d_inc_other, d_inc_edge, d_labels, d_given, w, d_dz, lddz, d_partial, ldp, ovec, d_score, d_coef, d_piece_loss
-        if (mode == MODE_SIGMOID_LOGITS) launched = launch_mode<MODE_SIGMOID_LOGITS>(SGL_EDGE_LOSS_ARGS);
-        else if (mode == MODE_LOGITS) launched = launch_mode<MODE_LOGITS>(SGL_EDGE_LOSS_ARGS);
-        else launched = launch_mode<MODE_GIVEN>(SGL_EDGE_LOSS_ARGS);
-#undef SGL_EDGE_LOSS_ARGS
-        if (!launched) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: no kernel instance for %d lanes x %d chunks", who, lpr, ch);
+        // (ch = 0, the in-place form, is a compiled instance of this family)
+        auto launch = [&](auto M) {
+            return with_slice_instance<sgl::EdgeLossSlices, 0>(in, vec4, [&](auto L, auto V, auto C) {
+                hipLaunchKernelGGL((edge_loss_grad_kernel<L, V, M, C>), grid, dim3(256), 0, st, d_z, ldz, n, di, d_pieces, n_pieces, d_inc_other,
+                                   d_inc_edge, d_labels, d_given, w, d_dz, lddz, d_partial, ldp, ovec, d_score, d_coef, d_piece_loss);
+            });
+        };
+        const bool launched = mode == MODE_SIGMOID_LOGITS ? launch(Int<MODE_SIGMOID_LOGITS>{})
+                              : mode == MODE_LOGITS       ? launch(Int<MODE_LOGITS>{})
+                                                          : launch(Int<MODE_GIVEN>{});
+        if (!launched) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: no kernel instance for %d lanes x %d chunks", who, in.lpr, in.ch);
         SGL_LAUNCH_CHECK(who);
     }
     if (n_fold > 0) {

@@ -5,7 +5,7 @@
 // makes only because it expands the square), every term >= 0, relative error (d + 3) 2^-24 whatever the offset of the data.  That
 // rules out MFMA (it would need the expanded form) and makes one step compute-balanced: 2 N k d flops against N d x 4 bytes.
 //
-// Layout.  LPR lanes (sgl::pick_lpr) own a row and keep their slice of it in REGISTERS across all k centres: CH vectors of VEC floats
+// Layout.  LPR lanes (sgl::slice_instance) own a row and keep their slice of it in REGISTERS across all k centres: CH vectors of VEC floats
 // (vector (c * LPR + l) of the row for lane l, chunk c), U rows per lane group so that one LDS read of a centre vector serves U rows
 // (at U = 1 the LDS pipe, shared by the four SIMDs, is the limit: one 16-byte read per four VALU instructions).  The centres are
 // staged in LDS in tiles of at most 64 KiB (two workgroups per CU), the pad of a tile zeroed; a running (best, label) per row crosses
@@ -22,7 +22,7 @@
 // distance never wins; a row whose k distances are ALL NaN (a NaN in the row) gets label 0 and mindist NaN.  Nothing traps.
 // VEC = 4 needs 16-byte aligned bases and pitches that are multiples of 4 floats on both matrices; pads are zeroed before use and
 // nothing beyond column d of a LAST row is read (edge_load).
-#include "sgl_centres.h"   // Sq, stage_centres, kTileFloats: shared with sgl_cluster_loss.hip (K12)
+#include "sgl_centres.h"   // Sq, restage_centres, kTileFloats: shared with sgl_cluster_loss.hip (K12)
 
 namespace {
 
@@ -98,7 +98,6 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float *__restr
                                                             int64_t *__restrict__ labels, float *__restrict__ mindist) {
     using V = typename Vt<VEC>::type;
     extern __shared__ __attribute__((aligned(16))) float tile[];
-    constexpr int GPB = 256 / LPR;                   // row groups per workgroup
     constexpr int T = kSlots<LPR>;                   // centres per step of the transposing reduction
     const int l = threadIdx.x % LPR;
     const int g = threadIdx.x / LPR;
@@ -107,12 +106,12 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float *__restr
         V xr[U][CH];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const int64_t row = b * (GPB * U) + u * GPB + g;
+            const int64_t row = batch_row<LPR, U>(b, u, g);
             const float *p = x + (row < n ? row : 0) * ldx;
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 const int col = (c * LPR + l) * VEC;
-                V v = {};
+                V v = vzero<VEC>();
                 if (row < n && col < d) v = edge_load<VEC>(p, col, d, row == n - 1);
                 xr[u][c] = v;
             }
@@ -120,12 +119,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float *__restr
         Best best[U];
         for (int j0 = 0; j0 < k; j0 += tile_k) {
             const int kt = (k - j0 < tile_k) ? k - j0 : tile_k;
-            if (!(staged && tile_k >= k)) {          // a tile that holds every centre is staged once per workgroup
-                __syncthreads();                     // the tile's last readers are done
-                stage_centres<VEC>(tile, cen, ldc, k, j0, kt, d, dp);
-                __syncthreads();
-                staged = true;
-            }
+            restage_centres<VEC>(staged, tile, cen, ldc, k, j0, kt, tile_k, d, dp);
             for (int jj = 0; jj < kt; jj += T) {     // T centres at a time; slots beyond the tile repeat its last centre and are not taken
                 Sq<VEC> acc[U][T];
 #pragma unroll
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(256) void kmeans_assign_kernel(const float *__restr
         if (l == 0) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const int64_t row = b * (GPB * U) + u * GPB + g;
+                const int64_t row = batch_row<LPR, U>(b, u, g);
                 if (row < n) {
                     labels[row] = best[u].label;
                     if (mindist) mindist[row] = best[u].min_dist();
@@ -208,11 +202,9 @@ void launch_assign(hipStream_t st, const float *d_x, int64_t ldx, int64_t n, int
     constexpr int U = rows_per_group(VEC, CH);
     const int dp = (d + VEC - 1) / VEC * VEC;
     const int tile_k = k < kTileFloats / dp ? k : kTileFloats / dp;
-    const int64_t per_batch = (int64_t)(256 / LPR) * U;
-    const int64_t n_batches = (n + per_batch - 1) / per_batch;
-    const int64_t blocks = sgl::loss_grid(n_batches, kMaxBlocks);
-    hipLaunchKernelGGL((kmeans_assign_kernel<LPR, VEC, CH, U>), dim3((unsigned)blocks), dim3(256), (size_t)tile_k * dp * sizeof(float), st,
-                       d_x, ldx, n, d, d_c, ldc, k, tile_k, dp, n_batches, d_labels, d_mindist);
+    const sgl::BatchGrid grid = sgl::loss_batch_grid(n, 256 / LPR, U, kMaxBlocks);
+    hipLaunchKernelGGL((kmeans_assign_kernel<LPR, VEC, CH, U>), dim3((unsigned)grid.blocks), dim3(256), (size_t)tile_k * dp * sizeof(float), st,
+                       d_x, ldx, n, d, d_c, ldc, k, tile_k, dp, grid.n_batches, d_labels, d_mindist);
 }
 
 }  // namespace
@@ -236,21 +228,12 @@ SGL_EXPORT int sgl_kmeans_assign_f32(const float *d_x, int64_t ldx, int64_t n, i
     }
     const bool vec4 = ldx % 4 == 0 && ldc % 4 == 0 && aligned_to(d_x, 16) && aligned_to(d_centres, 16);
     const int vec = vec4 ? 4 : 1;
-    const int lpr = sgl::pick_lpr(d, vec);
-    const int64_t chunks = (d + (int64_t)lpr * vec - 1) / ((int64_t)lpr * vec);
+    const sgl::SliceInstance in = sgl::slice_instance(d, vec, sgl::KmeansSlices::chunks(vec));
     if (!sgl::launch_fits(kMaxBlocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_kmeans_assign_f32: the grid does not fit one launch");
     const int di = (int)d, ki = (int)k;
-    bool launched = false;
-    if (chunks == 1) {
-        launched = with_lpr_vec(lpr, vec4, [&](auto L, auto V) { launch_assign<L, V, 1>(st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, d_mindist); });
-    } else if (vec4 && chunks <= 8) {                // lpr = 64 from here on; the capacity is the next compiled one
-        const int ch = chunks <= 4 ? (int)chunks : (chunks <= 6 ? 6 : 8);
-        launched = with_one_of<2, 3, 4, 6, 8>(ch, [&](auto C) { launch_assign<64, 4, C>(st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, d_mindist); });
-    } else if (!vec4 && chunks <= 32) {
-        const int ch = chunks <= 2 ? 2 : (chunks <= 4 ? 4 : (chunks <= 8 ? 8 : (chunks <= 16 ? 16 : 32)));
-        launched = with_one_of<2, 4, 8, 16, 32>(ch, [&](auto C) { launch_assign<64, 1, C>(st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, d_mindist); });
-    }
-    if (!launched) {
+    const bool launched = with_slice_instance<sgl::KmeansSlices>(
+        in, vec4, [&](auto L, auto V, auto C) { launch_assign<L, V, C>(st, d_x, ldx, n, di, d_centres, ldc, ki, d_labels, d_mindist); });
+    if (!launched) {                                 // ch = 0: rows beyond the register layouts
         const int64_t blocks = sgl::loss_grid((n + 3) / 4, kMaxBlocks);
         with_vec(vec4, [&](auto V) {
             hipLaunchKernelGGL((kmeans_assign_stream_kernel<V>), dim3((unsigned)blocks), dim3(256), 0, st, d_x, ldx, n, di, d_centres, ldc, ki,

@@ -1,7 +1,8 @@
 // Device helpers and typed launch dispatch of the row kernels, shared by sgl_aggregate.hip (float32 hops), sgl_aggregate_bf16.hip
-// (bfloat16 hops) and sgl_edge.hip: both aggregator files must pick the same lane layout and sum in the same lane order for their
-// results to be bit-identical, so the in-wavefront reductions exist once, here, and the layout rule once in sgl_core.cpp
-// (sgl::row_layout / sgl::row_instance: pure host arithmetic, checked on the CPU).  Not part of the ABI.
+// (bfloat16 hops), sgl_edge.hip and the loss / k-means kernels (K9, K11, K12, K14): both aggregator files must pick the same lane
+// layout and sum in the same lane order for their results to be bit-identical, so the in-wavefront reductions exist once, here, and
+// the layout rules once in sgl_core.cpp (sgl::row_layout / sgl::row_instance / sgl::slice_instance: pure host arithmetic, checked on
+// the CPU).  Not part of the ABI.
 #pragma once
 #include <type_traits>
 
@@ -64,6 +65,50 @@ __device__ __forceinline__ typename Vt<VEC>::type edge_load(const float *__restr
     } else {
         return p[c];
     }
+}
+
+// ---- the per-VEC column helpers of the loss / k-means kernels (K9, K11, K12, K14) ---------------------------------------------------
+template <int VEC>
+__device__ __forceinline__ typename Vt<VEC>::type vzero() {
+    if constexpr (VEC == 4) return f4{0.f, 0.f, 0.f, 0.f};
+    else return 0.f;
+}
+
+// columns col .. col + VEC - 1 of an output row, never beyond column d; `ovec`: the row is made of 16-byte vectors
+template <int VEC>
+__device__ __forceinline__ void store_cols(float *__restrict__ orow, const int col, const int d, const typename Vt<VEC>::type v,
+                                           const bool ovec = true) {
+    if constexpr (VEC == 4) {
+        if (ovec && col + 4 <= d) {
+            *reinterpret_cast<f4 *>(orow + col) = v;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (col + e < d) orow[col + e] = v[e];
+        }
+    } else {
+        orow[col] = v;
+    }
+}
+template <int VEC>
+__device__ __forceinline__ typename Vt<VEC>::type load_cols(const float *orow, const int col, const int d, const bool ovec = true) {
+    if constexpr (VEC == 4) {
+        if (ovec && col + 4 <= d) return *reinterpret_cast<const f4 *>(orow + col);
+        f4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? orow[col + e] : 0.f;
+        return v;
+    } else {
+        return orow[col];
+    }
+}
+
+// The register kernels of K9, K12 and K14 walk batches of 256 / LPR lane groups x U rows: row u of batch b for lane group g.  The
+// loads and the stores of a batch in K9 and K12 form it with this one expression (K14 writes it out: DESIGN.md K14).
+template <int LPR, int U>
+__device__ __forceinline__ int64_t batch_row(const int64_t b, const int u, const int g) {
+    constexpr int GPB = 256 / LPR;
+    return (b * U + u) * GPB + g;
 }
 
 // ---- row-wise reductions: LPR lanes cooperate on one row, 64/LPR rows per wavefront ------------------------
@@ -295,6 +340,19 @@ bool with_vec(bool vec4, F &&f) {   // floats per lane access
 template <typename F>
 bool with_hop_capacity(int n, F &&f) {   // kernels that keep per-hop values of up to 4 / 8 / 12 / 16 hops in registers
     return with_one_of<4, 8, 12, 16>(n <= 4 ? 4 : (n + 3) / 4 * 4, f);
+}
+
+// f(LPR, VEC, CH) for an instance of sgl::slice_instance: one vector per lane with any lane count, then 64 lanes with a count of the
+// family's list for the lane size (sgl_common.h: the list the rule read); MORE: counts the family compiles besides (K11's 0)
+template <int... MORE, int... Cs, typename F>
+bool with_chunks(sgl::Chunks<Cs...>, int ch, F &&f) {
+    return with_one_of<MORE..., Cs...>(ch, f);
+}
+template <typename Family, int... MORE, typename F>
+bool with_slice_instance(const sgl::SliceInstance &in, bool vec4, F &&f) {
+    if (in.ch == 1) return with_lpr_vec(in.lpr, vec4, [&](auto L, auto V) { f(L, V, Int<1>{}); });
+    if (vec4) return with_chunks<MORE...>(typename Family::Vec4{}, in.ch, [&](auto C) { f(Int<64>{}, Int<4>{}, C); });
+    return with_chunks<MORE...>(typename Family::Vec1{}, in.ch, [&](auto C) { f(Int<64>{}, Int<1>{}, C); });
 }
 
 // f(LPR, CH) for a layout of sgl::row_layout.  HAS_8X5: the kernel family has 8 x 5 instances (hop_rowdot2_reg_kernel alone).

@@ -1,9 +1,9 @@
-// The host arithmetic behind the strided launches as the library computes it, without a GPU: sgl::pick_lpr, sgl::class_loss_instance
-// (sgl_amd/csrc/sgl_core.cpp) and sgl::loss_grid (sgl_common.h) under the tuning key loss_blocks, built by tests/test_strided_cpu.py
+// The host arithmetic behind the strided launches as the library computes it, without a GPU: sgl::pick_lpr, sgl::slice_instance
+// (sgl_amd/csrc/sgl_core.cpp) over each family's lists and sgl::loss_grid (sgl_common.h) under the tuning key loss_blocks, built by tests/test_strided_cpu.py
 // with g++ and compared there against the restatements of tests/strided_common.py.
 // One query per line on stdin, one answer per line on stdout:
 //   lpr d vec                     ->   lanes per row
-//   cls c vec                     ->   lpr ch                 (ch = 0: the streaming kernel)
+//   km / el / cl / cls w vec      ->   lpr ch                 (the rule of K9 / K11 / K12 / K14; ch = 0: beyond the register layouts)
 //   grid wanted cap loss_blocks   ->   blocks                 (sets the key first and reads it back)
 #include <cstdio>
 #include <cstring>
@@ -17,8 +17,13 @@ int main() {
         const int got = sscanf(line, "%15s %lld %lld %lld", what, &a, &b, &c);
         if (got >= 3 && !strcmp(what, "lpr")) {
             printf("%d\n", sgl::pick_lpr(a, (int)b));
-        } else if (got >= 3 && !strcmp(what, "cls")) {
-            const sgl::ClassLossInstance in = sgl::class_loss_instance(a, (int)b);
+        } else if (got >= 3 && (!strcmp(what, "km") || !strcmp(what, "el") || !strcmp(what, "cl") || !strcmp(what, "cls"))) {
+            const int vec = (int)b;
+            const sgl::ChunkList compiled = !strcmp(what, "km")   ? sgl::KmeansSlices::chunks(vec)
+                                            : !strcmp(what, "el") ? sgl::EdgeLossSlices::chunks(vec)
+                                            : !strcmp(what, "cl") ? sgl::ClusterLossSlices::chunks(vec)
+                                                                  : sgl::ClassLossSlices::chunks(vec);
+            const sgl::SliceInstance in = sgl::slice_instance(a, vec, compiled);
             printf("%d %d\n", in.lpr, in.ch);
         } else if (got == 4 && !strcmp(what, "grid")) {
             int64_t back = -1;

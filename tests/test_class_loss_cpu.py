@@ -145,12 +145,17 @@ def test_argmax_cases_and_unique_maxima():
 def test_instance_rule_against_the_compiled_instances():
     want = compiled_instances()
     assert len(want) == 16
+    # the chunk counts of the 64-lane instances stand once, in sgl_common.h: the rule (sgl::slice_instance, sgl_core.cpp) and the
+    # dispatch (with_slice_instance, sgl_rows.h) of the entry point both read that list
     src = open(os.path.join(ROOT, "sgl_amd", "csrc", "sgl_class_loss.hip")).read()
-    lists = re.findall(r"with_one_of<([\d, ]+)>\(in\.ch, \[&\]\(auto C\) \{ launch_rows<64, (\d), C>", src)
-    assert {int(vec): tuple(int(v) for v in chs.split(",")) for chs, vec in lists} == CHUNKS
-    assert "launch_rows<L, V, 1>" in src and "class_loss_stream_kernel<V>" in src
+    common = open(os.path.join(ROOT, "sgl_amd", "csrc", "sgl_common.h")).read()
+    lists = re.findall(r"using ClassLossSlices = SliceFamily<Chunks<([\d, ]+)>, Chunks<([\d, ]+)>>;", common)
+    assert len(lists) == 1 and {vec: tuple(int(v) for v in chs.split(",")) for vec, chs in zip((4, 1), lists[0])} == CHUNKS
+    assert "sgl::slice_instance(c, vec, sgl::ClassLossSlices::chunks(vec))" in src and "with_one_of<" not in src
+    assert "with_slice_instance<sgl::ClassLossSlices>(" in src and "launch_rows<L, V, C>" in src and "class_loss_stream_kernel<V>" in src
     core = open(os.path.join(ROOT, "sgl_amd", "csrc", "sgl_core.cpp")).read()
-    assert "class_loss_instance" in core and "vec == 4 ? 4 : 16" in core              # the largest CH per lane size
+    assert "SliceInstance slice_instance(int64_t width, int vec, ChunkList compiled)" in core
+    assert (max(CHUNKS[4]), max(CHUNKS[1])) == (4, 16)                                # the largest CH per lane size
     assert {instance_for(c, 4) for c in WIDTHS} == {i for i in want if i[1] == 4}, "the widths do not reach every 16-byte instance"
     assert {instance_for(c, 1) for c in WIDTHS} == {i for i in want if i[1] == 1}, "the widths do not reach every 4-byte instance"
     assert instance_for(47, 4) == (16, 4, 1) and instance_for(172, 4) == (64, 4, 1) and instance_for(3, 1) == (8, 1, 1)

@@ -15,6 +15,7 @@ import class_loss_common as zlc
 import cluster_loss_common as clc
 import kmeans_common as kc
 import strided_common as sc
+import edge_loss_common as elc
 from edge_loss_common import hub_edges, plan_tables
 from edge_scores_common import EDGES
 from edge_scores_common import N_ROWS as EDGE_ROWS
@@ -26,6 +27,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def source(name):
     with open(os.path.join(ROOT, "sgl_amd", "csrc", name)) as f:
         return f.read()
+
+
+def chunk_lists():
+    """family -> {lane size: chunk counts of the compiled 64-lane instances}, as sgl_common.h states them: the lists that
+    sgl::slice_instance reads and with_slice_instance (sgl_rows.h) dispatches"""
+    text = source("sgl_common.h")
+    found = re.findall(r"using (\w+)Slices = SliceFamily<Chunks<([\d, ]+)>, Chunks<([\d, ]+)>>;", text)
+    assert len(found) == text.count("SliceFamily<Chunks<")                      # every family was read
+    return {name: {4: tuple(int(v) for v in v4.split(",")), 1: tuple(int(v) for v in v1.split(","))} for name, v4, v1 in found}
 
 
 def ok(g, what):
@@ -49,14 +59,38 @@ def test_caps_are_the_sources():
     agg = source("sgl_aggregate.hip")
     assert f"constexpr int kW1dBlocks = {sc.CAP_W1D};" in agg
     assert "n_edges < 256 * 1024 ? (n_edges + 255) / 256 : 1024" in source("sgl_edge.hip") and (sc.FILL_FROM, sc.FILL_BLOCKS) == (262144, 1024)
-    # every loss launch takes its grid from sgl::loss_grid with the kernel's own cap: two sites in K9, K12 and K14, one in K11
-    assert km.count("sgl::loss_grid(") == 2 and cl.count("sgl::loss_grid(") == 2 and zl.count("sgl::loss_grid(") == 2
-    assert el.count("sgl::loss_grid((n_fold + 3) / 4, kMaxFoldBlocks)") == 1
+    # every loss launch takes its grid from sgl::loss_grid with the kernel's own cap: two sites in K9, K12 and K14 -- the batches of
+    # the register kernels through sgl::loss_batch_grid, which hands them to loss_grid, and the streaming kernel -- and one in K11
+    common = source("sgl_common.h")
+    assert "return {n_batches, loss_grid(n_batches, cap)};" in common and "const int64_t per_batch = (int64_t)groups * u;" in common
+    assert "const int64_t n_batches = (n + per_batch - 1) / per_batch;" in common
+    for text in (km, cl, zl):
+        assert text.count("sgl::loss_batch_grid(n, 256 / LPR, U, kMaxBlocks)") == 1
+        assert text.count("sgl::loss_grid((n + 3) / 4, kMaxBlocks)") == 1
+        assert text.count("sgl::loss_grid(") + text.count("sgl::loss_batch_grid(") == 2
+    assert el.count("sgl::loss_grid((n_fold + 3) / 4, kMaxFoldBlocks)") == 1 and el.count("sgl::loss_grid(") == 1
     # rows per lane group, as the three files write them
     assert "return vec * ch * 4 <= 64 ? 4 : (vec * ch * 2 <= 64 ? 2 : 1);" in km
     assert "return vec * ch * 8 <= 64 ? 4 : (vec * ch * 4 <= 64 ? 2 : 1);" in cl
     assert [sc.k9_rows_per_group(v, c) for v, c in ((1, 1), (1, 16), (1, 32), (4, 1), (4, 4), (4, 6), (4, 8))] == [4, 4, 2, 4, 4, 2, 2]
-    assert "with_one_of<2, 3, 4, 6, 8>(ch" in km and "with_one_of<2, 4, 8, 16, 32>(ch" in km
+    # the chunk counts of the 64-lane instances: one list per family and lane size in sgl_common.h, read by the rule
+    # (sgl::slice_instance) and by the dispatch (with_slice_instance) of each entry point; K9's are these
+    lists = chunk_lists()
+    assert sorted(lists) == ["ClassLoss", "ClusterLoss", "EdgeLoss", "Kmeans"]
+    assert lists["Kmeans"] == {4: (2, 3, 4, 6, 8), 1: (2, 4, 8, 16, 32)}
+    for vec in (1, 4):                                                        # each list against the tests' own restatement
+        assert set(lists["Kmeans"][vec]) == {sc.k9_instance(d, vec)[2] for d in range(1, 2600)} - {0, 1}
+        assert set(lists["EdgeLoss"][vec]) == {i[3] for i in elc.compiled_instances() if i[1] == vec} - {0, 1}
+        assert set(lists["ClusterLoss"][vec]) == {i[2] for i in clc.compiled_instances() if i[1] == vec} - {0, 1}
+        assert lists["ClassLoss"][vec] == zlc.CHUNKS[vec]
+    assert all(list(v) == sorted(v) for fam in lists.values() for v in fam.values())   # ascending: the rule takes the first that fits
+    for text, family, more in ((km, "Kmeans", ""), (cl, "ClusterLoss", ""), (zl, "ClassLoss", ""), (el, "EdgeLoss", ", 0")):
+        assert text.count(f"sgl::slice_instance(") == 1 and f"sgl::{family}Slices::chunks(vec))" in text
+        assert text.count(f"with_slice_instance<sgl::{family}Slices{more}>(") == 1 and "with_one_of<" not in text.replace("with_one_of<MODE", "")
+        assert "#define" not in text
+    rows = source("sgl_rows.h")
+    assert "with_chunks<MORE...>(typename Family::Vec4{}, in.ch" in rows and "with_chunks<MORE...>(typename Family::Vec1{}, in.ch" in rows
+    assert "return with_one_of<MORE..., Cs...>(ch, f);" in rows
 
 
 def test_pick_lanes_and_stream_grid():
@@ -72,8 +106,24 @@ def test_pick_lanes_and_stream_grid():
     assert min(sc.CAP_K14 * sc.per_batch(sc.k14_instance(c, v)) * c * 4 for c in zlc.WIDTHS for v in (1, 4)) > 1 << 27
 
 
+class _Matrix:
+    """what the expected_instance rules of the *_common.py files read of a tensor: two rows of d floats whose pitch and base allow
+    16-byte lanes (vec = 4) or do not (vec = 1)"""
+
+    def __init__(self, d, vec):
+        self.shape = (2, d)
+        self.pitch = -(-d // 4) * 4 if vec == 4 else (d if d % 4 else d + 1)
+
+    def stride(self, dim):
+        return self.pitch if dim == 0 else 1
+
+    def data_ptr(self):
+        return 0
+
+
 def test_library_host_rules_equal_the_restatement(tmp_path):
-    """sgl::pick_lpr, sgl::class_loss_instance and sgl::loss_grid (host code), built with g++ into tests/native/strided_table.cpp"""
+    """sgl::pick_lpr, sgl::slice_instance over the lists of all four families and sgl::loss_grid (host code), built with g++ into
+    tests/native/strided_table.cpp"""
     gxx = shutil.which("g++")
     if gxx is None or not os.path.exists("/opt/rocm/include/hip/hip_runtime.h"):
         pytest.skip("needs g++ and the HIP headers")
@@ -84,7 +134,8 @@ def test_library_host_rules_equal_the_restatement(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     widths = list(range(1, 2600))
     grids = [(w, cap, key) for cap in (2048, 1 << 20) for key in (0, 1, 3, 2048, 5000) for w in (1, 2, 3, 4, 2047, 2048, 2049, 1 << 21)]
-    queries = [f"lpr {d} {v}" for v in (1, 4) for d in widths] + [f"cls {c} {v}" for v in (1, 4) for c in widths]
+    rules = ("cls", "km", "el", "cl")
+    queries = [f"lpr {d} {v}" for v in (1, 4) for d in widths] + [f"{rule} {c} {v}" for rule in rules for v in (1, 4) for c in widths]
     queries += [f"grid {w} {cap} {key}" for w, cap, key in grids] + ["grid 7 2048 0"]
     r = subprocess.run([exe], input="\n".join(queries) + "\n", capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -92,9 +143,18 @@ def test_library_host_rules_equal_the_restatement(tmp_path):
     assert len(got) == len(queries)
     m = 2 * len(widths)
     assert [g[0] for g in got[:m]] == [sc.pick_lpr(d, v) for v in (1, 4) for d in widths]
-    for (lpr, ch), (c, v) in zip(got[m:2 * m], [(c, v) for v in (1, 4) for c in widths]):
+    width_vec = [(c, v) for v in (1, 4) for c in widths]
+    for (lpr, ch), (c, v) in zip(got[m:2 * m], width_vec):
         assert (64 if ch == 0 else lpr, v, ch) == zlc.instance_for(c, v), (c, v, lpr, ch)
-    for (blocks,), (w, cap, key) in zip(got[2 * m:], grids):
+    for (lpr, ch), (d, v) in zip(got[2 * m:3 * m], width_vec):                  # K9
+        assert (64 if ch == 0 else lpr, v, ch) == sc.k9_instance(d, v)[:3], (d, v, lpr, ch)
+    for (lpr, ch), (d, v) in zip(got[3 * m:4 * m], width_vec):                  # K11: ch = 0 is an instance of the same kernel
+        assert lpr == sc.pick_lpr(d, v) and (lpr == 64 or ch == 1), (d, v, lpr, ch)
+        assert (lpr, v, 0, ch) == elc.expected_instance(_Matrix(d, v), "sigmoid"), (d, v, lpr, ch)
+    for (lpr, ch), (d, v) in zip(got[4 * m:5 * m], width_vec):                  # K12, both restatements
+        assert (64 if ch == 0 else lpr, v, ch) == sc.k12_instance(d, v)[:3], (d, v, lpr, ch)
+        assert sc.k12_instance(d, v) == clc.expected_instance(_Matrix(d, v), _Matrix(d, v)), (d, v)
+    for (blocks,), (w, cap, key) in zip(got[5 * m:], grids):
         assert blocks == sc.grid(w, 1, cap, key).blocks == min(w, cap, key if key > 0 else cap), (w, cap, key, blocks)
 
 

@@ -149,7 +149,7 @@ SOURCE_CONSTANTS = {
     "kTileFloats": ("sgl_amd/csrc/sgl_centres.h", r"constexpr int kTileFloats = (\d+);", 16384),
     "spmm_lanes_f32": ("sgl_amd/csrc/sgl_spmm.hip", r"const int64_t max_cols = 64 \* (\d+) \* vec;", 4),
     "spmm_lanes_bf16": ("sgl_amd/csrc/sgl_spmm_bf16.hip", r"const int64_t max_cols = 64 \* (\d+) \* bv;", 4),
-    "class_loss_vec4_chunks": ("sgl_amd/csrc/sgl_core.cpp", r"const int most = vec == 4 \? (\d+) : 16;", 4),
+    "class_loss_vec4_chunks": ("sgl_amd/csrc/sgl_common.h", r"using ClassLossSlices = SliceFamily<Chunks<[\d, ]*?(\d+)>, Chunks<2, 4, 8, 16>>;", 4),
     "class_loss_max_c_log2": ("sgl_amd/csrc/sgl_class_loss.hip", r"c <= \(\(int64_t\)1 << (\d+)\)", 30),
     "SGL_MAX_WIDTH": ("include/sgl_hip.h", r"#define SGL_MAX_WIDTH (\d+)", INT32_MAX - 4096),
     "SGL_MAX_HOPS": ("include/sgl_hip.h", r"#define SGL_MAX_HOPS (\d+)", 64),
