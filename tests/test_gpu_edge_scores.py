@@ -5,6 +5,8 @@ float64 (the truth) through oracle.truth_report -- at most twice as far from the
 condition-aware floor for cancelling sums; no tolerance is chosen in this file.  Bit-for-bit claims use torch.equal.  Every launch
 runs under torch.profiler: the kernel names seen must be the instances the restated selection rule (edge_scores_common) announces,
 and all of them together exactly the compiled ones."""
+import gc
+
 import numpy as np
 import pytest
 import torch
@@ -43,11 +45,24 @@ class Trace:
 
     def __enter__(self):
         from torch.profiler import ProfilerActivity, profile
+        # An earlier session's profiler objects sit in reference cycles: when the cycle collector frees them while this session runs
+        # (the backward path allocates enough to start it), the device records gathered so far go with them.  Collect them now and
+        # keep the collector off until the events are read.
+        self.gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
         self.prof = profile(activities=[ProfilerActivity.CUDA])
         self.prof.__enter__()
         return self
 
     def __exit__(self, et, ev, tb):
+        try:
+            return self.check(et, ev, tb)
+        finally:
+            if self.gc_was_on:
+                gc.enable()
+
+    def check(self, et, ev, tb):
         torch.cuda.synchronize()
         self.prof.__exit__(et, ev, tb)
         if et is not None:
