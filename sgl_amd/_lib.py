@@ -173,6 +173,17 @@ ENSEMBLE_PROTOTYPES = {
                                              c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
+# include/sgl_spgemm.h: K17, the product of two canonical device CSRs -- again a header and a table of their own
+SGL_SPGEMM_SUM, SGL_SPGEMM_ONES = 0, 1
+SGL_SPGEMM_NARROW_CAPS, SGL_SPGEMM_WINDOWS = (32, 128, 512), (1024, 32768, 524288)
+SPGEMM_PROTOTYPES = {
+    "sgl_csr_matmul_rule": (c_int, [c_int, c_int, c_int64, POINTER(c_int)]),
+    "sgl_csr_matmul_rowptr": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p,
+                                      POINTER(c_int64), c_void_p]),
+    "sgl_csr_matmul_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int,
+                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -202,7 +213,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m sgl_amd.csrc.build` (needs hipcc). "
                 "sgl_amd has no CPU fallback for the propagation hot path.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items()):
+        for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

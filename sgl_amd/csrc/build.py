@@ -14,11 +14,11 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libsgl_hip.so")
-SOURCES = ["sgl_core.cpp", "sgl_csr.hip", "sgl_spmm.hip", "sgl_spmm_bf16.hip", "sgl_aggregate.hip", "sgl_aggregate_bf16.hip", "sgl_normalize.hip", "sgl_ingest.hip", "sgl_shims.hip", "sgl_exchange.hip", "sgl_reorder.hip", "sgl_edge.hip", "sgl_edge_loss.hip", "sgl_kmeans.hip", "sgl_cluster_loss.hip", "sgl_class_loss.hip", "sgl_edge_split.hip", "sgl_csr_select.hip", "sgl_csr_merge.hip", "sgl_ensemble.hip"]
+SOURCES = ["sgl_core.cpp", "sgl_csr.hip", "sgl_spmm.hip", "sgl_spmm_bf16.hip", "sgl_aggregate.hip", "sgl_aggregate_bf16.hip", "sgl_normalize.hip", "sgl_ingest.hip", "sgl_shims.hip", "sgl_exchange.hip", "sgl_reorder.hip", "sgl_edge.hip", "sgl_edge_loss.hip", "sgl_kmeans.hip", "sgl_cluster_loss.hip", "sgl_class_loss.hip", "sgl_edge_split.hip", "sgl_csr_select.hip", "sgl_csr_merge.hip", "sgl_ensemble.hip", "sgl_spgemm.hip"]
 # measurement / test support, a library of its own (include/sgl_probe.h): memory probes, placed allocations, synthetic workloads
 PROBE_LIB = os.path.join(HERE, "libsgl_probe.so")
 PROBE_SOURCES = ["sgl_probe_core.cpp", "sgl_probe.hip", "sgl_synth.hip", "sgl_mem.hip"]
-HEADERS = ["sgl_common.h", "sgl_csr.h", "sgl_spmm_common.h", "sgl_rows.h", "sgl_centres.h", "sgl_hash.h", "sgl_csr_search.h", os.path.join(ROOT, "include", "sgl_hip.h"), os.path.join(ROOT, "include", "sgl_probe.h"), os.path.join(ROOT, "include", "sgl_ensemble.h")]
+HEADERS = ["sgl_common.h", "sgl_csr.h", "sgl_spmm_common.h", "sgl_rows.h", "sgl_centres.h", "sgl_hash.h", "sgl_csr_search.h", os.path.join(ROOT, "include", "sgl_hip.h"), os.path.join(ROOT, "include", "sgl_probe.h"), os.path.join(ROOT, "include", "sgl_ensemble.h"), os.path.join(ROOT, "include", "sgl_spgemm.h")]
 ARCH = "gfx950"
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
@@ -27,6 +27,9 @@ FLAGS = [
     "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",
     "-Wall", "-Wno-unused-function", "-Wno-unused-result",
 ]
+# per-source additions.  sgl_spgemm.hip: its value chain is one rounded multiply and one rounded add per product, stated lane by lane;
+# the packed two-float forms (v_pk_*_f32) are kept out of its code
+EXTRA_FLAGS = {"sgl_spgemm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hipcc():
@@ -53,7 +56,7 @@ def build(force=False, verbose=False):
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         if force or stale(obj, [src] + hdrs + [os.path.abspath(__file__)]):
-            cmd = [cc] + FLAGS + (["-x", "hip"] if src.endswith(".hip") else []) + ["-c", src, "-o", obj]
+            cmd = [cc] + FLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) + (["-x", "hip"] if src.endswith(".hip") else []) + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             r = subprocess.run(cmd, capture_output=True, text=True)

@@ -155,6 +155,13 @@ RowInstance row_instance(int64_t d, int n_hops, bool allow_8x5 = false);
 int out_cols(int64_t d, int64_t pad, int64_t room);                  // columns a row kernel writes; reads row_whole_lines
 int check_pad(const char *who, int64_t width, int64_t pad, int64_t ldo);
 
+// ---- K17 (sgl_spgemm.hip): which rows are sorted in LDS and how many columns one bitmap covers (host, sgl_core.cpp) ----
+struct SpgemmRule {
+    int narrow_cap, window_cols;
+};
+int spgemm_rule(const char *who, int narrow_cap, int window_cols, int64_t n, SpgemmRule &out);   // refuses by name what no instance serves
+int64_t spgemm_grid(int64_t wanted, int64_t cap);                    // at least 1; reads the tuning key spgemm_blocks
+
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
 // A HIP launch carries at most 2^32 - 1 threads per grid dimension; beyond that the launch is silently truncated on this

@@ -8,6 +8,7 @@
 #include <thread>
 
 #include "sgl_common.h"
+#include "../../include/sgl_spgemm.h"
 
 namespace sgl {
 
@@ -35,6 +36,7 @@ static std::map<std::string, int64_t> &tune_map() {
         {"spmm_heavy_first", 1}, // plan time: work items that end in a heavy row are issued first inside every XCD range
         {"agg_blocks", 0},       // 0 = one 16-byte element per thread (grid capped at 2^22 blocks); > 0 caps the grid of the streaming aggregators (grid-stride)
         {"loss_blocks", 0},      // 0 = each kernel's own cap; > 0 caps the grid of the k-means / cluster-loss / class-loss kernels and the edge-loss fold (grid-stride)
+        {"spgemm_blocks", 0},    // 0 = each K17 kernel's own cap; > 0 caps the grids of the sparse product's kernels (grid-stride)
         {"nafs_fused", 1},       // 0 = force the two-pass NAFS path
         {"row_lpr32x2", 1},      // row-wise kernels, 128 < d <= 256: 32 lanes x 2 chunks per row (2 rows per wavefront)
         {"row_whole_lines", 1},    // gate / NAFS / concat outputs: the pad columns of a row pitch (< one line beyond d) are written as zeros
@@ -56,6 +58,29 @@ int64_t tuning(const char *key, int64_t dflt) {
     auto it = m.find(key);
     if (it == m.end()) return dflt;
     return it->second;
+}
+
+// K17 (sgl_spgemm.hip): the narrow cap and the bitmap window of a call.  0 = auto: the largest cap (every row that fits a slice is
+// sorted in LDS); the smallest window that covers all n columns, else the largest.  Any other value must be a compiled one.
+int spgemm_rule(const char *who, int narrow_cap, int window_cols, int64_t n, SpgemmRule &out) {
+    static const int caps[] = SGL_SPGEMM_NARROW_CAPS, windows[] = SGL_SPGEMM_WINDOWS;
+    constexpr int n_caps = sizeof(caps) / sizeof(caps[0]), n_windows = sizeof(windows) / sizeof(windows[0]);
+    out.narrow_cap = narrow_cap == 0 ? caps[n_caps - 1] : 0;
+    for (int c : caps)
+        if (c == narrow_cap) out.narrow_cap = c;
+    if (!out.narrow_cap) return fail(SGL_ERR_INVALID, "%s: narrow_cap must be 0 (auto), %d, %d or %d, not %d", who, caps[0], caps[1], caps[2], narrow_cap);
+    out.window_cols = 0;
+    for (int w : windows)
+        if (w == window_cols || (window_cols == 0 && !out.window_cols && (w >= n || w == windows[n_windows - 1]))) out.window_cols = w;
+    if (!out.window_cols)
+        return fail(SGL_ERR_INVALID, "%s: window_cols must be 0 (auto), %d, %d or %d, not %d", who, windows[0], windows[1], windows[2], window_cols);
+    return SGL_OK;
+}
+
+int64_t spgemm_grid(int64_t wanted, int64_t cap) {
+    const int64_t forced = tuning("spgemm_blocks", 0);
+    if (forced > 0 && forced < cap) cap = forced;
+    return wanted < 1 ? 1 : wanted < cap ? wanted : cap;
 }
 
 // One wavefront per item: small matrices get smaller items so that the chip (256 CUs x 4 SIMDs x 8 waves) still
@@ -385,6 +410,17 @@ SGL_EXPORT int sgl_get_tuning(const char *key, int64_t *value) {
     auto it = m.find(key);
     if (it == m.end()) return sgl::fail(SGL_ERR_INVALID, "sgl_get_tuning: unknown key '%s'", key);
     *value = it->second;
+    return SGL_OK;
+}
+
+SGL_EXPORT int sgl_csr_matmul_rule(int narrow_cap, int window_cols, int64_t n, int *h_rule) {
+    if (!h_rule) return sgl::fail(SGL_ERR_INVALID, "sgl_csr_matmul_rule: NULL h_rule");
+    if (n < 0 || n > INT32_MAX) return sgl::fail(SGL_ERR_INVALID, "sgl_csr_matmul_rule: bad sizes (n must lie in [0, 2^31))");
+    sgl::SpgemmRule rule;
+    const int rc = sgl::spgemm_rule("sgl_csr_matmul_rule", narrow_cap, window_cols, n, rule);
+    if (rc != SGL_OK) return rc;
+    h_rule[0] = rule.narrow_cap;
+    h_rule[1] = rule.window_cols;
     return SGL_OK;
 }
 

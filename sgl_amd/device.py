@@ -19,7 +19,7 @@ __all__ = [
     "normalize_block", "degree_powers", "PreparedAdjacency", "PreparedBlock",
     "placed_empty", "MEM_MODES",
     "hop_reduce", "hop_concat", "hop_reduce_grad", "hop_concat_grad", "hop_lincomb", "hop_wsum1d", "hop_wsum2d", "hop_scores", "hop_scores2", "hop_gate", "gate_fusable", "nafs_aggregate", "nafs_prefix",
-    "gather_rows", "edge_dot", "ensemble_combine",
+    "gather_rows", "edge_dot", "ensemble_combine", "csr_matmul",
 ]
 
 
@@ -50,7 +50,7 @@ def _esize(dtype):
 
 # entry points whose last argument is not a stream
 _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
-                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch"})
+                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2012,6 +2012,62 @@ def csr_merge(a, b, mode="sum", lanes=0, positions=False):
     _wrote(out_rowptr, out_col, out_val, pos_a, pos_b)
     out = DeviceAdjacency(out_rowptr, out_col[:m], out_val[:m], (n_rows, n_cols))
     return (out, (pos_a[:m], pos_b[:m])) if positions else out
+
+
+CSR_MATMUL_VALUES = {"sum": _lib.SGL_SPGEMM_SUM, "ones": _lib.SGL_SPGEMM_ONES}
+CSR_MATMUL_NARROW_CAPS = _lib.SGL_SPGEMM_NARROW_CAPS     # the compiled LDS slices of spgemm_narrow_kernel (sgl_spgemm.hip)
+CSR_MATMUL_WINDOWS = _lib.SGL_SPGEMM_WINDOWS             # the compiled bitmap windows of spgemm_wide_kernel
+
+
+def csr_matmul(a, b, values="sum", narrow_cap=0, window_cols=0):
+    """The product a . b of two canonical device CSRs, [m, k] and [k, n], as a new one of shape [m, n] (sgl_csr_matmul_rowptr +
+    sgl_csr_matmul_fill; include/sgl_spgemm.h states the contract).  The pattern is structural: (i, c) is stored iff some stored
+    a[i, j] meets a stored b[j, c], and a sum that comes out exactly zero STAYS stored -- scipy's product drops such entries
+    ([[1, -1], [2, 3]] @ [[1, 0], [1, 5]] has 3 stored entries there, 4 here).  values="sum": every value is the float32 chain
+    acc = acc + a[i, j] * b[j, c] over a's row in storage order, the product rounded before the sum (scipy's float32 arithmetic, bit
+    for bit where scipy prunes nothing); values="ones": every stored value is 1.0 and neither side's values are read (what
+    meta-path sampling needs).  narrow_cap / window_cols: 0 = auto, or one of CSR_MATMUL_NARROW_CAPS / CSR_MATMUL_WINDOWS -- which
+    rows are sorted in LDS and how many columns one LDS bitmap covers; the result's bytes do not depend on them.  The first call
+    synchronises the device (the size of the result comes back through the host and its scratch is freed with hipFree)."""
+    from .io import DeviceAdjacency
+    rowptr_a, col_a = _csr_arrays(a, "csr_matmul")
+    rowptr_b, col_b = _csr_arrays(b, "csr_matmul")
+    dv = rowptr_a.device
+    if a.shape[1] != b.shape[0]:
+        raise ValueError(f"csr_matmul: the shapes do not chain: {tuple(a.shape)} and {tuple(b.shape)}")
+    if rowptr_b.device != dv:
+        raise ValueError("csr_matmul: a and b must live on one device")
+    (m, k), n = a.shape, b.shape[1]
+    if values not in CSR_MATMUL_VALUES:
+        raise ValueError(f"csr_matmul: values must be one of {tuple(CSR_MATMUL_VALUES)}, not {values!r}")
+    narrow_cap, window_cols = int(narrow_cap), int(window_cols)
+    if narrow_cap != 0 and narrow_cap not in CSR_MATMUL_NARROW_CAPS:
+        raise ValueError(f"csr_matmul: narrow_cap must be 0 (auto) or one of {CSR_MATMUL_NARROW_CAPS}, not {narrow_cap}")
+    if window_cols != 0 and window_cols not in CSR_MATMUL_WINDOWS:
+        raise ValueError(f"csr_matmul: window_cols must be 0 (auto) or one of {CSR_MATMUL_WINDOWS}, not {window_cols}")
+    sides = []
+    for name, adj, rowptr, col in (("a", a, rowptr_a, col_a), ("b", b, rowptr_b, col_b)):
+        val = adj.val
+        nnz = int(adj.col.numel())
+        if not (torch.is_tensor(val) and val.device == dv and val.dtype == torch.float32 and val.is_contiguous() and val.numel() == nnz):
+            raise TypeError(f"csr_matmul: {name}.val must be a contiguous float32 tensor of nnz values on the device of a.rowptr")
+        if adj.shape[0] > 0 and int(rowptr[-1]) != nnz:
+            raise ValueError(f"csr_matmul: {name}.rowptr ends at {int(rowptr[-1])}, {name}.col holds {nnz} entries")
+        if nnz == 0:
+            val = torch.zeros(1, dtype=torch.float32, device=dv)
+        sides.append((rowptr, col, val, nnz))
+    (ra, ca, va, na), (rb, cb, vb, nb) = sides
+    out_rowptr = torch.empty(m + 1, dtype=torch.int64, device=dv)
+    total = c_int64(0)
+    _call(dv, "sgl_csr_matmul_rowptr", ptr(ra), ptr(ca), na, ptr(rb), ptr(cb), nb, m, k, n, narrow_cap, window_cols, ptr(out_rowptr),
+          ctypes.byref(total))
+    nnz = total.value
+    out_col = torch.empty(max(nnz, 1), dtype=torch.int32, device=dv)
+    out_val = torch.empty(max(nnz, 1), dtype=torch.float32, device=dv)
+    _call(dv, "sgl_csr_matmul_fill", ptr(ra), ptr(ca), ptr(va), na, ptr(rb), ptr(cb), ptr(vb), nb, m, k, n, CSR_MATMUL_VALUES[values], narrow_cap,
+          window_cols, ptr(out_rowptr), ptr(out_col), ptr(out_val))
+    _wrote(out_rowptr, out_col, out_val)
+    return DeviceAdjacency(out_rowptr, out_col[:nnz], out_val[:nnz], (m, n))
 
 
 def kmeans_assign(x, centres, want_dist=True):

@@ -3,15 +3,15 @@ HeteroNodeDataset, sgl/dataset/choose_edge_type.py), with the edge lists and the
 
   HeteroGraph          the reference's constructor arguments; edge ends are GLOBAL node ids, the node types are contiguous id ranges
                        in `node_types` order (the only layout the reference's start_pos arithmetic supports: anything else raises).
-  HeteroNodeDataset    a graph and the three index sets; sample_by_edge_type / nars_preprocess as in the reference, the relation
+  HeteroNodeDataset    a graph and the three index sets; sample_by_edge_type / nars_preprocess / sample_by_meta_path as in the reference, the relation
                        sub-graph built ON the device: local ids, the mirror of an edge type whose two ends differ in type, all lists
-                       through io.coo_to_csr_device once, every stored value 1.0 (the reference's `adj.data = ones`).
+                       through io.coo_to_csr_device once, every stored value 1.0 (the reference's `adj.data = ones`).  A meta path
+                       "a__to__b__to__c" is the product of its edge types' 0/1 patterns on the device (device.csr_matmul, K17).
   choose_multi_subgraphs   the reference's ChooseMultiSubgraphs under a seed.  The reference walks a Python set of strings, so its draw
                        depends on the interpreter's hash seed; here candidates are walked in list order and drawn from random.Random(seed):
                        the same properties (sorted tuples, distinct, connected to the predict class, reverse duplicates removed), the
                        same draw for the same seed.
-
-Not here: sample_by_meta_path (a sparse x sparse product the reference itself calls extremely slow; neither model uses it)."""
+"""
 import math
 import random
 import warnings
@@ -194,19 +194,9 @@ class HeteroNodeDataset:
         edge_types = _check_edge_types(edge_types)
         data = self._data
         touched = {t for e in edge_types for t in edge_type_ends(e)}
-        offsets, local = data.node_id_offsets, {}
-        num_node, feats, node_id = 0, [], []
-        for t in data.node_types:                               # the sampled types keep the graph's order
-            if t not in touched:
-                continue
-            local[t] = offsets[t] - num_node                    # global id - local[t] = id inside the sub-graph
-            num_node += data.num_node[t]
-            if data[t].x is None:
-                raise ValueError(f"{t} nodes have no features!")
-            feats.append(data[t].x)
-            node_id += data.node_id_dict[t]
-        if len({f.shape[1] for f in feats}) != 1:
-            raise ValueError("the sampled node types have features of different widths")
+        place, num_node, x, node_id = self._sampled_nodes(touched)     # the sampled types keep the graph's order
+        offsets = data.node_id_offsets
+        local = {t: offsets[t] - place[t] for t in place}       # global id - local[t] = id inside the sub-graph
         rows, cols = [], []
         for e in edge_types:
             src, dst = edge_type_ends(e)
@@ -219,8 +209,63 @@ class HeteroNodeDataset:
         rows, cols = torch.cat(rows), torch.cat(cols)
         adj = io.coo_to_csr_device(rows, cols, torch.ones(rows.numel(), dtype=torch.float32, device=data.device), num_node, device=data.device)
         adj.val.fill_(1.0)                                      # edges given more than once count once
-        x = feats[0] if len(feats) == 1 else torch.cat(feats, dim=0)
-        return adj, x, torch.LongTensor(node_id)
+        return adj, x, node_id
+
+    def _sampled_nodes(self, touched):
+        """(row offset of every touched type inside the sub-graph, its node count, X, node ids): the touched types in the graph's order"""
+        data = self._data
+        place, num_node, feats, node_id = {}, 0, [], []
+        for t in data.node_types:
+            if t not in touched:
+                continue
+            place[t] = num_node
+            num_node += data.num_node[t]
+            if data[t].x is None:
+                raise ValueError(f"{t} nodes have no features!")
+            feats.append(data[t].x)
+            node_id += data.node_id_dict[t]
+        if len({f.shape[1] for f in feats}) != 1:
+            raise ValueError("the sampled node types have features of different widths")
+        return place, num_node, feats[0] if len(feats) == 1 else torch.cat(feats, dim=0), torch.LongTensor(node_id)
+
+    def sample_by_meta_path(self, meta_path, undirected=True):
+        """(DeviceAdjacency, X, node_id) of the composite relation "a__to__b__to__c...": the product of the stored edge types a__to__b,
+        b__to__c, ... as 0/1 patterns (device.csr_matmul, values="ones"), placed into the sub-graph over the first and the last type in
+        the graph's order -- rows are ids of the first type, columns ids of the last, the later type shifted by the earlier one's
+        size -- and, with `undirected`, merged with its mirror.  Every stored value is 1.0.  A three-part string is one edge type:
+        sample_by_edge_type.  Every factor has the shape of its two types' node counts (the reference infers it from the largest id
+        present, so its own product exists only where those agree; there the results are equal)."""
+        if not isinstance(meta_path, str):
+            raise TypeError("The given meta path must be a string!")
+        parts = meta_path.split("__")
+        if len(parts) == 3:
+            return self.sample_by_edge_type(meta_path, undirected)
+        if len(parts) < 5 or len(parts) % 2 == 0 or not all(parts[0::2]):
+            raise ValueError(f"a meta path reads '<type>__to__<type>__to__<type>...', not {meta_path!r}")
+        from . import device as dev
+        from . import transforms
+        data = self._data
+        types = parts[0::2]
+        chain = [types[i] + EDGE_TYPE_DELIMITER + types[i + 1] for i in range(len(types) - 1)]
+        edges = [data[e] for e in chain]                        # a missing edge type raises here, before anything is built
+        start, end = types[0], types[-1]
+        place, num_node, x, node_id = self._sampled_nodes({start, end})
+        offsets, built = data.node_id_offsets, {}
+        for e, edge in zip(chain, edges):                       # every edge type once, in type-local ids
+            if e not in built:
+                src, dst = edge_type_ends(e)
+                row, col = edge.edge_index
+                built[e] = io.coo_to_csr_device(row - offsets[src], col - offsets[dst], torch.ones(row.numel(), dtype=torch.float32, device=data.device),
+                                                data.num_node[src], device=data.device, num_col=data.num_node[dst])
+        adj = built[chain[0]]
+        for e in chain[1:]:
+            adj = dev.csr_matmul(adj, built[e], values="ones")
+        row_map = torch.arange(place[start], place[start] + data.num_node[start], dtype=torch.int32, device=data.device)
+        col_map = torch.arange(place[end], place[end] + data.num_node[end], dtype=torch.int32, device=data.device)
+        adj = dev.csr_select(adj, row_map=row_map, col_map=col_map, n_rows_out=num_node, n_cols_out=num_node)
+        if undirected is True:
+            adj = transforms.to_undirected(adj, reduce="keep")
+        return adj, x, node_id
 
     def nars_preprocess(self, edge_types, predict_class, random_subgraph_num, subgraph_edge_type_num, seed=0):
         """{edge type tuple: sample_by_edge_type(tuple)} for random_subgraph_num of the combinations choose_multi_subgraphs finds"""
