@@ -184,6 +184,14 @@ SPGEMM_PROTOTYPES = {
                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sgl_kmeans_mfma.h: K18, the k-means assignment step on the matrix cores -- a header and a table of their own as well
+SGL_KMEANS_MATRIX_MAX_K = 256
+KMEANS_MATRIX_PROTOTYPES = {
+    "sgl_kmeans_assign_matrix_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    "sgl_kmeans_assign_matrix_rule": (c_int, [c_int64, c_int64, c_int, POINTER(c_int)]),
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -213,7 +221,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -m sgl_amd.csrc.build` (needs hipcc). "
                 "sgl_amd has no CPU fallback for the propagation hot path.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items()):
+        for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items(),
+                                  *KMEANS_MATRIX_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -143,6 +143,7 @@ struct SliceFamily {
     static constexpr ChunkList chunks(int vec) { return vec == 4 ? V4::list() : V1::list(); }
 };
 using KmeansSlices = SliceFamily<Chunks<2, 3, 4, 6, 8>, Chunks<2, 4, 8, 16, 32>>;   // K9: rows of up to 2048 floats
+using KmeansMatrixTiles = Chunks<1, 2, 3, 4, 6, 8>;   // K18: accumulator tiles of 32 centres per row tile, k <= 256 (sgl_kmeans_mfma.hip)
 using EdgeLossSlices = SliceFamily<Chunks<2, 4, 8>, Chunks<2, 8, 32>>;              // K11
 using ClusterLossSlices = SliceFamily<Chunks<2, 4, 8>, Chunks<2, 8, 32>>;           // K12
 using ClassLossSlices = SliceFamily<Chunks<2, 4>, Chunks<2, 4, 8, 16>>;             // K14: up to 1024 logits in at most 16 registers

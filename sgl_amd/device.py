@@ -2070,11 +2070,27 @@ def csr_matmul(a, b, values="sum", narrow_cap=0, window_cols=0):
     return DeviceAdjacency(out_rowptr, out_col[:nnz], out_val[:nnz], (m, n))
 
 
-def kmeans_assign(x, centres, want_dist=True):
+KMEANS_FORMS = ("direct", "matrix")
+KMEANS_MATRIX_MAX_K = _lib.SGL_KMEANS_MATRIX_MAX_K      # the centres the accumulator tiles of sgl_kmeans_mfma.hip cover
+
+
+def kmeans_assign(x, centres, want_dist=True, form="direct", shift=None):
     """(labels, mindist) of the k-means assignment step (sgl_kmeans_assign_f32): labels[i] = argmin_j |x[i] - centres[j]|^2 (int64 [n],
     the lowest index on a tie) and that minimum (float32 [n]; None with want_dist=False) -- the direct sum of squared differences, not
     the expanded form.  x: [n, d], centres: [k, d] float32 CUDA matrices on one device, read in place (padded buffers, column views).
-    A row that holds NaN gets label 0 and mindist NaN.  No atomics: two runs are bit-equal."""
+    A row that holds NaN gets label 0 and mindist NaN.  No atomics: two runs are bit-equal.
+
+    form="matrix" (sgl_kmeans_assign_matrix_f32, include/sgl_kmeans_mfma.h): the nearest centre is searched in the centred expanded
+    form |c - s|^2 - 2 <c - s, x - s> on the matrix cores, mindist is the direct form for the centre that was chosen.  shift: the
+    vector s, a float32 [d] tensor on x's device, used as given; None = centres.mean(0) in float32.  Labels can differ from the direct
+    form only between centres that are closer than the rounding of the form (the header has the bound).  k <= KMEANS_MATRIX_MAX_K:
+    a larger k raises, nothing falls back to the direct kernel."""
+    if form not in KMEANS_FORMS:
+        raise ValueError(f"kmeans_assign: form must be one of {KMEANS_FORMS}, got {form!r}")
+    if shift is not None and form == "direct":
+        raise ValueError("kmeans_assign: shift belongs to form='matrix' (the direct form is translation-invariant)")
+    if form == "matrix" and torch.is_tensor(centres) and centres.dim() == 2 and centres.shape[0] > KMEANS_MATRIX_MAX_K:
+        raise ValueError(f"kmeans_assign: form='matrix' takes at most {KMEANS_MATRIX_MAX_K} centres, got {centres.shape[0]}")
     _no_bf16("kmeans_assign", x, centres)
     _check_mat(x, "x")
     _check_mat(centres, "centres")
@@ -2083,8 +2099,19 @@ def kmeans_assign(x, centres, want_dist=True):
     n, k = x.shape[0], centres.shape[0]
     if k < 1 and n > 0:
         raise ValueError("kmeans_assign: at least one centre is needed")
+    if form == "matrix":
+        if shift is None:
+            shift = centres.mean(0) if k else torch.zeros(x.shape[1], dtype=torch.float32, device=x.device)
+        elif not (torch.is_tensor(shift) and shift.is_cuda and shift.device == x.device and shift.dtype == torch.float32
+                  and shift.shape == (x.shape[1],)):
+            raise ValueError("kmeans_assign: shift must be a float32 [d] tensor on x's device")
+        shift = shift.contiguous()
     labels = torch.empty(n, dtype=torch.int64, device=x.device)
     mindist = torch.empty(n, dtype=torch.float32, device=x.device) if want_dist else None
+    if form == "matrix":
+        _call(x.device, "sgl_kmeans_assign_matrix_f32", ptr(x), _ld(x), n, x.shape[1], ptr(centres), _ld(centres), k, ptr(shift), ptr(labels),
+              _opt_ptr(mindist))
+        return labels, mindist
     _call(x.device, "sgl_kmeans_assign_f32", ptr(x), _ld(x), n, x.shape[1], ptr(centres), _ld(centres), k, ptr(labels), _opt_ptr(mindist))
     return labels, mindist
 

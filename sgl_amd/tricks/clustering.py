@@ -89,14 +89,14 @@ class _Update:
         return sums / counts.to(torch.float32)[:, None]
 
 
-def _lloyd(x, centres, update, max_iter, tol_abs):
+def _lloyd(x, centres, update, max_iter, tol_abs, assign="direct"):
     """sklearn's _kmeans_single_lloyd (sklearn/cluster/_kmeans.py): assign, update, stop when the labels equal the previous
     iteration's, else when the summed squared centre shift is <= tol_abs; after a stop by shift (or by max_iter) assign once more so
-    that the labels belong to the returned centres"""
+    that the labels belong to the returned centres.  assign: the form of every assignment (device.kmeans_assign's `form`)"""
     labels_old, strict, n_iter = None, False, 0
     labels = mindist = None
     for it in range(max_iter):
-        labels, mindist = dev.kmeans_assign(x, centres)
+        labels, mindist = dev.kmeans_assign(x, centres, form=assign)
         new = update(labels, mindist)
         shift = float(((new.to(torch.float64) - centres.to(torch.float64)) ** 2).sum())
         centres, n_iter = new, it + 1
@@ -107,7 +107,7 @@ def _lloyd(x, centres, update, max_iter, tol_abs):
             break
         labels_old = labels
     if not strict:
-        labels, mindist = dev.kmeans_assign(x, centres)
+        labels, mindist = dev.kmeans_assign(x, centres, form=assign)
     return KMeansResult(labels, centres, float(mindist.sum(dtype=torch.float64)), n_iter)
 
 
@@ -131,7 +131,7 @@ def _seed_plus_plus(x, k, gen):
 
 
 @torch.no_grad()
-def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-means++"):
+def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-means++", assign="direct"):
     """Lloyd's k-means of the rows of x ([n, d] float32 CUDA tensor; an ndarray or host tensor is uploaded to the current device) on
     the device; returns a KMeansResult on x's device.
 
@@ -143,7 +143,10 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     candidate per step (sklearn's greedy variant tries 2 + ln k candidates per step), with draws from a torch.Generator seeded with
     `seed` (None: a fresh random seed): same seed, same device, same input give a bit-equal result -- nothing here uses atomics.
     An empty cluster takes the row with the largest distance to its centre (the lowest index on ties), which leaves its former
-    cluster; several empty clusters take rows in descending order of distance (a property of this function, not sklearn parity)."""
+    cluster; several empty clusters take rows in descending order of distance (a property of this function, not sklearn parity).
+    assign: "direct" (K9) or "matrix" (K18: the assignments of the Lloyd loop search the nearest centre on the matrix cores, centred
+    on the mean of the centres; at most device.KMEANS_MATRIX_MAX_K clusters).  The seeding stays on the direct kernel: one centre per
+    call leaves a matrix unit nothing to do."""
     if not torch.is_tensor(x):
         x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
     if not x.is_cuda:
@@ -152,6 +155,10 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     dev._check_mat(x, "x")
     n, d = x.shape
     k = int(n_clusters)
+    if assign not in dev.KMEANS_FORMS:
+        raise ValueError(f"assign must be one of {dev.KMEANS_FORMS}, got {assign!r}")
+    if assign == "matrix" and k > dev.KMEANS_MATRIX_MAX_K:
+        raise ValueError(f"assign='matrix' takes at most {dev.KMEANS_MATRIX_MAX_K} clusters, got {k}")
     if k < 1 or n < k:
         raise ValueError(f"n_samples={n} should be >= n_clusters={k} >= 1")
     if max_iter < 1 or n_init < 1:
@@ -173,7 +180,7 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     update = _Update(x, k)
     best = None
     for _ in range(n_init):
-        run = _lloyd(x, given if given is not None else _seed_plus_plus(x, k, gen), update, max_iter, tol_abs)
+        run = _lloyd(x, given if given is not None else _seed_plus_plus(x, k, gen), update, max_iter, tol_abs, assign)
         if best is None or run.inertia < best.inertia:
             best = run
     return best
@@ -248,18 +255,19 @@ NodeClusteringNAFS keeps (best_hop_acc, best_hop_nmi, best_hop_adjscore, acc, nm
 
 @torch.no_grad()
 def nafs_node_clustering(adj, x, y, hops, r_list=(0.5, 0.4, 0.3, 0.2, 0.1, 0), method="mean", n_init=20, seed=42, device="cuda",
-                         strict_order=False, reorder=None):
+                         strict_order=False, reorder=None, assign="direct"):
     """NodeClusteringNAFS._execute (sgl/tasks/node_clustering.py:171-258): for every hop count of `hops` (an int = range(hops), or a
     list) the NAFS ensemble features, their k-means labels (k = the number of distinct labels in y, n_init runs seeded with `seed`)
     and (acc, nmi, adjscore) against y; then the best-hop bookkeeping of lines 189-197 (strictly greater wins, the bests start at
     0).  One nafs_ensemble_sweep -- one propagation per r for ALL hop counts -- whose consumer clusters and scores each feature matrix
-    as soon as its ensemble is complete; only three floats per hop count outlive it.  Returns a NodeClusteringResult."""
+    as soon as its ensemble is complete; only three floats per hop count outlive it.  assign: kmeans' (the form of the assignment
+    step).  Returns a NodeClusteringResult."""
     device = torch.device(device)
     y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(-1).to(device)
     k = int(torch.unique(y).numel())
 
     def cluster(hop, feats):
-        return clustering_scores(y, kmeans(feats, k, n_init=n_init, seed=seed).labels)
+        return clustering_scores(y, kmeans(feats, k, n_init=n_init, seed=seed, assign=assign).labels)
 
     metrics = nafs_ensemble_sweep(adj, x, hops, r_list=r_list, method=method, device=device, strict_order=strict_order, reorder=reorder,
                                   consume=cluster)
@@ -350,18 +358,18 @@ def _model_output(model, nodes, device):
     return model.model_forward(nodes, device) if hasattr(model, "model_forward") else model(nodes)
 
 
-def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda"):
+def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda", assign="direct"):
     """clustering_train of the reference (sgl/tasks/utils.py:116-136), one step: model_forward, k-means of the DETACHED output
     (kmeans above: n_init runs seeded with `seed`, on the device -- the reference copies the output to the host for sklearn),
     cluster_loss on its labels and centres, backward, optimizer.step, and the three scores of the k-means labels against y.
-    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated."""
+    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated.  assign: kmeans'."""
     device = torch.device(device)
     if optimizer is not None:
         model.train()
         optimizer.zero_grad()
     with torch.set_grad_enabled(optimizer is not None):
         out = _model_output(model, train_idx, device)
-        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed)
+        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed, assign=assign)
         loss = cluster_loss(out, km.labels, km.centres, check=False)
         if optimizer is not None:
             loss.backward()

@@ -14,7 +14,12 @@ mismatch ends the run with a non-zero exit status.
 Per width the JSON holds: ms of both candidates (median, min, max) for the assignment and for the iteration, their ratios, the
 assignment as a multiple of ONE read of X at the measured copy ceiling (6.29 TB/s), and the peak allocation of both.
 "accepted": the kernel's median is not above the composition's by more than the spread (max - min) the repetitions of the two
-recorded."""
+recorded.
+
+The matrix leg (--matrix-out, default profiles/kmeans_matrix.json; --matrix-only skips the two-way legs above): the
+matrix-core form (form="matrix"), the direct kernel and the torch composition interleaved THREE ways under the same protocol, labels
+of sampled rows checked against float64 first (the bound of include/sgl_kmeans_mfma.h), one Lloyd iteration per form, and
+"matrix_faster": the matrix form's min-max lies wholly below the direct kernel's."""
 import argparse
 import json
 import os
@@ -79,6 +84,51 @@ def compare(ours, theirs, args, tag):
     return r
 
 
+def matrix_leg(x, c, args):
+    """matrix form, direct kernel and torch.cdist().argmin interleaved in one process; one Lloyd iteration per form"""
+    n, d = x.shape
+    k = c.shape[0]
+    shift = c.mean(0)
+    labels, mindist = dev.kmeans_assign(x, c, form="matrix")
+    pick = torch.randperm(n, device=x.device)[:4096]
+    dist = torch.stack([((x[pick].double() - cj.double()) ** 2).sum(1) for cj in c], dim=1)      # differences first: exact zeros stay zeros
+    xn, cn = (x[pick].double() - shift.double()).norm(dim=1)[:, None], (c.double() - shift.double()).norm(dim=1)[None, :]
+    bound = (d + 3) * 2.0 ** -23 * (cn ** 2 + 2 * xn * cn) + 2.0 ** -23 * dist.sqrt() * (xn + cn)
+    got, best = labels[pick][:, None], dist.argmin(1)[:, None]
+    excess = (dist.gather(1, got) - dist.gather(1, best)) - 2 * (bound.gather(1, got) + bound.gather(1, best))
+    worst = float(((mindist[pick].double() - dist.gather(1, got)[:, 0]).abs() / dist.gather(1, got)[:, 0].clamp_min(1e-300)).max())
+    differ = int((got != best).sum())
+    ok = float(excess.max()) <= 0 and worst <= (d + 3) * 2.0 ** -23
+    print(f"EXP kmeans-matrix d={d}: {len(pick)} sampled rows against float64: {differ} labels off the argmin, largest excess over the "
+          f"bound {float(excess.max()):.3e}, worst relative distance error {worst:.2e}{'' if ok else '  WRONG'}", flush=True)
+    if not ok:
+        raise SystemExit(f"bench_kmeans.py: the matrix form's labels are wrong at d={d}; nothing was timed")
+    del labels, mindist, dist, bound, excess
+    update = clustering._Update(x, k)
+    legs = {"matrix": lambda: dev.kmeans_assign(x, c, form="matrix"), "matrix_labels_only": lambda: dev.kmeans_assign(x, c, want_dist=False, form="matrix"),
+            "direct": lambda: dev.kmeans_assign(x, c), "torch": lambda: torch.cdist(x, c).argmin(1),
+            "iteration_matrix": lambda: update(*dev.kmeans_assign(x, c, form="matrix")), "iteration_direct": lambda: update(*dev.kmeans_assign(x, c))}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for _ in range(args.reps):                     # interleaved: every candidate sees the same drift of the machine
+        for name, fn in legs.items():
+            ms[name].append(timed(fn))
+    r = {name + "_ms": stats(v) for name, v in ms.items()}
+    one_read_ms = n * d * 4 / COPY_CEILING_BYTES_PER_S * 1e3
+    r["one_read_of_x_ms"] = one_read_ms
+    for name in ("matrix", "matrix_labels_only", "direct"):
+        r[name + "_over_one_read_of_x"] = r[name + "_ms"]["median"] / one_read_ms
+    r["matrix_tflops"] = 2.0 * n * k * d / (r["matrix_ms"]["median"] * 1e-3) * 1e-12
+    r["matrix_faster"] = bool(r["matrix_ms"]["max"] < r["direct_ms"]["min"])
+    print(f"EXP kmeans-matrix d={d}: " + ", ".join(f"{name} {r[name + '_ms']['median']:.3f} ms ({r[name + '_ms']['min']:.3f}-{r[name + '_ms']['max']:.3f})"
+                                                  for name in legs) + f"; matrix = {r['matrix_over_one_read_of_x']:.2f} x one read of X "
+          f"({one_read_ms:.3f} ms), {'faster than' if r['matrix_faster'] else 'NOT wholly below'} the direct kernel", flush=True)
+    return r
+
+
 def one_width(x, c, args):
     n, d = x.shape
     k = c.shape[0]
@@ -134,6 +184,8 @@ def main():
     ap.add_argument("--dims", default="100,128,600")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans.json"))
+    ap.add_argument("--matrix-out", default=os.path.join(ROOT, "profiles", "kmeans_matrix.json"))
+    ap.add_argument("--matrix-only", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_kmeans.py needs a GPU (nothing here is measured without one)")
@@ -146,18 +198,28 @@ def main():
     result = {"n_rows": args.n, "k": args.k, "reps": args.reps, "warmup": args.warmup, "device": torch.cuda.get_device_name(device),
               "copy_ceiling_bytes_per_s": COPY_CEILING_BYTES_PER_S, "shapes": {}}
     failed = []
+    matrix = {key: result[key] for key in ("n_rows", "k", "reps", "warmup", "device", "copy_ceiling_bytes_per_s")}
+    matrix["shapes"] = {}
     for d in [int(v) for v in args.dims.split(",")]:
         c = torch.randn((args.k, d), generator=g, device=device, dtype=torch.float32)
         x = torch.randn((args.n, d), generator=g, device=device, dtype=torch.float32)
         x += c[torch.randint(0, args.k, (args.n,), generator=g, device=device)]
         c = x[torch.randint(0, args.n, (args.k,), generator=g, device=device)].clone()       # a seeding, not the optimum
-        r = one_width(x, c, args)
-        result["shapes"][f"d{d}"] = {"d": d, **r}
-        failed += [f"d{d}_{what}" for what in ("assign", "iteration") if not r[what]["accepted"]]
+        matrix["shapes"][f"d{d}"] = {"d": d, **matrix_leg(x, c, args)}
+        if not args.matrix_only:
+            r = one_width(x, c, args)
+            result["shapes"][f"d{d}"] = {"d": d, **r}
+            failed += [f"d{d}_{what}" for what in ("assign", "iteration") if not r[what]["accepted"]]
         del x, c
         torch.cuda.empty_cache()
     result["not_accepted"] = failed
-    if args.out:
+    if args.matrix_out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.matrix_out)), exist_ok=True)
+        with open(args.matrix_out, "w") as f:
+            json.dump(matrix, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"EXP kmeans wrote {args.matrix_out}", flush=True)
+    if args.out and not args.matrix_only:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1, sort_keys=True)
