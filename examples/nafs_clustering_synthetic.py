@@ -3,7 +3,8 @@
 sgl/tasks/node_clustering.py:121-258) end to end on the MI355X, on a planted-partition graph.
 
 `nafs_node_clustering` runs ONE propagation per r for all hop counts (nafs_ensemble_sweep) and clusters each hop count's features
-where they lie: k-means with the assignment kernel (sgl_kmeans_assign_f32) and the membership-matrix SpMM as the centre update, then
+where they lie: k-means with the assignment kernel (sgl_kmeans_assign_f32) and the membership-matrix SpMM as the centre update
+(--update sums: the one-pass per-cluster sums kernel, sgl_cluster_sums_f32), then
 acc / nmi / adjscore from one contingency table.  Nothing but the graph and the features is uploaded, and nothing but three floats
 per hop count comes back.
 
@@ -47,10 +48,12 @@ def main():
     ap.add_argument("--method", default="mean", choices=("mean", "max", "concat", "simple"))
     ap.add_argument("--n-init", type=int, default=5)
     ap.add_argument("--assign", default="direct", choices=("direct", "matrix"), help="the k-means assignment: K9, or K18 on the matrix cores")
+    ap.add_argument("--update", default="spmm", choices=("spmm", "sums"), help="the k-means centre update: membership-matrix SpMM, or K19's one-pass sums")
     a = ap.parse_args()
     adj, x, y = planted_partition(a.nodes, a.classes, 10, 0.8, 32, seed=0)
     t0 = time.time()
-    res = nafs_node_clustering(adj, x, y, a.hops, r_list=(0.5, 0.3, 0), method=a.method, n_init=a.n_init, seed=42, assign=a.assign)
+    res = nafs_node_clustering(adj, x, y, a.hops, r_list=(0.5, 0.3, 0), method=a.method, n_init=a.n_init, seed=42, assign=a.assign,
+                               update=a.update)
     took = time.time() - t0
     print(f"{a.nodes} nodes, {adj.nnz} edges, {a.classes} blocks, method {a.method}, n_init {a.n_init}: {took:.2f} s")
     print("hops    acc     nmi     adjscore")

@@ -50,7 +50,8 @@ def _esize(dtype):
 
 # entry points whose last argument is not a stream
 _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
-                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule"})
+                        "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule",
+                        "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2114,6 +2115,42 @@ def kmeans_assign(x, centres, want_dist=True, form="direct", shift=None):
         return labels, mindist
     _call(x.device, "sgl_kmeans_assign_f32", ptr(x), _ld(x), n, x.shape[1], ptr(centres), _ld(centres), k, ptr(labels), _opt_ptr(mindist))
     return labels, mindist
+
+
+CLUSTER_SUMS_MAX_K = _lib.SGL_CLUSTER_SUMS_MAX_K        # the clusters whose accumulators fit the LDS of sgl_cluster_sums.hip
+
+
+def cluster_sums(x, labels, k, check=True):
+    """(sums, counts) of the k-means centre update (sgl_cluster_sums_f32, include/sgl_cluster_sums.h): sums[j] = the sum of the rows
+    x[i] with labels[i] = j (float32 [k, d]) and counts[j] their number (int64 [k]), in ONE pass over x: no sort, no CSR, no plan,
+    no atomics -- two runs are bit-equal, and the bits do not depend on x's pitch or alignment.  An empty cluster gives a zero row
+    and a zero count.  x: [n, d] float32 CUDA matrix, read in place (padded buffers, column views); labels: contiguous int64 [n] on
+    x's device.  check=True costs one host read and raises ValueError on a label outside [0, k); check=False (labels that come from
+    kmeans_assign) validates nothing: such a row is skipped.  k <= CLUSTER_SUMS_MAX_K: a larger k raises.  The partial tables are a
+    scratch tensor of this call (torch's caching allocator)."""
+    _no_bf16("cluster_sums", x)
+    _check_mat(x, "x")
+    k = int(k)
+    if k < 1:
+        raise ValueError("cluster_sums: at least one cluster is needed")
+    if k > CLUSTER_SUMS_MAX_K:
+        raise ValueError(f"cluster_sums: at most {CLUSTER_SUMS_MAX_K} clusters, got {k}")
+    n, d = x.shape
+    if not (torch.is_tensor(labels) and labels.device == x.device and labels.dtype == torch.int64 and labels.dim() == 1
+            and labels.numel() == n and labels.is_contiguous()):
+        raise ValueError("cluster_sums: `labels` must be a contiguous int64 [n] tensor on x's device")
+    if check and n:
+        lo, hi = (int(v) for v in torch.aminmax(labels))
+        if lo < 0 or hi >= k:
+            raise ValueError(f"cluster_sums: label {lo if lo < 0 else hi} is outside [0, {k})")
+    sums = torch.empty((k, d), dtype=torch.float32, device=x.device)
+    counts = torch.empty(k, dtype=torch.int64, device=x.device)
+    nbytes = int(_call(None, "sgl_cluster_sums_scratch", n, d, k, raw=True))
+    if nbytes < 0:
+        raise _lib.SglHipError(f"sgl_cluster_sums_scratch failed: {_lib.last_error()}")
+    scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    _call(x.device, "sgl_cluster_sums_f32", ptr(x), _ld(x), n, d, ptr(labels), k, ptr(sums), max(d, 1), ptr(counts), ptr(scratch))
+    return sums, counts
 
 
 def cluster_loss_grad(x, centres, labels, w, dx=None, row_loss=None):

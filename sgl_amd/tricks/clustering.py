@@ -59,13 +59,16 @@ def _mean_variance(x):
 class _Update:
     """the centre update of one matrix x: centres = (M x) / counts, M the k x n membership matrix of the labels"""
 
-    def __init__(self, x, k):
+    def __init__(self, x, k, form="spmm"):
         n = x.shape[0]
-        self.x, self.k = x, k
-        self.rows = torch.arange(n, dtype=torch.int64, device=x.device)
-        self.ones = torch.ones(n, dtype=torch.float32, device=x.device)
+        self.x, self.k, self.form = x, k, form
+        if form == "spmm":
+            self.rows = torch.arange(n, dtype=torch.int64, device=x.device)
+            self.ones = torch.ones(n, dtype=torch.float32, device=x.device)
 
     def sums(self, labels):
+        if self.form == "sums":                      # K19: one pass over x, no membership matrix
+            return dev.cluster_sums(self.x, labels, self.k, check=False)
         from ..io import coo_to_csr_device
         m = coo_to_csr_device(labels, self.rows, self.ones, self.k, device=self.x.device, num_col=self.x.shape[0])
         return dev.DeviceCSR(m.rowptr, m.col, m.val, m.shape).spmm(self.x), m.rowptr[1:] - m.rowptr[:-1]
@@ -130,8 +133,11 @@ def _seed_plus_plus(x, k, gen):
     return centres
 
 
+KMEANS_UPDATES = ("spmm", "sums")
+
+
 @torch.no_grad()
-def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-means++", assign="direct"):
+def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-means++", assign="direct", update="spmm"):
     """Lloyd's k-means of the rows of x ([n, d] float32 CUDA tensor; an ndarray or host tensor is uploaded to the current device) on
     the device; returns a KMeansResult on x's device.
 
@@ -146,7 +152,10 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     cluster; several empty clusters take rows in descending order of distance (a property of this function, not sklearn parity).
     assign: "direct" (K9) or "matrix" (K18: the assignments of the Lloyd loop search the nearest centre on the matrix cores, centred
     on the mean of the centres; at most device.KMEANS_MATRIX_MAX_K clusters).  The seeding stays on the direct kernel: one centre per
-    call leaves a matrix unit nothing to do."""
+    call leaves a matrix unit nothing to do.
+    update: "spmm" (the per-cluster sums as membership matrix x X through the library's SpMM) or "sums" (K19, device.cluster_sums: one
+    pass over x, a two-level sequential float32 sum; at most device.CLUSTER_SUMS_MAX_K clusters).  The two sum in different orders:
+    centres agree to rounding, not bit for bit."""
     if not torch.is_tensor(x):
         x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
     if not x.is_cuda:
@@ -159,6 +168,10 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
         raise ValueError(f"assign must be one of {dev.KMEANS_FORMS}, got {assign!r}")
     if assign == "matrix" and k > dev.KMEANS_MATRIX_MAX_K:
         raise ValueError(f"assign='matrix' takes at most {dev.KMEANS_MATRIX_MAX_K} clusters, got {k}")
+    if update not in KMEANS_UPDATES:
+        raise ValueError(f"update must be one of {KMEANS_UPDATES}, got {update!r}")
+    if update == "sums" and k > dev.CLUSTER_SUMS_MAX_K:
+        raise ValueError(f"update='sums' takes at most {dev.CLUSTER_SUMS_MAX_K} clusters, got {k}")
     if k < 1 or n < k:
         raise ValueError(f"n_samples={n} should be >= n_clusters={k} >= 1")
     if max_iter < 1 or n_init < 1:
@@ -177,10 +190,10 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     else:
         gen.manual_seed(int(seed))
     tol_abs = tol * _mean_variance(x)
-    update = _Update(x, k)
+    step = _Update(x, k, update)
     best = None
     for _ in range(n_init):
-        run = _lloyd(x, given if given is not None else _seed_plus_plus(x, k, gen), update, max_iter, tol_abs, assign)
+        run = _lloyd(x, given if given is not None else _seed_plus_plus(x, k, gen), step, max_iter, tol_abs, assign)
         if best is None or run.inertia < best.inertia:
             best = run
     return best
@@ -255,19 +268,19 @@ NodeClusteringNAFS keeps (best_hop_acc, best_hop_nmi, best_hop_adjscore, acc, nm
 
 @torch.no_grad()
 def nafs_node_clustering(adj, x, y, hops, r_list=(0.5, 0.4, 0.3, 0.2, 0.1, 0), method="mean", n_init=20, seed=42, device="cuda",
-                         strict_order=False, reorder=None, assign="direct"):
+                         strict_order=False, reorder=None, assign="direct", update="spmm"):
     """NodeClusteringNAFS._execute (sgl/tasks/node_clustering.py:171-258): for every hop count of `hops` (an int = range(hops), or a
     list) the NAFS ensemble features, their k-means labels (k = the number of distinct labels in y, n_init runs seeded with `seed`)
     and (acc, nmi, adjscore) against y; then the best-hop bookkeeping of lines 189-197 (strictly greater wins, the bests start at
     0).  One nafs_ensemble_sweep -- one propagation per r for ALL hop counts -- whose consumer clusters and scores each feature matrix
-    as soon as its ensemble is complete; only three floats per hop count outlive it.  assign: kmeans' (the form of the assignment
-    step).  Returns a NodeClusteringResult."""
+    as soon as its ensemble is complete; only three floats per hop count outlive it.  assign, update: kmeans' (the forms of the
+    assignment step and of the centre update).  Returns a NodeClusteringResult."""
     device = torch.device(device)
     y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(-1).to(device)
     k = int(torch.unique(y).numel())
 
     def cluster(hop, feats):
-        return clustering_scores(y, kmeans(feats, k, n_init=n_init, seed=seed, assign=assign).labels)
+        return clustering_scores(y, kmeans(feats, k, n_init=n_init, seed=seed, assign=assign, update=update).labels)
 
     metrics = nafs_ensemble_sweep(adj, x, hops, r_list=r_list, method=method, device=device, strict_order=strict_order, reorder=reorder,
                                   consume=cluster)
@@ -358,18 +371,18 @@ def _model_output(model, nodes, device):
     return model.model_forward(nodes, device) if hasattr(model, "model_forward") else model(nodes)
 
 
-def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda", assign="direct"):
+def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda", assign="direct", update="spmm"):
     """clustering_train of the reference (sgl/tasks/utils.py:116-136), one step: model_forward, k-means of the DETACHED output
     (kmeans above: n_init runs seeded with `seed`, on the device -- the reference copies the output to the host for sklearn),
     cluster_loss on its labels and centres, backward, optimizer.step, and the three scores of the k-means labels against y.
-    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated.  assign: kmeans'."""
+    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated.  assign, update: kmeans'."""
     device = torch.device(device)
     if optimizer is not None:
         model.train()
         optimizer.zero_grad()
     with torch.set_grad_enabled(optimizer is not None):
         out = _model_output(model, train_idx, device)
-        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed, assign=assign)
+        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed, assign=assign, update=update)
         loss = cluster_loss(out, km.labels, km.centres, check=False)
         if optimizer is not None:
             loss.backward()

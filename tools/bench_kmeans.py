@@ -19,8 +19,14 @@ recorded.
 The matrix leg (--matrix-out, default profiles/kmeans_matrix.json; --matrix-only skips the two-way legs above): the
 matrix-core form (form="matrix"), the direct kernel and the torch composition interleaved THREE ways under the same protocol, labels
 of sampled rows checked against float64 first (the bound of include/sgl_kmeans_mfma.h), one Lloyd iteration per form, and
-"matrix_faster": the matrix form's min-max lies wholly below the direct kernel's."""
+"matrix_faster": the matrix form's min-max lies wholly below the direct kernel's.
+
+The sums leg (--sums-out, default profiles/kmeans_sums.json; --sums-only runs nothing else): the centre update alone in
+both forms -- the membership-matrix SpMM (update="spmm") and the one-pass kernel (device.cluster_sums, update="sums") -- and the whole
+iteration, matrix assignment + update, in both forms, the four interleaved under the same protocol.  Both updates are checked against
+float64 sums of sampled clusters first.  "sums_faster": the new update's min-max lies wholly below the SpMM update's."""
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -30,7 +36,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from sgl_amd import device as dev, synthetic  # noqa: E402
+from sgl_amd import _lib, device as dev, synthetic  # noqa: E402
 from sgl_amd.tricks import clustering  # noqa: E402
 
 COPY_CEILING_BYTES_PER_S = 6.29e12
@@ -129,6 +135,54 @@ def matrix_leg(x, c, args):
     return r
 
 
+def sums_leg(x, c, args):
+    """the centre update in both forms, alone and behind the matrix assignment, interleaved in one process"""
+    n, d = x.shape
+    k = c.shape[0]
+    labels, mindist = dev.kmeans_assign(x, c, form="matrix")
+    old, new = clustering._Update(x, k), clustering._Update(x, k, "sums")
+    (s_old, n_old), (s_new, n_new) = old.sums(labels), new.sums(labels)
+    rule = (ctypes.c_int64 * 5)()
+    _lib.check(_lib.lib().sgl_cluster_sums_rule(n, d, k, 1, rule), "sgl_cluster_sums_rule")
+    worst = {"spmm": 0.0, "sums": 0.0}
+    ok = bool(torch.equal(n_old, n_new))
+    for j in torch.randperm(k)[:8].tolist():       # sampled clusters against float64; the bound of include/sgl_cluster_sums.h
+        rows = x[labels == j].double()
+        exact, mass = rows.sum(0), rows.abs().sum(0).clamp_min(1e-300)
+        ok = ok and int(n_new[j]) == rows.shape[0]
+        for name, got in (("spmm", s_old), ("sums", s_new)):
+            worst[name] = max(worst[name], float(((got[j].double() - exact).abs() / mass).max()))
+    bound = (rule[0] + rule[1]) * 2.0 ** -24
+    ok = ok and worst["sums"] <= bound
+    print(f"EXP kmeans-sums d={d}: B={rule[0]} R={rule[1]} slab={rule[2]} S={rule[3]} LDS={rule[4]} B; 8 sampled clusters against float64, error / sum|x|: "
+          f"spmm {worst['spmm']:.2e}, sums {worst['sums']:.2e} (bound {bound:.2e}){'' if ok else '  WRONG'}", flush=True)
+    if not ok:
+        raise SystemExit(f"bench_kmeans.py: the one-pass sums are wrong at d={d}; nothing was timed")
+    del s_old, s_new, rows
+    legs = {"update_spmm": lambda: old(labels, mindist), "update_sums": lambda: new(labels, mindist),
+            "iteration_spmm": lambda: old(*dev.kmeans_assign(x, c, form="matrix")), "iteration_sums": lambda: new(*dev.kmeans_assign(x, c, form="matrix"))}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for _ in range(args.reps):                     # interleaved: every candidate sees the same drift of the machine
+        for name, fn in legs.items():
+            ms[name].append(timed(fn))
+    r = {name + "_ms": stats(v) for name, v in ms.items()}
+    one_read_ms = n * d * 4 / COPY_CEILING_BYTES_PER_S * 1e3
+    r.update(one_read_of_x_ms=one_read_ms, blocks=rule[0], rows_per_block=rule[1], slab=rule[2], slabs=rule[3], lds_bytes=rule[4],
+             error_over_sum_abs=worst, error_bound=bound)
+    for name in ("update_spmm", "update_sums"):
+        r[name + "_over_one_read_of_x"] = r[name + "_ms"]["median"] / one_read_ms
+    r["sums_faster"] = bool(r["update_sums_ms"]["max"] < r["update_spmm_ms"]["min"])
+    r["iteration_faster"] = bool(r["iteration_sums_ms"]["max"] < r["iteration_spmm_ms"]["min"])
+    print(f"EXP kmeans-sums d={d}: " + ", ".join(f"{name} {r[name + '_ms']['median']:.3f} ms ({r[name + '_ms']['min']:.3f}-{r[name + '_ms']['max']:.3f})"
+                                                for name in legs) + f"; update_sums = {r['update_sums_over_one_read_of_x']:.2f} x one read of X "
+          f"({one_read_ms:.3f} ms), {'wholly below' if r['sums_faster'] else 'NOT wholly below'} the SpMM update", flush=True)
+    return r
+
+
 def one_width(x, c, args):
     n, d = x.shape
     k = c.shape[0]
@@ -186,6 +240,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kmeans.json"))
     ap.add_argument("--matrix-out", default=os.path.join(ROOT, "profiles", "kmeans_matrix.json"))
     ap.add_argument("--matrix-only", action="store_true")
+    ap.add_argument("--sums-out", default=os.path.join(ROOT, "profiles", "kmeans_sums.json"))
+    ap.add_argument("--sums-only", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_kmeans.py needs a GPU (nothing here is measured without one)")
@@ -200,26 +256,36 @@ def main():
     failed = []
     matrix = {key: result[key] for key in ("n_rows", "k", "reps", "warmup", "device", "copy_ceiling_bytes_per_s")}
     matrix["shapes"] = {}
+    sums = dict(matrix, shapes={})
     for d in [int(v) for v in args.dims.split(",")]:
         c = torch.randn((args.k, d), generator=g, device=device, dtype=torch.float32)
         x = torch.randn((args.n, d), generator=g, device=device, dtype=torch.float32)
         x += c[torch.randint(0, args.k, (args.n,), generator=g, device=device)]
         c = x[torch.randint(0, args.n, (args.k,), generator=g, device=device)].clone()       # a seeding, not the optimum
-        matrix["shapes"][f"d{d}"] = {"d": d, **matrix_leg(x, c, args)}
         if not args.matrix_only:
+            sums["shapes"][f"d{d}"] = {"d": d, **sums_leg(x, c, args)}
+        if not args.sums_only:
+            matrix["shapes"][f"d{d}"] = {"d": d, **matrix_leg(x, c, args)}
+        if not (args.matrix_only or args.sums_only):
             r = one_width(x, c, args)
             result["shapes"][f"d{d}"] = {"d": d, **r}
             failed += [f"d{d}_{what}" for what in ("assign", "iteration") if not r[what]["accepted"]]
         del x, c
         torch.cuda.empty_cache()
     result["not_accepted"] = failed
-    if args.matrix_out:
+    if args.sums_out and not args.matrix_only:
+        os.makedirs(os.path.dirname(os.path.abspath(args.sums_out)), exist_ok=True)
+        with open(args.sums_out, "w") as f:
+            json.dump(sums, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"EXP kmeans wrote {args.sums_out}", flush=True)
+    if args.matrix_out and not args.sums_only:
         os.makedirs(os.path.dirname(os.path.abspath(args.matrix_out)), exist_ok=True)
         with open(args.matrix_out, "w") as f:
             json.dump(matrix, f, indent=1, sort_keys=True)
             f.write("\n")
         print(f"EXP kmeans wrote {args.matrix_out}", flush=True)
-    if args.out and not args.matrix_only:
+    if args.out and not (args.matrix_only or args.sums_only):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1, sort_keys=True)
