@@ -47,13 +47,14 @@ def main():
     ap.add_argument("--classes", type=int, default=5)
     ap.add_argument("--method", default="mean", choices=("mean", "max", "concat", "simple"))
     ap.add_argument("--n-init", type=int, default=5)
+    ap.add_argument("--init", default="k-means++", choices=("k-means++", "greedy-k-means++"), help="the k-means seeding: plain, or K20's greedy step kernel (sklearn's)")
     ap.add_argument("--assign", default="direct", choices=("direct", "matrix"), help="the k-means assignment: K9, or K18 on the matrix cores")
     ap.add_argument("--update", default="spmm", choices=("spmm", "sums"), help="the k-means centre update: membership-matrix SpMM, or K19's one-pass sums")
     a = ap.parse_args()
     adj, x, y = planted_partition(a.nodes, a.classes, 10, 0.8, 32, seed=0)
     t0 = time.time()
     res = nafs_node_clustering(adj, x, y, a.hops, r_list=(0.5, 0.3, 0), method=a.method, n_init=a.n_init, seed=42, assign=a.assign,
-                               update=a.update)
+                               update=a.update, init=a.init)
     took = time.time() - t0
     print(f"{a.nodes} nodes, {adj.nnz} edges, {a.classes} blocks, method {a.method}, n_init {a.n_init}: {took:.2f} s")
     print("hops    acc     nmi     adjscore")

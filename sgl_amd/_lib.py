@@ -200,6 +200,14 @@ CLUSTER_SUMS_PROTOTYPES = {
     "sgl_cluster_sums_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sgl_kmeans_seed.h: K20, greedy k-means++ seeding on the device -- a header and a table of their own too
+SGL_KMEANS_SEED_MAX_TRIALS = 8
+KMEANS_SEED_PROTOTYPES = {
+    "sgl_kmeans_seed_rule": (c_int, [c_int64, c_int64, c_int, POINTER(c_int64)]),
+    "sgl_kmeans_seed_scratch": (c_int64, [c_int64, c_int]),
+    "sgl_kmeans_seed_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -230,7 +238,7 @@ def lib():
                 "sgl_amd has no CPU fallback for the propagation hot path.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items(),
-                                  *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items()):
+                                  *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items(), *KMEANS_SEED_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -1,6 +1,7 @@
 // Device helpers shared by the kernels that hold rows of X in registers against centres staged in LDS: sgl_kmeans.hip (K9, the
 // assignment step) and sgl_cluster_loss.hip (K12, the clustering loss and its gradient).  A lane's sum of squared differences in the
-// DIRECT form (Sq), and the staging of a tile of NEGATED centres (stage_centres, restage_centres);
+// DIRECT form (Sq), the staging of a tile of NEGATED centres (stage_centres, restage_centres), and the transposing lane sum of K9's
+// distances (reduce_slots), which sgl_kmeans_seed.hip (K20) repeats bit for bit;
 // the lane sums (group_sum), the row loads that never read beyond column d of a last row (edge_load) and the column
 // helpers (vzero, store_cols, load_cols) are sgl_rows.h's.  Not part of the ABI.
 #pragma once
@@ -81,6 +82,42 @@ __device__ __forceinline__ void restage_centres(bool &staged, float *__restrict_
         __syncthreads();
         staged = true;
     }
+}
+
+// ---- transposing reduction ------------------------------------------------------------------------------------------------------------
+// group_sum per (row, centre) costs 6 - 8 VALU instructions at LPR = 32 / 64 and leaves every lane with the same total: more than the
+// 4 packed instructions a lane spends on a vector of the distance itself (measured: 13 x one read of X at d = 100).  So a lane group
+// takes T centres at a time (T = 4 at LPR = 64, 2 at LPR = 32) and the steps that cross the 16-lane rows TRANSPOSE: v_permlane32_swap /
+// v_permlane16_swap exchange one half of the T partial sums for the other, after which each row of 16 lanes holds the sums of ONE of
+// the T centres (slot_of_lane) and finishes them with the DPP steps of group_sum<16>.  T - 1 swaps and adds plus 4 DPP adds for T
+// centres, and the running minimum is compared once per T centres per lane; the rows' minima are merged once per row of X
+// (merge_rows).  Every partial sum goes through the same (low half + high half, even row + odd row) additions whatever its slot, so
+// the bits of a distance do not depend on where its centre stands.
+template <int LPR>
+constexpr int kSlots = LPR == 64 ? 4 : (LPR == 32 ? 2 : 1);
+
+template <int LPR>
+__device__ __forceinline__ int slot_of_lane() {      // the slot whose total reduce_slots leaves in this lane
+    const int row = (threadIdx.x % 64) / 16;
+    if constexpr (LPR == 64) return ((row & 1) << 1) | (row >> 1);
+    if constexpr (LPR == 32) return row & 1;
+    return 0;
+}
+
+__device__ __forceinline__ float swap_add32(const float a, const float b) {   // lanes 0-31: a + a[lane ^ 32], lanes 32-63: b + b[lane ^ 32]
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ float swap_add16(const float a, const float b) {   // even rows: a + a[lane ^ 16], odd rows: b + b[lane ^ 16]
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+template <int LPR>
+__device__ __forceinline__ float reduce_slots(const float (&p)[kSlots<LPR>]) {
+    if constexpr (LPR == 64) return group_sum<16>(swap_add16(swap_add32(p[0], p[1]), swap_add32(p[2], p[3])));
+    else if constexpr (LPR == 32) return group_sum<16>(swap_add16(p[0], p[1]));
+    else return group_sum<LPR>(p[0]);
 }
 
 }  // namespace

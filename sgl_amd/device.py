@@ -51,7 +51,7 @@ def _esize(dtype):
 # entry points whose last argument is not a stream
 _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
                         "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule",
-                        "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch"})
+                        "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch", "sgl_kmeans_seed_rule", "sgl_kmeans_seed_scratch"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2151,6 +2151,41 @@ def cluster_sums(x, labels, k, check=True):
     scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     _call(x.device, "sgl_cluster_sums_f32", ptr(x), _ld(x), n, d, ptr(labels), k, ptr(sums), max(d, 1), ptr(counts), ptr(scratch))
     return sums, counts
+
+
+KMEANS_SEED_MAX_TRIALS = _lib.SGL_KMEANS_SEED_MAX_TRIALS    # the candidates per step that sgl_kmeans_seed.hip keeps in LDS
+
+
+def kmeans_seed(x, k, draws, trials):
+    """(centre_ids, near, pot) of a greedy k-means++ seeding (sgl_kmeans_seed_f32, include/sgl_kmeans_seed.h): centre_ids int64 [k], the
+    rows of x chosen as centres; near float32 [n], the squared distance of every row to the nearest of them (the direct form, the bits
+    of kmeans_assign's 16-byte-lane form); pot float64 [k], the sum of near after every step.  Every step after the first tries
+    `trials` candidate rows, drawn with probability proportional to near, in ONE read of x and keeps the one that lowers the sum most
+    (the lowest on a tie); trials=1 is plain k-means++.  x: [n, d] float32 CUDA matrix, read in place (padded buffers, column views);
+    draws: float64 [k, trials] on x's device, uniform in [0, 1): row 0 gives the first centre, row j the candidates of step j.
+    2 k launches, no host read, no atomics: two runs are bit-equal, and the bits do not depend on x's pitch or alignment.  A row that
+    holds NaN keeps a NaN in near and is never drawn.  1 <= trials <= KMEANS_SEED_MAX_TRIALS.  The scratch is a tensor of this call
+    (torch's caching allocator)."""
+    _no_bf16("kmeans_seed", x)
+    _check_mat(x, "x")
+    k, trials = int(k), int(trials)
+    n, d = x.shape
+    if not 1 <= trials <= KMEANS_SEED_MAX_TRIALS:
+        raise ValueError(f"kmeans_seed: trials must be in [1, {KMEANS_SEED_MAX_TRIALS}], got {trials}")
+    if k < 1 or n < k:
+        raise ValueError(f"kmeans_seed: n_samples={n} should be >= k={k} >= 1")
+    if not (torch.is_tensor(draws) and draws.device == x.device and draws.dtype == torch.float64 and draws.shape == (k, trials)
+            and draws.is_contiguous()):
+        raise ValueError(f"kmeans_seed: `draws` must be a contiguous float64 [{k}, {trials}] tensor on x's device")
+    centre_ids = torch.empty(k, dtype=torch.int64, device=x.device)
+    near = torch.empty(n, dtype=torch.float32, device=x.device)
+    pot = torch.empty(k, dtype=torch.float64, device=x.device)
+    nbytes = int(_call(None, "sgl_kmeans_seed_scratch", n, trials, raw=True))
+    if nbytes < 0:
+        raise _lib.SglHipError(f"sgl_kmeans_seed_scratch failed: {_lib.last_error()}")
+    scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    _call(x.device, "sgl_kmeans_seed_f32", ptr(x), _ld(x), n, d, k, trials, ptr(draws), ptr(centre_ids), ptr(near), ptr(pot), ptr(scratch))
+    return centre_ids, near, pot
 
 
 def cluster_loss_grad(x, centres, labels, w, dx=None, row_loss=None):

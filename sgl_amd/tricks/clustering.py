@@ -16,9 +16,11 @@ on CPU cores, after copying [N, d] to the host.  Here the features stay where na
     arithmetic on the table.
 
 What is and is not sklearn parity: the Lloyd loop follows sklearn's stopping rule exactly, so from the SAME initial centres it ends
-with the same labels after the same number of iterations wherever no row sits on a tie.  The seeding is plain k-means++ (one
-candidate per step) from a torch.Generator -- sklearn's greedy variant tries 2 + ln k candidates per step and draws from numpy --
-so with a seed alone the two agree only on inputs with a single optimum.
+with the same labels after the same number of iterations wherever no row sits on a tie.  The default seeding is plain k-means++ (one
+candidate per step); init="greedy-k-means++" is sklearn's greedy variant, 2 + floor(ln k) candidates per step of which the one that
+lowers the potential most is kept, on a kernel of its own (device.kmeans_seed -> sgl_kmeans_seed_f32: the candidates of a step in
+LDS, one read of the features per step).  Either draws from a torch.Generator where sklearn draws from numpy, so with a seed alone
+the two agree only on inputs with a single optimum.
 
 The TRAINABLE task, NodeClustering (sgl/tasks/node_clustering.py:12-119), trains a model on cluster_loss (sgl/tasks/utils.py:101-113)
 with a k-means of the model output in every step (clustering_train, 116-136).  Here the output never leaves the device: kmeans above,
@@ -133,11 +135,29 @@ def _seed_plus_plus(x, k, gen):
     return centres
 
 
+KMEANS_INITS = ("k-means++", "greedy-k-means++")
+
+
+def _local_trials(k, n_local_trials):
+    """the candidates per step of the greedy seeding: sklearn's 2 + floor(ln k) for None"""
+    trials = 2 + int(np.log(k)) if n_local_trials is None else int(n_local_trials)
+    if not 1 <= trials <= dev.KMEANS_SEED_MAX_TRIALS:
+        raise ValueError(f"n_local_trials must be in [1, {dev.KMEANS_SEED_MAX_TRIALS}], got {trials}")
+    return trials
+
+
+def _seed_greedy(x, k, gen, trials):
+    """greedy k-means++ (K20): one [k, trials] float64 table of draws per run, uploaded once; 2 k launches and one gather"""
+    draws = torch.rand((k, trials), generator=gen, dtype=torch.float64).to(x.device)
+    return x[dev.kmeans_seed(x, k, draws, trials)[0]]
+
+
 KMEANS_UPDATES = ("spmm", "sums")
 
 
 @torch.no_grad()
-def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-means++", assign="direct", update="spmm"):
+def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-means++", assign="direct", update="spmm",
+           n_local_trials=None):
     """Lloyd's k-means of the rows of x ([n, d] float32 CUDA tensor; an ndarray or host tensor is uploaded to the current device) on
     the device; returns a KMeansResult on x's device.
 
@@ -145,9 +165,12 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     else when the summed squared centre shift is at most tol * mean over the columns of var(x) (float64, taken once); after a stop by
     shift one more assignment; n_iter counts as n_iter_ does; inertia is the float64 sum of the float32 squared distances.  Of n_init
     runs the lowest inertia wins, the earliest run on a tie.
-    init: "k-means++", or a [k, d] tensor / array of initial centres, which forces one run.  The seeding is PLAIN k-means++, one
-    candidate per step (sklearn's greedy variant tries 2 + ln k candidates per step), with draws from a torch.Generator seeded with
-    `seed` (None: a fresh random seed): same seed, same device, same input give a bit-equal result -- nothing here uses atomics.
+    init: "k-means++" (the default), "greedy-k-means++", or a [k, d] tensor / array of initial centres, which forces one run.
+    "k-means++" is PLAIN k-means++, one candidate per step, in torch.  "greedy-k-means++" (K20, device.kmeans_seed) is sklearn's
+    seeding: n_local_trials candidates per step (None: 2 + floor(ln k); at most device.KMEANS_SEED_MAX_TRIALS; 1 is plain k-means++
+    on the kernel), all tried in one read of x, and the one that lowers the potential most is kept.  Both draw from a torch.Generator
+    seeded with `seed` (None: a fresh random seed), not from numpy's stream as sklearn does: same seed, same device, same input give
+    a bit-equal result -- nothing here uses atomics -- but the two inits consume the draws differently and give different centres.
     An empty cluster takes the row with the largest distance to its centre (the lowest index on ties), which leaves its former
     cluster; several empty clusters take rows in descending order of distance (a property of this function, not sklearn parity).
     assign: "direct" (K9) or "matrix" (K18: the assignments of the Lloyd loop search the nearest centre on the matrix cores, centred
@@ -182,8 +205,9 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
         if given.shape != (k, d):
             raise ValueError(f"init must be [{k}, {d}]")
         n_init = 1
-    elif init != "k-means++":
-        raise ValueError("init must be 'k-means++' or a [k, d] matrix of centres")
+    elif init not in KMEANS_INITS:
+        raise ValueError(f"init must be one of {KMEANS_INITS} or a [k, d] matrix of centres")
+    trials = _local_trials(k, n_local_trials) if given is None and init == "greedy-k-means++" else None
     gen = torch.Generator()
     if seed is None:
         gen.seed()
@@ -193,7 +217,8 @@ def kmeans(x, n_clusters, n_init=20, max_iter=300, tol=1e-4, seed=None, init="k-
     step = _Update(x, k, update)
     best = None
     for _ in range(n_init):
-        run = _lloyd(x, given if given is not None else _seed_plus_plus(x, k, gen), step, max_iter, tol_abs, assign)
+        start = given if given is not None else (_seed_greedy(x, k, gen, trials) if trials else _seed_plus_plus(x, k, gen))
+        run = _lloyd(x, start, step, max_iter, tol_abs, assign)
         if best is None or run.inertia < best.inertia:
             best = run
     return best
@@ -268,19 +293,19 @@ NodeClusteringNAFS keeps (best_hop_acc, best_hop_nmi, best_hop_adjscore, acc, nm
 
 @torch.no_grad()
 def nafs_node_clustering(adj, x, y, hops, r_list=(0.5, 0.4, 0.3, 0.2, 0.1, 0), method="mean", n_init=20, seed=42, device="cuda",
-                         strict_order=False, reorder=None, assign="direct", update="spmm"):
+                         strict_order=False, reorder=None, assign="direct", update="spmm", init="k-means++"):
     """NodeClusteringNAFS._execute (sgl/tasks/node_clustering.py:171-258): for every hop count of `hops` (an int = range(hops), or a
     list) the NAFS ensemble features, their k-means labels (k = the number of distinct labels in y, n_init runs seeded with `seed`)
     and (acc, nmi, adjscore) against y; then the best-hop bookkeeping of lines 189-197 (strictly greater wins, the bests start at
     0).  One nafs_ensemble_sweep -- one propagation per r for ALL hop counts -- whose consumer clusters and scores each feature matrix
-    as soon as its ensemble is complete; only three floats per hop count outlive it.  assign, update: kmeans' (the forms of the
-    assignment step and of the centre update).  Returns a NodeClusteringResult."""
+    as soon as its ensemble is complete; only three floats per hop count outlive it.  assign, update, init: kmeans' (the forms of the
+    assignment step and of the centre update, the seeding).  Returns a NodeClusteringResult."""
     device = torch.device(device)
     y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(-1).to(device)
     k = int(torch.unique(y).numel())
 
     def cluster(hop, feats):
-        return clustering_scores(y, kmeans(feats, k, n_init=n_init, seed=seed, assign=assign, update=update).labels)
+        return clustering_scores(y, kmeans(feats, k, n_init=n_init, seed=seed, assign=assign, update=update, init=init).labels)
 
     metrics = nafs_ensemble_sweep(adj, x, hops, r_list=r_list, method=method, device=device, strict_order=strict_order, reorder=reorder,
                                   consume=cluster)
@@ -371,18 +396,19 @@ def _model_output(model, nodes, device):
     return model.model_forward(nodes, device) if hasattr(model, "model_forward") else model(nodes)
 
 
-def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda", assign="direct", update="spmm"):
+def clustering_train(model, train_idx, y, optimizer, n_clusters, n_init=20, seed=None, device="cuda", assign="direct", update="spmm",
+                     init="k-means++"):
     """clustering_train of the reference (sgl/tasks/utils.py:116-136), one step: model_forward, k-means of the DETACHED output
     (kmeans above: n_init runs seeded with `seed`, on the device -- the reference copies the output to the host for sklearn),
     cluster_loss on its labels and centres, backward, optimizer.step, and the three scores of the k-means labels against y.
-    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated.  assign, update: kmeans'."""
+    Returns (loss, acc, nmi, adjscore).  optimizer=None: the loss and scores alone, nothing is updated.  assign, update, init: kmeans'."""
     device = torch.device(device)
     if optimizer is not None:
         model.train()
         optimizer.zero_grad()
     with torch.set_grad_enabled(optimizer is not None):
         out = _model_output(model, train_idx, device)
-        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed, assign=assign, update=update)
+        km = kmeans(out.detach(), n_clusters, n_init=n_init, seed=seed, assign=assign, update=update, init=init)
         loss = cluster_loss(out, km.labels, km.centres, check=False)
         if optimizer is not None:
             loss.backward()

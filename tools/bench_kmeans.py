@@ -9,7 +9,7 @@ Both candidates run INTERLEAVED in one process (warm-up, then --reps repetitions
 of one call of each is recorded as well.  Before anything is timed, the labels of sampled rows are compared with a float64 argmin; a
 mismatch ends the run with a non-zero exit status.
 
-    python tools/bench_kmeans.py [--reps 20] [--warmup 3] [--n 2449029] [--k 47] [--out profiles/kmeans.json]
+    python tools/bench_kmeans.py [--reps 20] [--warmup 3] [--n 2449029] [--k 47] [--out profiles/kmeans.json] [--seed-only]
 
 Per width the JSON holds: ms of both candidates (median, min, max) for the assignment and for the iteration, their ratios, the
 assignment as a multiple of ONE read of X at the measured copy ceiling (6.29 TB/s), and the peak allocation of both.
@@ -24,7 +24,15 @@ of sampled rows checked against float64 first (the bound of include/sgl_kmeans_m
 The sums leg (--sums-out, default profiles/kmeans_sums.json; --sums-only runs nothing else): the centre update alone in
 both forms -- the membership-matrix SpMM (update="spmm") and the one-pass kernel (device.cluster_sums, update="sums") -- and the whole
 iteration, matrix assignment + update, in both forms, the four interleaved under the same protocol.  Both updates are checked against
-float64 sums of sampled clusters first.  "sums_faster": the new update's min-max lies wholly below the SpMM update's."""
+float64 sums of sampled clusters first.  "sums_faster": the new update's min-max lies wholly below the SpMM update's.
+
+The seeding leg (--seed-out, default profiles/kmeans_seed.json; --seed-only runs nothing else): one whole seeding of k
+centres by the torch k-means++ of tricks/clustering.py (_seed_plus_plus), by the step kernel with one candidate per step
+(device.kmeans_seed, trials=1) and with five, interleaved under the same protocol, draws uploaded inside the timed call as kmeans
+does.  First the kernel's `near` must equal, bit for bit, the assignment kernel's minimum over the centres it chose, and its last
+potential their float64 sum.  Then one kmeans call of --seed-n-init runs under each init, Lloyd loop capped at --seed-max-iter
+iterations (matrix assignment, one-pass sums), timed once with a host clock.  "trials1_below_torch": the min-max of trials=1 lies
+wholly below the torch seeding's; "trials5_not_above_torch": the median of trials=5 is not above the torch seeding's."""
 import argparse
 import ctypes
 import json
@@ -183,6 +191,59 @@ def sums_leg(x, c, args):
     return r
 
 
+def seed_leg(x, args):
+    """one whole seeding: the torch k-means++, the step kernel with 1 and with 5 candidates per step; a kmeans call under each init"""
+    import time
+    n, d = x.shape
+    k = args.k
+    rule = (ctypes.c_int64 * 5)()
+    _lib.check(_lib.lib().sgl_kmeans_seed_rule(n, d, 5, rule), "sgl_kmeans_seed_rule")
+    gen = torch.Generator().manual_seed(args.seed)
+    same = {}
+    for trials in (1, 5):                          # values first: near against the assignment kernel over the chosen centres
+        ids, near, pot = dev.kmeans_seed(x, k, torch.rand((k, trials), generator=gen, dtype=torch.float64).to(x.device), trials)
+        want = dev.kmeans_assign(x, x[ids])[1]
+        total = float(want.sum(dtype=torch.float64))
+        ok = bool(torch.equal(near.view(torch.int32), want.view(torch.int32))) and abs(float(pot[-1]) - total) <= 1e-9 * total
+        same[trials] = int(torch.unique(ids).numel())
+        print(f"EXP kmeans-seed d={d} trials={trials}: {same[trials]} distinct centres of {k}, near {'equals' if ok else 'DIFFERS FROM'} the "
+              f"assignment kernel's minimum, last potential {float(pot[-1]):.6e} against {total:.6e}{'' if ok else '  WRONG'}", flush=True)
+        if not ok:
+            raise SystemExit(f"bench_kmeans.py: the seeding kernel's distances are wrong at d={d}; nothing was timed")
+    del ids, near, pot, want
+    legs = {"torch": lambda: clustering._seed_plus_plus(x, k, gen), "trials1": lambda: clustering._seed_greedy(x, k, gen, 1),
+            "trials5": lambda: clustering._seed_greedy(x, k, gen, 5)}
+    for _ in range(args.warmup):
+        for fn in legs.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in legs}
+    for _ in range(args.reps):                     # interleaved: every candidate sees the same drift of the machine
+        for name, fn in legs.items():
+            ms[name].append(timed(fn))
+    r = {name + "_ms": stats(v) for name, v in ms.items()}
+    one_read_ms = n * d * 4 / COPY_CEILING_BYTES_PER_S * 1e3
+    r.update(one_read_of_x_ms=one_read_ms, steps=k, blocks=rule[0], rows_per_block=rule[1], lds_bytes_trials5=rule[4], distinct_centres=same)
+    for name in legs:
+        r[name + "_step_over_one_read_of_x"] = r[name + "_ms"]["median"] / k / one_read_ms
+    r["trials1_below_torch"] = bool(r["trials1_ms"]["max"] < r["torch_ms"]["min"])
+    r["trials5_not_above_torch"] = bool(r["trials5_ms"]["median"] <= r["torch_ms"]["median"])
+    print(f"EXP kmeans-seed d={d}: " + ", ".join(f"{name} {r[name + '_ms']['median']:.3f} ms ({r[name + '_ms']['min']:.3f}-{r[name + '_ms']['max']:.3f}), "
+                                                f"{r[name + '_step_over_one_read_of_x']:.2f} x one read of X per step" for name in legs)
+          + f" (one read {one_read_ms:.3f} ms); trials=1 {'wholly below' if r['trials1_below_torch'] else 'NOT wholly below'} the torch seeding, trials=5 "
+          f"{'not above' if r['trials5_not_above_torch'] else 'ABOVE'} it", flush=True)
+    r["kmeans_call"] = {"n_init": args.seed_n_init, "max_iter": args.seed_max_iter, "assign": "matrix", "update": "sums", "timed": "once, host clock"}
+    for init in clustering.KMEANS_INITS:           # what a user calls; the Lloyd loop is the same code under both
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run = clustering.kmeans(x, k, n_init=args.seed_n_init, max_iter=args.seed_max_iter, seed=args.seed, init=init, assign="matrix", update="sums")
+        torch.cuda.synchronize()
+        r["kmeans_call"][init] = {"seconds": time.perf_counter() - t0, "inertia": run.inertia, "n_iter": run.n_iter}
+        print(f"EXP kmeans-seed d={d}: kmeans(n_init={args.seed_n_init}, max_iter={args.seed_max_iter}, init={init!r}): "
+              f"{r['kmeans_call'][init]['seconds']:.2f} s, inertia {run.inertia:.6e}", flush=True)
+    return r
+
+
 def one_width(x, c, args):
     n, d = x.shape
     k = c.shape[0]
@@ -242,6 +303,10 @@ def main():
     ap.add_argument("--matrix-only", action="store_true")
     ap.add_argument("--sums-out", default=os.path.join(ROOT, "profiles", "kmeans_sums.json"))
     ap.add_argument("--sums-only", action="store_true")
+    ap.add_argument("--seed-out", default=os.path.join(ROOT, "profiles", "kmeans_seed.json"))
+    ap.add_argument("--seed-only", action="store_true")
+    ap.add_argument("--seed-n-init", type=int, default=20)
+    ap.add_argument("--seed-max-iter", type=int, default=20)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_kmeans.py needs a GPU (nothing here is measured without one)")
@@ -257,35 +322,44 @@ def main():
     matrix = {key: result[key] for key in ("n_rows", "k", "reps", "warmup", "device", "copy_ceiling_bytes_per_s")}
     matrix["shapes"] = {}
     sums = dict(matrix, shapes={})
+    seeding = dict(matrix, shapes={})
     for d in [int(v) for v in args.dims.split(",")]:
         c = torch.randn((args.k, d), generator=g, device=device, dtype=torch.float32)
         x = torch.randn((args.n, d), generator=g, device=device, dtype=torch.float32)
         x += c[torch.randint(0, args.k, (args.n,), generator=g, device=device)]
         c = x[torch.randint(0, args.n, (args.k,), generator=g, device=device)].clone()       # a seeding, not the optimum
-        if not args.matrix_only:
-            sums["shapes"][f"d{d}"] = {"d": d, **sums_leg(x, c, args)}
-        if not args.sums_only:
-            matrix["shapes"][f"d{d}"] = {"d": d, **matrix_leg(x, c, args)}
         if not (args.matrix_only or args.sums_only):
+            seeding["shapes"][f"d{d}"] = {"d": d, **seed_leg(x, args)}
+        if not (args.matrix_only or args.seed_only):
+            sums["shapes"][f"d{d}"] = {"d": d, **sums_leg(x, c, args)}
+        if not (args.sums_only or args.seed_only):
+            matrix["shapes"][f"d{d}"] = {"d": d, **matrix_leg(x, c, args)}
+        if not (args.matrix_only or args.sums_only or args.seed_only):
             r = one_width(x, c, args)
             result["shapes"][f"d{d}"] = {"d": d, **r}
             failed += [f"d{d}_{what}" for what in ("assign", "iteration") if not r[what]["accepted"]]
         del x, c
         torch.cuda.empty_cache()
     result["not_accepted"] = failed
-    if args.sums_out and not args.matrix_only:
+    if args.seed_out and not (args.matrix_only or args.sums_only):
+        os.makedirs(os.path.dirname(os.path.abspath(args.seed_out)), exist_ok=True)
+        with open(args.seed_out, "w") as f:
+            json.dump(seeding, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"EXP kmeans wrote {args.seed_out}", flush=True)
+    if args.sums_out and not (args.matrix_only or args.seed_only):
         os.makedirs(os.path.dirname(os.path.abspath(args.sums_out)), exist_ok=True)
         with open(args.sums_out, "w") as f:
             json.dump(sums, f, indent=1, sort_keys=True)
             f.write("\n")
         print(f"EXP kmeans wrote {args.sums_out}", flush=True)
-    if args.matrix_out and not args.sums_only:
+    if args.matrix_out and not (args.sums_only or args.seed_only):
         os.makedirs(os.path.dirname(os.path.abspath(args.matrix_out)), exist_ok=True)
         with open(args.matrix_out, "w") as f:
             json.dump(matrix, f, indent=1, sort_keys=True)
             f.write("\n")
         print(f"EXP kmeans wrote {args.matrix_out}", flush=True)
-    if args.out and not (args.matrix_only or args.sums_only):
+    if args.out and not (args.matrix_only or args.sums_only or args.seed_only):
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
             json.dump(result, f, indent=1, sort_keys=True)
