@@ -208,6 +208,18 @@ KMEANS_SEED_PROTOTYPES = {
     "sgl_kmeans_seed_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# include/sgl_linear_head.h: K21, the linear classification head fused with its loss -- a header and a table of their own too
+SGL_LINEAR_HEAD_MAX_C = 256
+LINEAR_HEAD_PROTOTYPES = {
+    "sgl_linear_class_rule": (c_int, [c_int64, c_int64, POINTER(c_int)]),
+    "sgl_linear_class_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_float, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "sgl_linear_wgrad_rule": (c_int, [c_int64, c_int64, c_int64, POINTER(c_int64)]),
+    "sgl_linear_wgrad_scratch": (c_int64, [c_int64, c_int64, c_int64]),
+    "sgl_linear_wgrad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                     c_void_p]),
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -238,7 +250,8 @@ def lib():
                 "sgl_amd has no CPU fallback for the propagation hot path.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items(),
-                                  *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items(), *KMEANS_SEED_PROTOTYPES.items()):
+                                  *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items(), *KMEANS_SEED_PROTOTYPES.items(),
+                                  *LINEAR_HEAD_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -1,0 +1,469 @@
+// K21: a linear classification head fused with its loss (include/sgl_linear_head.h states the contract and the bounds).  The unfused
+// step writes the logits Z = X W^T + b [n, C], reads them again for the loss (K14) and runs two rocBLAS products in the backward; the
+// head's GEMM is skinny (C <= 256) and memory-bound, which is the shape K18 (sgl_kmeans_mfma.hip) serves on v_mfma_f32_32x32x2_f32.
+//
+// linear_class_kernel.  K18's work split: Z^T[j][i] = sum_col W[j][col] x[i][col], the rows of W are the A operand (staged in LDS, row
+// pitch W + 4 floats so that the 16-byte reads of 16 consecutive classes fall into 16 different bank groups; column chunks with carried
+// accumulators when C (d + 4) floats exceed the tile), rows of X the B operand straight from memory: lane (i = lane % 32, h = lane / 32)
+// takes the float4 at columns 8 q + 4 h of ITS row, element e of it is one MFMA step -- no transpose, and the chain of a logit is the
+// same whatever the chunk width (a multiple of 8).  256 threads; a wavefront owns R tiles of 32 rows (R = 2 up to 4 class tiles, else
+// 1) and keeps NT = ceil(C / 32) accumulator tiles per row tile (sgl::KmeansMatrixTiles).  Workgroups stride over batches of 4 R x 32
+// rows (sgl::loss_batch_grid, K9's cap).
+//
+// The epilogue works in the accumulator layout: lane (i, h) holds the 16 NT logits 32 t + 8 g + 4 h + e (g, e = 0 .. 3) of row i, its
+// partner lane i + 32 (v_permlane32_swap) the other 16 NT.  The bias is added from LDS; the maximum, the first NaN, the first column of
+// the maximum (K14's Best, ascending in a lane), the sum of the exponentials and the logit of the label are in-lane loops followed by
+// ONE exchange each; slots >= C are left out by a select on the slot.  A lane's logits are runs of 4 consecutive classes: z and dz are
+// written as 16-byte stores where the output's base and pitch allow.
+//
+// linear_wgrad_kernel + linear_fold_kernel.  dW^T is not formed: D[j][col] = sum_i dz[i][j] x[i][col] with dz^T the A operand and X the
+// B operand, the MFMA's k index the two rows of a pair -- lane (i, h) reads dz[row 2 s + h][32 t + i] and x[row 2 s + h][32 u + i], both
+// 4-byte reads that a half-wave coalesces into one 128-byte piece of a row; edges are zeros by select, column d of X reads as 1 (db).
+// K19's two levels: B row blocks x S slabs (blockIdx.x = b S + s: the workgroups that share rows are neighbours), 8 tiles of 32 x 32
+// per wavefront resident for the life of the block, the four wavefronts added in LDS in a fixed order, one table per workgroup, a fold
+// in ascending block order.
+#include <climits>
+#include <cmath>
+
+#include "sgl_rows.h"   // f4, edge_load, store_cols, with_vec, with_chunks, SGL_LAUNCH_CHECK
+
+#include "../../include/sgl_linear_head.h"
+
+namespace {
+
+using f16v = float __attribute__((ext_vector_type(16)));
+
+constexpr int kMaxBlocks = 2048;                     // K9's cap: 256 CUs x 8 resident workgroups, the batches beyond are strided over
+constexpr int kTileFloats = 16384;                   // LDS of a workgroup of linear_class_kernel: 64 KiB
+constexpr int kPitchPad = 4;                         // floats: makes pitch / 4 odd
+constexpr int kStep = 32;                            // columns of X a lane pair takes per step: 4 vectors in each half
+constexpr int kNoIndex = INT32_MAX;                  // "no candidate" of the index minimum
+
+constexpr int row_tiles(int nt) { return nt <= 4 ? 2 : 1; }   // R: 2 x NT x 16 accumulator registers stay within 128
+
+struct ClassRule {
+    int nt, r, w, p;     // class tiles, row tiles per wavefront, columns staged at once, LDS pitch
+};
+bool class_rule(int64_t d, int64_t c, ClassRule &out) {
+    const sgl::ChunkList tiles = sgl::KmeansMatrixTiles::list();
+    const int64_t need = (c + 31) / 32;
+    int nt = 0;
+    for (int t = tiles.count - 1; t >= 0; --t)
+        if (tiles.values[t] >= need) nt = tiles.values[t];
+    if (!nt) return false;
+    const int64_t dp = (d + 7) / 8 * 8, budget = kTileFloats - nt * 32;
+    int64_t w = dp;
+    if (c * (dp + kPitchPad) > budget) w = (budget / c - kPitchPad) / 8 * 8;   // >= 48 at c = 256
+    out = {nt, row_tiles(nt), (int)w, (int)w + kPitchPad};
+    return true;
+}
+
+// columns col .. col + 3 of a row, zeros from column d on; col < d.  VEC = 1: the four elements one by one
+template <int VEC>
+__device__ __forceinline__ f4 load4(const float *__restrict__ p, const int col, const int d, const bool last_row) {
+    if constexpr (VEC == 4) {
+        return edge_load<4>(p, col, d, last_row);
+    } else {
+        f4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? p[col + e] : 0.f;
+        return v;
+    }
+}
+
+// columns c0 .. c0 + wc - 1 of the c rows of W into the tile, zeros from column d on: one wavefront per row
+template <int VEC>
+__device__ __forceinline__ void stage_weights(float *__restrict__ tile, const float *__restrict__ wt, const int64_t ldw, const int c,
+                                              const int d, const int c0, const int wc, const int p) {
+    const int lane = threadIdx.x % 64;
+    for (int j = threadIdx.x / 64; j < c; j += 4) {
+        const float *wrow = wt + (int64_t)j * ldw;
+        for (int lc = lane * 4; lc < wc; lc += 256) {
+            const int col = c0 + lc;
+            f4 v = {0.f, 0.f, 0.f, 0.f};
+            if (col < d) v = load4<VEC>(wrow, col, d, j == c - 1);
+            *reinterpret_cast<f4 *>(tile + j * p + lc) = v;
+        }
+    }
+}
+
+__device__ __forceinline__ int imin(const int a, const int b) { return a < b ? a : b; }
+// the two halves' values of a lane pair: [0] is half 0's in both lanes, [1] half 1's
+__device__ __forceinline__ auto halves(const unsigned v) { return __builtin_amdgcn_permlane32_swap(v, v, false, false); }
+__device__ __forceinline__ float halves_sum(const float v) {
+    const auto r = halves(__float_as_uint(v));
+    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+__device__ __forceinline__ int halves_min(const int v) {
+    const auto r = halves((unsigned)v);
+    return imin((int)r[0], (int)r[1]);
+}
+
+template <int VEC, int NT, int R>
+__global__ __launch_bounds__(256) void linear_class_kernel(const float *__restrict__ x, const int64_t ldx, const int64_t n, const int d,
+                                                           const float *__restrict__ wt, const int64_t ldw, const int c,
+                                                           const float *__restrict__ bias, const int64_t *__restrict__ labels,
+                                                           const float wgt, const int w, const int p, const int64_t n_batches,
+                                                           float *__restrict__ row_loss, int64_t *__restrict__ pred,
+                                                           float *__restrict__ dz, const int64_t lddz, const bool dz_vec,
+                                                           float *__restrict__ z, const int64_t ldz, const bool z_vec) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *tile = lds, *bs = lds + c * p;
+    const int lane = threadIdx.x % 64, i = lane % 32, h = lane / 32, wave = threadIdx.x / 64;
+    const bool one_chunk = w >= d, want_exp = dz != nullptr || row_loss != nullptr;
+    bool staged = false;
+    for (int j = threadIdx.x; j < NT * 32; j += 256) bs[j] = (bias && j < c) ? bias[j] : 0.f;
+    __syncthreads();
+    for (int64_t b = blockIdx.x; b < n_batches; b += gridDim.x) {
+        bool in[R], last[R];
+        const float *xp[R];
+        f16v acc[R][NT];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t row = (b * 4 * R + wave * R + r) * 32 + i;
+            in[r] = row < n;
+            const int64_t from = in[r] ? row : 0;    // a tile row beyond the matrix loads nothing and writes nothing
+            last[r] = from == n - 1;
+            xp[r] = x + from * ldx;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) acc[r][t][v] = 0.f;
+        }
+        for (int c0 = 0; c0 < d; c0 += w) {
+            const int left = (d - c0 + 7) / 8 * 8, wc = left < w ? left : w;
+            if (!(staged && one_chunk)) {            // all columns fit: staged once per workgroup, not once per batch
+                __syncthreads();                     // the tile's last readers are done
+                stage_weights<VEC>(tile, wt, ldw, c, d, c0, wc, p);
+                __syncthreads();
+                staged = true;
+            }
+            for (int q0 = 0; q0 < wc; q0 += kStep) {
+                f4 xr[R][4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int col = c0 + q0 + 8 * t + 4 * h;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        f4 v = {0.f, 0.f, 0.f, 0.f};
+                        if (q0 + 8 * t < wc && in[r] && col < d) v = load4<VEC>(xp[r], col, d, last[r]);
+                        xr[r][t] = v;
+                    }
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    if (q0 + 8 * t < wc) {           // the same for every lane
+                        const int lc = q0 + 8 * t + 4 * h;
+#pragma unroll
+                        for (int ct = 0; ct < NT; ++ct) {
+                            const int j = ct * 32 + i;
+                            f4 a = *reinterpret_cast<const f4 *>(tile + (j < c ? j : c - 1) * p + lc);
+                            if (j >= c) a = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                                for (int r = 0; r < R; ++r) acc[r][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], xr[r][t][e], acc[r][ct], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int64_t row = (b * 4 * R + wave * R + r) * 32 + i;
+            // this lane's logits in ascending class order: the bias, the logits out, K14's candidates
+            float top = -INFINITY;
+            int at = kNoIndex, nan_at = kNoIndex;
+#pragma unroll
+            for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int j0 = ct * 32 + 8 * g + 4 * h;
+                    const f4 bb = *reinterpret_cast<const f4 *>(bs + j0);
+                    f4 run;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float v = acc[r][ct][4 * g + e] + bb[e];
+                        acc[r][ct][4 * g + e] = run[e] = v;
+                        if (j0 + e < c) {
+                            if (v != v) {
+                                if (nan_at == kNoIndex) nan_at = j0 + e;
+                            } else if (at == kNoIndex || v > top) {
+                                top = v;
+                                at = j0 + e;
+                            }
+                        }
+                    }
+                    if (z && in[r] && j0 < c) store_cols<4>(z + row * ldz, j0, c, run, z_vec);
+                }
+            const auto tt = halves(__float_as_uint(top));
+            const float m = fmaxf(__uint_as_float(tt[0]), __uint_as_float(tt[1]));   // of the entries that are not NaN
+            if (pred) {
+                const int first_nan = halves_min(nan_at);
+                const int first_top = halves_min((at != kNoIndex && top == m) ? at : kNoIndex);
+                if (in[r] && h == 0) pred[row] = first_nan != kNoIndex ? first_nan : first_top;
+            }
+            if (!want_exp) continue;                 // (uniform: the same for every lane of the launch)
+            const int64_t label = in[r] ? labels[row] : -1;
+            const bool live = label >= 0 && label < c;
+            const int y = live ? (int)label : -1;
+            float part = 0.f, zy = 0.f;
+#pragma unroll
+            for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int j = ct * 32 + 8 * (v / 4) + 4 * h + v % 4;
+                    const float lz = acc[r][ct][v];
+                    const float ex = j < c ? expf(lz - m) : 0.f;
+                    zy = j == y ? lz : zy;
+                    acc[r][ct][v] = ex;
+                    part += ex;
+                }
+            const float s = halves_sum(part);
+            zy = halves_sum(zy);                     // the other half holds 0: exact
+            if (!in[r]) continue;
+            if (row_loss && h == 0) row_loss[row] = live ? (m + logf(s)) - zy : 0.f;
+            if (dz) {
+                float *orow = dz + row * lddz;
+#pragma unroll
+                for (int ct = 0; ct < NT; ++ct)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int j0 = ct * 32 + 8 * g + 4 * h;
+                        f4 o;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] = live ? wgt * (acc[r][ct][4 * g + e] / s - (j0 + e == y ? 1.f : 0.f)) : 0.f;
+                        if (j0 < c) store_cols<4>(orow, j0, c, o, dz_vec);
+                    }
+            }
+        }
+    }
+}
+
+// ---- the weight gradient -------------------------------------------------------------------------------------------------------------
+constexpr int kTiles = 8;                            // 32 x 32 accumulator tiles per wavefront: 128 registers
+constexpr int kTableFloats = kTiles * 1024;          // one workgroup's table: 32 KiB
+constexpr int kPairs = 8;                            // row pairs a wavefront loads before their MFMA steps
+constexpr int kRowsPerClass = 40;                    // R >= 40 C (d + 1) / d: the tables, 2 C (d + 1) floats per block, are <= 5 % of X
+constexpr int kFold = 32;                            // tables in flight per thread of the fold
+
+struct WgradRule {
+    int64_t blocks, rows;                            // B, R
+    int ct, ut, slabs;                               // class tiles x column tiles of a slab, S
+};
+bool wgrad_rule(int64_t n, int64_t d, int64_t c, WgradRule &out) {
+    if (c > SGL_LINEAR_HEAD_MAX_C) return false;
+    const int ct = c <= 32 ? 1 : (c <= 64 ? 2 : (c <= 128 ? 4 : 8)), ut = kTiles / ct;
+    const int64_t tu = (d + 1 + 31) / 32;
+    out = {0, 0, ct, ut, (int)((tu + ut - 1) / ut)};
+    if (n == 0 || c == 0) return true;
+    const int64_t forced = sgl::tuning("loss_blocks", 0);
+    const int64_t rmin = d ? (kRowsPerClass * c * (d + 1) + d - 1) / d : kRowsPerClass * c;
+    int64_t want = forced > 0 ? forced : (n / rmin > 1 ? n / rmin : 1);
+    if (want > kMaxBlocks) want = kMaxBlocks;
+    if (want > n) want = n;
+    out.rows = (n + want - 1) / want;
+    out.blocks = (n + out.rows - 1) / out.rows;
+    return true;
+}
+
+template <int CT>
+__global__ __launch_bounds__(256) void linear_wgrad_kernel(const float *__restrict__ x, const int64_t ldx, const int64_t n, const int d,
+                                                           const float *__restrict__ dz, const int64_t lddz, const int c,
+                                                           const int64_t rows, const int slabs, float *__restrict__ part) {
+    constexpr int UT = kTiles / CT;
+    __shared__ float table[kTableFloats];
+    const int lane = threadIdx.x % 64, i = lane % 32, h = lane / 32, wave = threadIdx.x / 64;
+    const int64_t b = blockIdx.x / slabs;
+    const int s = (int)(blockIdx.x % slabs), u0 = s * UT;
+    const int64_t r0 = b * rows, r1 = r0 + rows < n ? r0 + rows : n;
+    const int tiles_c = (c + 31) / 32, tiles_u = (d + 1 + 31) / 32 - u0;      // live tiles of the slab (the same for every lane)
+    const int64_t pairs = (r1 - r0 + 1) / 2;
+    f16v acc[CT][UT];
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int u = 0; u < UT; ++u)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[t][u][v] = 0.f;
+
+    for (int64_t p0 = wave; p0 < pairs; p0 += 4 * kPairs) {                   // this wavefront's pairs p0, p0 + 4, ...: ascending rows
+        float a[kPairs][CT], bb[kPairs][UT];
+#pragma unroll
+        for (int k = 0; k < kPairs; ++k) {
+            const int64_t row = r0 + 2 * (p0 + 4 * k) + h;
+            const bool on = row < r1;                // the odd row of a last pair, the pairs beyond the block: zeros
+#pragma unroll
+            for (int t = 0; t < CT; ++t) {
+                const int j = 32 * t + i;
+                a[k][t] = (on && j < c) ? dz[row * lddz + j] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < UT; ++u) {
+                const int col = 32 * (u0 + u) + i;
+                bb[k][u] = (on && col < d) ? x[row * ldx + col] : ((on && col == d) ? 1.f : 0.f);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kPairs; ++k) {
+            if (p0 + 4 * k < pairs) {                // the same for every lane of the wavefront
+#pragma unroll
+                for (int t = 0; t < CT; ++t)
+#pragma unroll
+                    for (int u = 0; u < UT; ++u)
+                        if (t < tiles_c && u < tiles_u) acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[k][t], bb[k][u], acc[t][u], 0, 0, 0);
+            }
+        }
+    }
+    // ((wave 0 + wave 1) + wave 2) + wave 3 in LDS; element (tile, v, lane) at tile * 1024 + v * 64 + lane: consecutive lanes, no conflict
+    for (int turn = 0; turn < 4; ++turn) {
+        if (wave == turn) {
+#pragma unroll
+            for (int t = 0; t < CT; ++t)
+#pragma unroll
+                for (int u = 0; u < UT; ++u)
+                    if (t < tiles_c && u < tiles_u) {
+#pragma unroll
+                        for (int v = 0; v < 16; ++v) {
+                            float *at = table + (t * UT + u) * 1024 + v * 64 + lane;
+                            *at = turn ? *at + acc[t][u][v] : acc[t][u][v];
+                        }
+                    }
+        }
+        __syncthreads();
+    }
+    // the table as [32 CT classes][32 UT columns]; only classes < c and columns <= d are written (and read by the fold)
+    float *out = part + (int64_t)blockIdx.x * kTableFloats;
+    for (int e = threadIdx.x; e < kTableFloats; e += 256) {
+        const int tile = e / 1024, v = e / 64 % 16, l = e % 64, t = tile / UT, u = tile % UT;
+        const int jl = 32 * t + 8 * (v / 4) + 4 * (l / 32) + v % 4, cl = 32 * u + l % 32;
+        if (jl < c && 32 * u0 + cl <= d) out[jl * (32 * UT) + cl] = table[e];
+    }
+}
+
+// dw[j, col] / db[j] = the B tables' values in ascending block order, one float32 add each; kFold loads are issued before their adds
+__global__ __launch_bounds__(256) void linear_fold_kernel(const float *__restrict__ part, const int64_t blocks, const int slabs, const int ut,
+                                                          const int c, const int d, float *__restrict__ dw, const int64_t lddw,
+                                                          float *__restrict__ db) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)c * (d + 1)) return;
+    const int64_t j = idx / (d + 1);
+    const int col = (int)(idx % (d + 1)), s = col / (32 * ut);
+    const float *p = part + (int64_t)s * kTableFloats + j * (32 * ut) + (col - s * 32 * ut);
+    const int64_t stride = (int64_t)slabs * kTableFloats;
+    float a = 0.f;
+    int64_t b = 0;
+    for (; b + kFold <= blocks; b += kFold) {
+        float t[kFold];
+#pragma unroll
+        for (int e = 0; e < kFold; ++e) t[e] = p[(b + e) * stride];
+#pragma unroll
+        for (int e = 0; e < kFold; ++e) a = a + t[e];
+    }
+    for (; b < blocks; ++b) a = a + p[b * stride];
+    if (col < d) dw[j * lddw + col] = a;
+    else if (db) db[j] = a;
+}
+
+int check_wgrad(const char *who, int64_t n, int64_t d, int64_t c, WgradRule &rule) {
+    if (!(n >= 0 && d >= 0 && d < INT32_MAX && c >= 0)) return sgl::fail(SGL_ERR_INVALID, "%s: bad sizes", who);
+    SGL_REQUIRE_WIDTH(who, "d", d);
+    if (!wgrad_rule(n, d, c, rule))
+        return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: c=%lld is beyond the compiled range (c <= %d)", who, (long long)c, SGL_LINEAR_HEAD_MAX_C);
+    return SGL_OK;
+}
+
+}  // namespace
+
+SGL_EXPORT int sgl_linear_class_rule(int64_t d, int64_t c, int rule[4]) {
+    SGL_REQUIRE(rule, "sgl_linear_class_rule: NULL arguments");
+    SGL_REQUIRE(d >= 0 && d < INT32_MAX && c >= 1, "sgl_linear_class_rule: bad sizes");
+    SGL_REQUIRE_WIDTH("sgl_linear_class_rule", "d", d);
+    ClassRule r;
+    if (!class_rule(d, c, r))
+        return sgl::fail(SGL_ERR_UNSUPPORTED, "sgl_linear_class_rule: c=%lld is beyond the compiled range (c <= %d)", (long long)c,
+                         SGL_LINEAR_HEAD_MAX_C);
+    rule[0] = r.nt, rule[1] = r.r, rule[2] = r.w, rule[3] = r.p;
+    return SGL_OK;
+}
+
+SGL_EXPORT int sgl_linear_class_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_w, int64_t ldw, int64_t c,
+                                    const float *d_bias, const int64_t *d_labels, float w, float *d_row_loss, int64_t *d_pred, float *d_dz,
+                                    int64_t lddz, float *d_z, int64_t ldz, void *stream) {
+    const char *who = "sgl_linear_class_f32";
+    SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX && c >= 1 && c < INT32_MAX, "%s: bad sizes (n >= 0, d >= 0, c >= 1)", who);
+    SGL_REQUIRE_WIDTH(who, "d", d);
+    SGL_REQUIRE(d_row_loss || d_pred || d_dz || d_z || n == 0, "%s: at least one of d_row_loss, d_pred, d_dz and d_z is needed", who);
+    SGL_REQUIRE((d_x || n == 0 || d == 0) && (d_w || d == 0), "%s: NULL arguments", who);
+    SGL_REQUIRE(d_labels || n == 0 || !(d_dz || d_row_loss), "%s: d_labels may be NULL only without d_row_loss and d_dz", who);
+    SGL_REQUIRE(ldx >= d && ldw >= d && (lddz >= c || !d_dz) && (ldz >= c || !d_z), "%s: row pitch smaller than the row", who);
+    SGL_REQUIRE(aligned_to(d_x, 4) && aligned_to(d_w, 4) && aligned_to(d_bias, 4) && aligned_to(d_dz, 4) && aligned_to(d_z, 4) &&
+                    aligned_to(d_row_loss, 4) && aligned_to(d_labels, 8) && aligned_to(d_pred, 8),
+                "%s: pointers must be aligned to their element size", who);
+    ClassRule rule;
+    if (!class_rule(d, c, rule))
+        return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: c=%lld is beyond the compiled range (c <= %d)", who, (long long)c, SGL_LINEAR_HEAD_MAX_C);
+    if (n == 0) return SGL_OK;
+    hipStream_t st = sgl::as_stream(stream);
+    const bool vec4 = ldx % 4 == 0 && ldw % 4 == 0 && aligned_to(d_x, 16) && aligned_to(d_w, 16);
+    const bool dz_vec = d_dz && lddz % 4 == 0 && aligned_to(d_dz, 16), z_vec = d_z && ldz % 4 == 0 && aligned_to(d_z, 16);
+    if (!sgl::launch_fits(kMaxBlocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
+    const int di = (int)d, ci = (int)c;
+    with_chunks(sgl::KmeansMatrixTiles{}, rule.nt, [&](auto N) {
+        with_vec(vec4, [&](auto V) {
+            constexpr int R = row_tiles(N);
+            const sgl::BatchGrid grid = sgl::loss_batch_grid(n, 4, R * 32, kMaxBlocks);
+            const size_t lds = ((size_t)ci * rule.p + N * 32) * sizeof(float);
+            hipLaunchKernelGGL((linear_class_kernel<V, N, R>), dim3((unsigned)grid.blocks), dim3(256), lds, st, d_x, ldx, n, di, d_w, ldw, ci,
+                               d_bias, d_labels, w, rule.w, rule.p, grid.n_batches, d_row_loss, d_pred, d_dz, lddz, dz_vec, d_z, ldz, z_vec);
+        });
+    });
+    SGL_LAUNCH_CHECK(who);
+    return SGL_OK;
+}
+
+SGL_EXPORT int sgl_linear_wgrad_rule(int64_t n, int64_t d, int64_t c, int64_t *out) {
+    SGL_REQUIRE(out, "sgl_linear_wgrad_rule: bad arguments");
+    WgradRule r;
+    const int rc = check_wgrad("sgl_linear_wgrad_rule", n, d, c, r);
+    if (rc != SGL_OK) return rc;
+    out[0] = r.blocks, out[1] = r.rows, out[2] = r.ct, out[3] = r.ut, out[4] = r.slabs;
+    return SGL_OK;
+}
+
+SGL_EXPORT int64_t sgl_linear_wgrad_scratch(int64_t n, int64_t d, int64_t c) {
+    WgradRule r;
+    return check_wgrad("sgl_linear_wgrad_scratch", n, d, c, r) == SGL_OK ? r.blocks * r.slabs * kTableFloats * (int64_t)sizeof(float) : -1;
+}
+
+SGL_EXPORT int sgl_linear_wgrad_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_dz, int64_t lddz, int64_t c,
+                                    float *d_dw, int64_t lddw, float *d_db, void *d_scratch, void *stream) {
+    const char *who = "sgl_linear_wgrad_f32";
+    WgradRule rule;
+    const int rc = check_wgrad(who, n, d, c, rule);
+    if (rc != SGL_OK) return rc;
+    SGL_REQUIRE((d_x || n == 0 || d == 0) && (d_dz || n == 0 || c == 0) && (d_dw || c == 0 || d == 0) && (d_scratch || rule.blocks == 0),
+                "%s: NULL arguments", who);
+    SGL_REQUIRE(ldx >= d && lddz >= c && lddw >= d, "%s: row pitch smaller than the row", who);
+    SGL_REQUIRE(aligned_to(d_x, 4) && aligned_to(d_dz, 4) && aligned_to(d_dw, 4) && aligned_to(d_db, 4) && aligned_to(d_scratch, 16),
+                "%s: pointers must be aligned to their element size (the scratch to 16 bytes)", who);
+    if (c == 0) return SGL_OK;
+    hipStream_t st = sgl::as_stream(stream);
+    const int ci = (int)c, di = (int)d;
+    float *part = static_cast<float *>(d_scratch);
+    if (rule.blocks) {
+        const int64_t grid = rule.blocks * rule.slabs;
+        if (!sgl::launch_fits(grid, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
+        with_one_of<1, 2, 4, 8>(rule.ct, [&](auto CT) {
+            hipLaunchKernelGGL((linear_wgrad_kernel<CT>), dim3((unsigned)grid), dim3(256), 0, st, d_x, ldx, n, di, d_dz, lddz, ci, rule.rows,
+                               rule.slabs, part);
+        });
+        SGL_LAUNCH_CHECK(who);
+    }
+    const int64_t cells = c * (d + 1);
+    if (!sgl::launch_fits((cells + 255) / 256, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
+    hipLaunchKernelGGL(linear_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, part, rule.blocks, rule.slabs, rule.ut, ci,
+                       di, d_dw, lddw, d_db);
+    SGL_LAUNCH_CHECK(who);
+    return SGL_OK;
+}

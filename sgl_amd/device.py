@@ -51,7 +51,8 @@ def _esize(dtype):
 # entry points whose last argument is not a stream
 _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
                         "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule",
-                        "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch", "sgl_kmeans_seed_rule", "sgl_kmeans_seed_scratch"})
+                        "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch", "sgl_kmeans_seed_rule", "sgl_kmeans_seed_scratch",
+                        "sgl_linear_class_rule", "sgl_linear_wgrad_rule", "sgl_linear_wgrad_scratch"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2272,6 +2273,101 @@ def class_loss_grad(z, labels, w, dz=False, row_loss=False, pred=False):
           _ld(dz) if dz is not None else 0, _opt_ptr(row_loss), _opt_ptr(pred))
     _wrote(dz, row_loss, pred)
     return dz, row_loss, pred
+
+
+LINEAR_HEAD_MAX_C = _lib.SGL_LINEAR_HEAD_MAX_C          # the classes the accumulator tiles of sgl_linear_head.hip cover
+
+
+def _refuse_bf16(who, *tensors):
+    """_no_bf16's refusal as the ValueError the linear-head entry points raise for every input they cannot serve"""
+    try:
+        _no_bf16(who, *tensors)
+    except TypeError as e:
+        raise ValueError(str(e)) from None
+
+
+def _row_vector(who, name, t, n, dtype, like):
+    if not (torch.is_tensor(t) and t.device == like.device and t.dtype == dtype and t.dim() == 1 and t.numel() == n and t.is_contiguous()):
+        raise ValueError(f"{who}: `{name}` must be a contiguous {str(dtype).replace('torch.', '')} [{n}] tensor on x's device")
+    return t
+
+
+def linear_class_loss(x, weight, bias, labels, w, dz=False, row_loss=False, pred=False, logits=False):
+    """One launch of sgl_linear_class_f32 (include/sgl_linear_head.h): the logits Z = x weight^T + bias of a linear head are formed on
+    the matrix cores and class_loss_grad's outputs are computed from them where they stand -- Z is not written unless asked for.
+    x: [n, d], weight: [C, d] (nn.Linear's layout) float32 CUDA matrices on one device, read in place (padded buffers, column views);
+    bias: contiguous float32 [C] or None; labels: int64 [n] on x's device, row i LIVE iff 0 <= labels[i] < C.  row_loss, dz (weight w)
+    and pred have class_loss_grad's meaning, logits is Z [n, C].  dz / row_loss / pred / logits: True allocates the output, a tensor
+    is written in place, None / False leaves it out; at least one is needed.  labels may be None without dz and row_loss: no exp is
+    evaluated then.  C <= LINEAR_HEAD_MAX_C: a larger C raises ValueError, nothing falls back to torch.  Returns (dz, row_loss, pred,
+    logits).  No atomics: two runs are bit-equal; the header states the error bounds.  Nothing here synchronises."""
+    who = "linear_class_loss"
+    _refuse_bf16(who, x, weight, bias, dz, logits)
+    _check_mat(x, "x")
+    _check_mat(weight, "weight")
+    if x.shape[1] != weight.shape[1] or x.device != weight.device:
+        raise ValueError(f"{who}: x and weight must have the same row length and live on one device")
+    n, c = x.shape[0], weight.shape[0]
+    if c < 1:
+        raise ValueError(f"{who}: at least one class is needed")
+    if c > LINEAR_HEAD_MAX_C:
+        raise ValueError(f"{who}: at most {LINEAR_HEAD_MAX_C} classes, got {c}")
+    if bias is not None:
+        _row_vector(who, "bias", bias, c, torch.float32, x)
+    dz, row_loss, pred, logits = (None if t is False else t for t in (dz, row_loss, pred, logits))
+    if dz is None and row_loss is None and pred is None and logits is None:
+        raise ValueError(f"{who}: at least one of `dz`, `row_loss`, `pred` and `logits` is needed")
+    if labels is None:
+        if dz is not None or row_loss is not None:
+            raise ValueError(f"{who}: `labels` may be None only without `dz` and `row_loss`")
+    else:
+        _row_vector(who, "labels", labels, n, torch.int64, x)
+    mats = []
+    for name, t in (("dz", dz), ("logits", logits)):
+        if t is True:
+            t = alloc_rows(n, c, x.device)
+        elif t is not None:
+            _check_mat(t, name)
+            if t.shape != (n, c) or t.device != x.device:
+                raise ValueError(f"{who}: `{name}` must be a [n, C] matrix on x's device")
+        mats.append(t)
+    dz, logits = mats
+    row_loss = torch.empty(n, dtype=torch.float32, device=x.device) if row_loss is True else row_loss
+    pred = torch.empty(n, dtype=torch.int64, device=x.device) if pred is True else pred
+    if row_loss is not None:
+        _row_vector(who, "row_loss", row_loss, n, torch.float32, x)
+    if pred is not None:
+        _row_vector(who, "pred", pred, n, torch.int64, x)
+    _call(x.device, "sgl_linear_class_f32", ptr(x), _ld(x), n, x.shape[1], ptr(weight), _ld(weight), c, _opt_ptr(bias), _opt_ptr(labels),
+          float(w), _opt_ptr(row_loss), _opt_ptr(pred), _opt_ptr(dz), _ld(dz) if dz is not None else 0, _opt_ptr(logits),
+          _ld(logits) if logits is not None else 0)
+    _wrote(dz, row_loss, pred, logits)
+    return dz, row_loss, pred, logits
+
+
+def linear_wgrad(x, dz):
+    """(dW, db) of a linear head from dz = dLoss/dLogits (sgl_linear_wgrad_f32, include/sgl_linear_head.h): dW = dz^T x (float32
+    [C, d]) and db = dz.sum(0) (float32 [C]) on the matrix cores, in two kernels -- partial tables per row block, then a fold in block
+    order.  x: [n, d], dz: [n, C] float32 CUDA matrices on one device, read in place (padded buffers, column views).  No atomics: two
+    runs are bit-equal, and the bits do not depend on the pitches or the alignment.  C <= LINEAR_HEAD_MAX_C: a larger C raises
+    ValueError.  dX = dz weight is not computed here (pre-propagated features need no gradient): that stays a torch matmul.  The
+    partial tables are a scratch tensor of this call (torch's caching allocator)."""
+    _refuse_bf16("linear_wgrad", x, dz)
+    _check_mat(x, "x")
+    _check_mat(dz, "dz")
+    if x.shape[0] != dz.shape[0] or x.device != dz.device:
+        raise ValueError("linear_wgrad: x and dz must have the same number of rows and live on one device")
+    (n, d), c = x.shape, dz.shape[1]
+    if c > LINEAR_HEAD_MAX_C:
+        raise ValueError(f"linear_wgrad: at most {LINEAR_HEAD_MAX_C} classes, got {c}")
+    dw = torch.empty((c, d), dtype=torch.float32, device=x.device)
+    db = torch.empty(c, dtype=torch.float32, device=x.device)
+    nbytes = int(_call(None, "sgl_linear_wgrad_scratch", n, d, c, raw=True))
+    if nbytes < 0:
+        raise _lib.SglHipError(f"sgl_linear_wgrad_scratch failed: {_lib.last_error()}")
+    scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    _call(x.device, "sgl_linear_wgrad_f32", ptr(x), _ld(x), n, d, ptr(dz), _ld(dz), c, ptr(dw), max(d, 1), ptr(db), ptr(scratch))
+    return dw, db
 
 
 def gather_rows(x, idx, out=None):

@@ -58,6 +58,11 @@ class LogisticRegression(nn.Module):
         super(LogisticRegression, self).__init__()
         self.__fc = nn.Linear(feat_dim, output_dim)
 
+    @property
+    def linear(self):
+        """the head's one nn.Linear (weight [C, d], bias [C]): what the fused head of tricks.classification reads and trains"""
+        return self.__fc
+
     def forward(self, feature):
         return self.__fc(feature)
 

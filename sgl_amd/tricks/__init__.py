@@ -7,7 +7,7 @@ task (sgl/tasks/utils.py:101-136, node_clustering.py:12-119); the loss, the accu
 (sgl/tasks/utils.py:12-98, node_classification.py:11-112; sgl/tricks/utils.py:7-10) and of its heterogeneous form
 (node_classification.py:115-217); and the label use / label reuse
 loop around `model.preprocess` (reference: sgl/tasks/node_classification_with_label_use.py:58-137)."""
-from .classification import (HeteroNodeClassification, HeteroNodeClassificationResult, NodeClassificationResult, accuracy, cross_entropy, epoch_batches, evaluate, loge_cross_entropy,
+from .classification import (HeteroNodeClassification, HeteroNodeClassificationResult, NodeClassificationResult, accuracy, cross_entropy, epoch_batches, evaluate, linear_cross_entropy, loge_cross_entropy,
                              hetero_node_classification, mini_batch_evaluate, mini_batch_train, node_classification, predict, train)
 from .clustering import (KMeansResult, NodeClusteringResult, NodeClusteringTrainResult, cluster_loss, clustering_scores, clustering_train,
                          kmeans, nafs_node_clustering, node_clustering)
@@ -25,6 +25,6 @@ __all__ = ["CorrectAndSmooth", "label_propagation", "nafs_ensemble_features", "n
            "EdgePlan", "edge_bce_loss", "edge_predict_train", "edge_predict_eval", "gae_link_prediction", "GAELinkPredictionResult",
            "kmeans", "KMeansResult", "clustering_scores", "nafs_node_clustering", "NodeClusteringResult",
            "cluster_loss", "clustering_train", "node_clustering", "NodeClusteringTrainResult",
-           "cross_entropy", "loge_cross_entropy", "predict", "accuracy", "train", "mini_batch_train", "evaluate", "mini_batch_evaluate",
+           "cross_entropy", "loge_cross_entropy", "linear_cross_entropy", "predict", "accuracy", "train", "mini_batch_train", "evaluate", "mini_batch_evaluate",
            "node_classification", "NodeClassificationResult", "epoch_batches",
            "hetero_node_classification", "HeteroNodeClassification", "HeteroNodeClassificationResult"]

@@ -22,7 +22,7 @@ import torch.nn.functional as F
 
 from .. import device as dev
 
-__all__ = ["cross_entropy", "loge_cross_entropy", "predict", "accuracy", "train", "mini_batch_train", "evaluate", "mini_batch_evaluate",
+__all__ = ["cross_entropy", "loge_cross_entropy", "linear_cross_entropy", "predict", "accuracy", "train", "mini_batch_train", "evaluate", "mini_batch_evaluate",
            "node_classification", "NodeClassificationResult", "epoch_batches",
            "hetero_node_classification", "HeteroNodeClassification", "HeteroNodeClassificationResult"]
 
@@ -139,6 +139,113 @@ def loge_cross_entropy(output, labels, epsilon=LOGE_EPSILON, **kw):
     return (loss, pred) if kw.get("return_pred") else loss
 
 
+class _LinearCrossEntropy(torch.autograd.Function):
+    """_CrossEntropy with the head inside: (loss, pred) of one launch of device.linear_class_loss over the rows x, which also writes
+    dLogits with weight w; the backward multiplies that buffer by the upstream gradient in place (as _CrossEntropy does), hands it to
+    device.linear_wgrad for dW and db, and forms dX = dLogits weight in torch only when x asks for a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, w, scale, want_pred):
+        dz, row_loss, pred, _ = dev.linear_class_loss(x, weight, bias, labels, w, dz=True, row_loss=True, pred=want_pred)
+        ctx.dz, ctx.scale = dz, scale
+        ctx.save_for_backward(x, weight)
+        loss = (row_loss.sum(dtype=torch.float64) * (w if scale is None else scale)).to(torch.float32)
+        if want_pred:
+            ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        dz, ctx.dz = ctx.dz, None
+        if dz is None:
+            raise RuntimeError("linear_cross_entropy: backward ran twice; the gradient buffer of the forward launch was handed out the first time")
+        x, weight = ctx.saved_tensors
+        if ctx.scale is not None:
+            g = (g * ctx.scale).to(torch.float32)
+        dz.mul_(g)
+        dw, db = dev.linear_wgrad(x, dz)
+        dx = dz @ weight if ctx.needs_input_grad[0] else None
+        return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None)
+
+
+def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index=-100, check=True, return_pred=False):
+    """cross_entropy(F.linear(x, weight, bias), labels, ...) -- its value, its label semantics (ignore_index, check, the mean over no
+    live row is NaN) and its gradients -- without the [n, C] logits: ONE launch (device.linear_class_loss -> sgl_linear_class_f32,
+    csrc/sgl_linear_head.hip) forms the logits on the matrix cores and writes the per-row losses, the arg-max when return_pred=True and,
+    when a gradient is wanted, dLogits; the backward gets dweight and dbias from device.linear_wgrad (two launches, deterministic).
+    dx = dLogits weight is a torch matmul and is formed only when x requires grad (pre-propagated features do not).
+    x: [n, d] float32 CUDA matrix read in place; weight [C, d], bias [C] or None: an nn.Linear's parameters, C <=
+    device.LINEAR_HEAD_MAX_C (ValueError beyond; nothing falls back).  The loss is the float64 sum of the float32 row losses; a second
+    backward raises.  return_pred=True returns (loss, pred int64 [n]).  No atomics: two runs are bit-equal."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError("linear_cross_entropy: reduction must be 'mean' or 'sum'")
+    if not (torch.is_tensor(x) and x.dim() == 2 and torch.is_tensor(weight) and weight.dim() == 2 and weight.shape[0] >= 1):
+        raise TypeError("linear_cross_entropy: x must be a [n, d] matrix and weight a [C >= 1, d] matrix")
+    n, c = x.shape[0], weight.shape[0]
+    y, live = _class_labels(labels, c, n, x.device, ignore_index, check)
+    w, scale = 1.0, None
+    if reduction == "mean":
+        if check:
+            w = 1.0 / live if live else float("nan")
+        else:
+            scale = 1.0 / live.to(torch.float64)
+    params = [t for t in (x, weight, bias) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in params):
+        loss, pred = _LinearCrossEntropy.apply(x, weight, bias, y, w, scale, bool(return_pred))
+    else:
+        _, row_loss, pred, _ = dev.linear_class_loss(x.detach(), weight.detach(), None if bias is None else bias.detach(), y, w,
+                                                     row_loss=True, pred=bool(return_pred))
+        loss = (row_loss.sum(dtype=torch.float64) * (w if scale is None else scale)).to(torch.float32)
+    return (loss, pred) if return_pred else loss
+
+
+def _fused_head(model, loss_fn="cross_entropy"):
+    """the nn.Linear of a model whose step can run on the fused head -- an SGAP model with a LogisticRegression head behind a message
+    operator that is not learnable -- and ValueError for everything else (and for a callable loss): fused_head=True never falls back"""
+    from ..models.base_model import BaseSGAPModel
+    from ..models.simple_models import LogisticRegression
+    if not isinstance(loss_fn, str):
+        raise ValueError("fused_head=True needs a built-in loss ('cross_entropy' or 'loge'), not a callable")
+    if not (isinstance(model, BaseSGAPModel) and isinstance(model._base_model, LogisticRegression)):
+        raise ValueError(f"fused_head=True needs a model whose head is a LogisticRegression (SGC, SSGC), not {type(model).__name__}")
+    if model._pre_msg_learnable or model._processed_feature is None:
+        raise ValueError("fused_head=True needs pre-propagated features behind a message operator that is not learnable "
+                         "(call model.preprocess first)")
+    return model._base_model.linear
+
+
+def _head_rows(model, idx, device):
+    """the rows the head reads, as BaseSGAPModel.forward takes them"""
+    from ..models.base_model import take_rows
+    feat = model._processed_feature
+    if isinstance(feat, np.ndarray):
+        feat = torch.from_numpy(feat)
+    return take_rows(feat, idx, device)
+
+
+def _fused_loss_and_pred(model, loss_fn, idx, y, device):
+    fc = _fused_head(model, loss_fn)
+    x = _head_rows(model, idx, device)
+    ce, pred = linear_cross_entropy(x, fc.weight, fc.bias, y, check=False, return_pred=True)
+    return (ce if loss_fn == "cross_entropy" else torch.log(LOGE_EPSILON + ce) - math.log(LOGE_EPSILON)), pred
+
+
+def fused_head_predict(model, idx, device):
+    """the predicted classes of the rows idx from the arg-max-only launch of the fused head: no [n, C] matrix exists"""
+    fc = _fused_head(model)
+    return dev.linear_class_loss(_head_rows(model, idx, device), fc.weight.detach(), None if fc.bias is None else fc.bias.detach(),
+                                 None, 1.0, pred=True)[2]
+
+
+def fused_head_logits(model, idx, device):
+    """model_forward(idx, device) of a fused-head model from the head's own kernel (the logits output of device.linear_class_loss):
+    for the callers that need the [n, C] matrix itself -- post-processing, label reuse"""
+    fc = _fused_head(model)
+    return dev.linear_class_loss(_head_rows(model, idx, device), fc.weight.detach(), None if fc.bias is None else fc.bias.detach(),
+                                 None, 1.0, logits=True)[3]
+
+
 def predict(output):
     """output.max(1)[1] of accuracy (sgl/tasks/utils.py:13) for a [n, C] float32 CUDA matrix: the lowest index of every row's maximum,
     int64 [n] -- the launch with one output: one read of the logits, no exp.  A NaN counts as the maximum, the first NaN wins."""
@@ -184,17 +291,23 @@ def _check_loss_fn(loss_fn):
         raise TypeError("loss_fn must be 'cross_entropy', 'loge' or a callable")
 
 
-def train(model, train_idx, labels, device, optimizer, loss_fn="cross_entropy"):
+def train(model, train_idx, labels, device, optimizer, loss_fn="cross_entropy", fused_head=False):
     """train of the reference (sgl/tasks/utils.py:66-76), one full-batch step: model_forward, the loss and the accuracy of the output,
     backward, optimizer.step.  labels: the int64 labels of ALL nodes on `device`.  With a built-in loss one launch gives the loss,
-    dLogits and the predictions.  Returns (loss, acc) as Python floats: one host read for both."""
+    dLogits and the predictions.  Returns (loss, acc) as Python floats: one host read for both.
+    fused_head=True (a LogisticRegression head on pre-propagated features, a built-in loss; ValueError otherwise): the step never
+    forms the logits -- the rows go to linear_cross_entropy, whose backward gives the head's two gradients."""
     _check_loss_fn(loss_fn)
+    if fused_head:
+        _fused_head(model, loss_fn)
     device = torch.device(device)
     model.train()
     optimizer.zero_grad()
     y = labels[_as_index(train_idx, labels.device)]
-    output = model.model_forward(train_idx, device)
-    loss, pred = _loss_and_pred(loss_fn, output, y)
+    if fused_head:
+        loss, pred = _fused_loss_and_pred(model, loss_fn, train_idx, y, device)
+    else:
+        loss, pred = _loss_and_pred(loss_fn, model.model_forward(train_idx, device), y)
     correct = _correct(pred, y)
     loss.backward()
     optimizer.step()
@@ -202,18 +315,22 @@ def train(model, train_idx, labels, device, optimizer, loss_fn="cross_entropy"):
     return loss_v, correct_v / len(y)
 
 
-def mini_batch_train(model, train_idx, train_loader, labels, device, optimizer, loss_fn="cross_entropy"):
+def mini_batch_train(model, train_idx, train_loader, labels, device, optimizer, loss_fn="cross_entropy", fused_head=False):
     """mini_batch_train of the reference (sgl/tasks/utils.py:79-98): one step per batch of `train_loader` (an iterable of index
     batches); the loss is the unweighted mean of the batch losses, the accuracy the correct count over len(train_idx).  One host read
-    at the end of the epoch."""
+    at the end of the epoch.  fused_head: as in train."""
     _check_loss_fn(loss_fn)
+    if fused_head:
+        _fused_head(model, loss_fn)
     device = torch.device(device)
     model.train()
     losses, correct = [], None
     for batch in train_loader:
         y = labels[_as_index(batch, labels.device)]
-        output = model.model_forward(batch, device)
-        loss, pred = _loss_and_pred(loss_fn, output, y)
+        if fused_head:
+            loss, pred = _fused_loss_and_pred(model, loss_fn, batch, y, device)
+        else:
+            loss, pred = _loss_and_pred(loss_fn, model.model_forward(batch, device), y)
         hit = _correct(pred, y)
         correct = hit if correct is None else correct + hit
         losses.append(loss.detach().double())
@@ -226,32 +343,32 @@ def mini_batch_train(model, train_idx, train_loader, labels, device, optimizer, 
     return sum(values[:-1]) / len(losses), values[-1] / len(train_idx)
 
 
-def _forward_pred(model, idx, device):
-    return _pred_of(model.model_forward(idx, device))
+def _forward_pred(model, idx, device, fused_head=False):
+    return fused_head_predict(model, idx, device) if fused_head else _pred_of(model.model_forward(idx, device))
 
 
 @torch.no_grad()
-def evaluate(model, val_idx, test_idx, labels, device):
+def evaluate(model, val_idx, test_idx, labels, device, fused_head=False):
     """evaluate of the reference (sgl/tasks/utils.py:38-45): (acc_val, acc_test) of the model in eval mode -- two arg-max launches,
-    one host read for both accuracies"""
+    one host read for both accuracies.  fused_head=True: the arg-max-only launch of the fused head, no logits are written."""
     device = torch.device(device)
     model.eval()
-    counts = [_correct(_forward_pred(model, idx, device), labels[_as_index(idx, labels.device)]) for idx in (val_idx, test_idx)]
+    counts = [_correct(_forward_pred(model, idx, device, fused_head), labels[_as_index(idx, labels.device)]) for idx in (val_idx, test_idx)]
     val, test = torch.stack(counts).tolist()
     return val / len(val_idx), test / len(test_idx)
 
 
 @torch.no_grad()
-def mini_batch_evaluate(model, val_idx, val_loader, test_idx, test_loader, labels, device):
+def mini_batch_evaluate(model, val_idx, val_loader, test_idx, test_loader, labels, device, fused_head=False):
     """mini_batch_evaluate of the reference (sgl/tasks/utils.py:48-63): the correct counts of the batches over len(val_idx) and
-    len(test_idx); one host read"""
+    len(test_idx); one host read.  fused_head: as in evaluate."""
     device = torch.device(device)
     model.eval()
     counts = []
     for loader in (val_loader, test_loader):
         total = torch.zeros((), dtype=torch.float64, device=labels.device)
         for batch in loader:
-            total = total + _correct(_forward_pred(model, batch, device), labels[_as_index(batch, labels.device)]).to(labels.device)
+            total = total + _correct(_forward_pred(model, batch, device, fused_head), labels[_as_index(batch, labels.device)]).to(labels.device)
         counts.append(total)
     val, test = torch.stack(counts).tolist()
     return val / len(val_idx), test / len(test_idx)
@@ -278,7 +395,7 @@ post-processing entry (epoch = "post", acc_val, acc_test)"""
 
 
 def node_classification(model, adj, x, y, train_idx, val_idx, test_idx, epochs, lr, weight_decay, loss_fn="cross_entropy", seed=42,
-                        train_batch_size=None, eval_batch_size=None, batches=None, device="cuda"):
+                        train_batch_size=None, eval_batch_size=None, batches=None, device="cuda", fused_head=False):
     """NodeClassification._execute and _postprocess of the reference (sgl/tasks/node_classification.py:45-112), on the device:
     torch.manual_seed(seed), model.preprocess(adj, x), Adam(lr, weight_decay), `epochs` times train + evaluate (mini_batch_train +
     mini_batch_evaluate when train_batch_size is given), then the post-processing step -- model_forward over all nodes in eval mode
@@ -289,8 +406,12 @@ def node_classification(model, adj, x, y, train_idx, val_idx, test_idx, epochs, 
     generator); the evaluation batches keep their order.  batches: a dict that overrides them with explicit lists of index batches --
     "train" (used every epoch; or a callable epoch -> list), "val", "test", "all".
     The reference passes a torch `x` to preprocess, which its own propagate rejects; here both ndarray and tensor are accepted, as
-    everywhere else."""
+    everywhere else.
+    fused_head=True: every step and every evaluation runs on the fused linear head (train, evaluate); the post-processing step takes
+    its logits from the same kernel.  ValueError for a model or a loss the fused head does not serve, before anything is trained."""
     _check_loss_fn(loss_fn)
+    if fused_head and not isinstance(loss_fn, str):
+        raise ValueError("fused_head=True needs a built-in loss ('cross_entropy' or 'loge'), not a callable")
     device = torch.device(device)
     y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(-1).to(device=device, dtype=torch.int64)
     n = int(y.numel())
@@ -304,6 +425,10 @@ def node_classification(model, adj, x, y, train_idx, val_idx, test_idx, epochs, 
     torch.manual_seed(seed)
     model.preprocess(adj, x)
     model = model.to(device)
+    if fused_head:
+        _fused_head(model, loss_fn)
+    forward = (lambda idx: fused_head_logits(model, idx, device)) if fused_head else (lambda idx: model.model_forward(idx, device))
+    head = dict(fused_head=True) if fused_head else {}       # the unfused calls keep the argument lists they have always had
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     if mini:
         ordered = {key: batches[key] if key in batches else epoch_batches(idx, eval_batch_size, None, device)
@@ -312,24 +437,24 @@ def node_classification(model, adj, x, y, train_idx, val_idx, test_idx, epochs, 
     history = []
     for epoch in range(epochs):
         if not mini:
-            loss, acc = train(model, train_idx, y, device, optimizer, loss_fn)
-            acc_val, acc_test = evaluate(model, val_idx, test_idx, y, device)
+            loss, acc = train(model, train_idx, y, device, optimizer, loss_fn, **head)
+            acc_val, acc_test = evaluate(model, val_idx, test_idx, y, device, **head)
         else:
             if "train" in batches:
                 loader = batches["train"](epoch) if callable(batches["train"]) else batches["train"]
             else:
                 loader = epoch_batches(train_idx, train_batch_size, seed + epoch, device)
-            loss, acc = mini_batch_train(model, train_idx, loader, y, device, optimizer, loss_fn)
-            acc_val, acc_test = mini_batch_evaluate(model, val_idx, ordered["val"], test_idx, ordered["test"], y, device)
+            loss, acc = mini_batch_train(model, train_idx, loader, y, device, optimizer, loss_fn, **head)
+            acc_val, acc_test = mini_batch_evaluate(model, val_idx, ordered["val"], test_idx, ordered["test"], y, device, **head)
         history.append(dict(epoch=epoch, loss=loss, acc_train=acc, acc_val=acc_val, acc_test=acc_test))
         if acc_val > best_val:
             best_val, best_test = acc_val, acc_test
     with torch.no_grad():                              # _postprocess (lines 93-112)
         model.eval()
         if not mini:
-            out = model.model_forward(range(n), device)
+            out = forward(range(n))
         else:
-            out = torch.vstack([model.model_forward(batch, device) for batch in ordered["all"]])
+            out = torch.vstack([forward(batch) for batch in ordered["all"]])
         if hasattr(model, "postprocess"):
             out = model.postprocess(adj, out)
         counts = []

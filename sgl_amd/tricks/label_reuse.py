@@ -41,13 +41,20 @@ def add_labels(x, labels, idx, num_classes, out=None, device="cuda"):
 
 
 @torch.no_grad()
-def predict_all(model, n, device, batch_size=None):
-    """model.model_forward over all n nodes (in batches of `batch_size`, the reference's label_reuse_batch_size) -> [n, C] on device"""
+def predict_all(model, n, device, batch_size=None, fused_head=False):
+    """model.model_forward over all n nodes (in batches of `batch_size`, the reference's label_reuse_batch_size) -> [n, C] on device.
+    fused_head=True (a LogisticRegression head on pre-propagated features; ValueError otherwise): the logits come from the fused
+    head's own kernel (classification.fused_head_logits), not from a torch GEMM."""
     device = torch.device(device)
+    if fused_head:
+        from .classification import fused_head_logits
+        forward = lambda idx: fused_head_logits(model, idx, device)   # noqa: E731
+    else:
+        forward = lambda idx: model.model_forward(idx, device)        # noqa: E731
     # contiguous row ranges: the hop rows are views of the hop matrices, nothing is gathered (models/base_model.py take_rows)
     if batch_size is None or batch_size >= n:
-        return model.model_forward(range(n), device)
-    return torch.cat([model.model_forward(range(s, min(s + batch_size, n)), device) for s in range(0, n, batch_size)])
+        return forward(range(n))
+    return torch.cat([forward(range(s, min(s + batch_size, n))) for s in range(0, n, batch_size)])
 
 
 @torch.no_grad()
