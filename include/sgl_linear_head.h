@@ -43,7 +43,8 @@
  * one float).  Two runs are bit-equal.  Error: |dW[j, col] - exact| <= (R / 2 + B + 8) u sum_i |dz[i, j] x[i, col]| (first order): a
  * term passes one product, at most R / 4 + 1 adds in its wavefront, 3 adds in LDS and B in the fold; db the same with x = 1.
  * dX = dZ W is not computed here (pre-propagated features need no gradient).  Nothing synchronises or allocates: d_scratch
- * (sgl_linear_wgrad_scratch bytes, 16-byte aligned) is the caller's. */
+ * (sgl_linear_wgrad_scratch bytes, 16-byte aligned) is the caller's.
+ * The same two kernels on rows idx[i] of a stored float32 or bfloat16 table, without the gathered copy: sgl_linear_rows.h (K22). */
 #ifndef SGL_LINEAR_HEAD_H
 #define SGL_LINEAR_HEAD_H
 

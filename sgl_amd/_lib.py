@@ -220,6 +220,18 @@ LINEAR_HEAD_PROTOTYPES = {
                                      c_void_p]),
 }
 
+# include/sgl_linear_rows.h: K22, K21's two kernels on rows idx[i] of a stored float32 / bfloat16 table
+_CLASS_ROWS = (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_float, c_void_p,
+                       c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p])
+_WGRAD_ROWS = (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                       c_void_p])
+LINEAR_ROWS_PROTOTYPES = {
+    "sgl_linear_class_rows_f32": _CLASS_ROWS,
+    "sgl_linear_class_rows_bf16": _CLASS_ROWS,
+    "sgl_linear_wgrad_rows_f32": _WGRAD_ROWS,
+    "sgl_linear_wgrad_rows_bf16": _WGRAD_ROWS,
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -251,7 +263,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items(),
                                   *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items(), *KMEANS_SEED_PROTOTYPES.items(),
-                                  *LINEAR_HEAD_PROTOTYPES.items()):
+                                  *LINEAR_HEAD_PROTOTYPES.items(), *LINEAR_ROWS_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -18,7 +18,7 @@ SOURCES = ["sgl_core.cpp", "sgl_csr.hip", "sgl_spmm.hip", "sgl_spmm_bf16.hip", "
 # measurement / test support, a library of its own (include/sgl_probe.h): memory probes, placed allocations, synthetic workloads
 PROBE_LIB = os.path.join(HERE, "libsgl_probe.so")
 PROBE_SOURCES = ["sgl_probe_core.cpp", "sgl_probe.hip", "sgl_synth.hip", "sgl_mem.hip"]
-HEADERS = ["sgl_common.h", "sgl_csr.h", "sgl_spmm_common.h", "sgl_rows.h", "sgl_centres.h", "sgl_hash.h", "sgl_csr_search.h", os.path.join(ROOT, "include", "sgl_hip.h"), os.path.join(ROOT, "include", "sgl_probe.h"), os.path.join(ROOT, "include", "sgl_ensemble.h"), os.path.join(ROOT, "include", "sgl_spgemm.h"), os.path.join(ROOT, "include", "sgl_kmeans_mfma.h"), os.path.join(ROOT, "include", "sgl_cluster_sums.h"), os.path.join(ROOT, "include", "sgl_kmeans_seed.h"), os.path.join(ROOT, "include", "sgl_linear_head.h")]
+HEADERS = ["sgl_common.h", "sgl_csr.h", "sgl_spmm_common.h", "sgl_rows.h", "sgl_centres.h", "sgl_hash.h", "sgl_csr_search.h", os.path.join(ROOT, "include", "sgl_hip.h"), os.path.join(ROOT, "include", "sgl_probe.h"), os.path.join(ROOT, "include", "sgl_ensemble.h"), os.path.join(ROOT, "include", "sgl_spgemm.h"), os.path.join(ROOT, "include", "sgl_kmeans_mfma.h"), os.path.join(ROOT, "include", "sgl_cluster_sums.h"), os.path.join(ROOT, "include", "sgl_kmeans_seed.h"), os.path.join(ROOT, "include", "sgl_linear_head.h"), os.path.join(ROOT, "include", "sgl_linear_rows.h")]
 ARCH = "gfx950"
 FLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",

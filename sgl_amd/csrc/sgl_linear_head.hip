@@ -22,12 +22,24 @@
 // K19's two levels: B row blocks x S slabs (blockIdx.x = b S + s: the workgroups that share rows are neighbours), 8 tiles of 32 x 32
 // per wavefront resident for the life of the block, the four wavefronts added in LDS in a fixed order, one table per workgroup, a fold
 // in ascending block order.
+//
+// K22 (include/sgl_linear_rows.h): the same two bodies on STORED rows -- the B operand is row idx[i] of a float32 or bfloat16 table, not
+// row i of a dense float32 matrix.  The bodies take a row source <T, ROWS>: K21 is <float, false> and compiles to what it was; ROWS
+// resolves the source row of a tile row once per batch (class kernel: one coalesced 8-byte read of idx per lane, python's negative wrap,
+// a range check that turns a bad index into a row of NaN without a trap) resp. once per row pair (weight gradient: the half-wave reads
+// one word), keeps the 64-bit row address, and tests "the table's last row" where K21 tests "the matrix's last row".  bfloat16: a lane's
+// four columns are ONE 8-byte access (base 8-byte aligned, pitch a multiple of 4 elements; else four 2-byte ones), each element widened
+// exactly (bits << 16) into the float the MFMA takes -- W stays float32 in LDS, so a logit's chain and its bits are those of K21 on the
+// widened rows.  In flight per wavefront and look-ahead step (kStep = 32 columns): 4 R row loads per lane, 16 bytes each for float32
+// (R x 4 KiB per wavefront), 8 bytes each for bfloat16 (R x 2 KiB).  The lane width of W is a run-time flag here (staging is once per
+// workgroup), so a table's wide lanes do not depend on W's pitch as they do in K21.
 #include <climits>
 #include <cmath>
 
 #include "sgl_rows.h"   // f4, edge_load, store_cols, with_vec, with_chunks, SGL_LAUNCH_CHECK
 
 #include "../../include/sgl_linear_head.h"
+#include "../../include/sgl_linear_rows.h"
 
 namespace {
 
@@ -71,6 +83,35 @@ __device__ __forceinline__ f4 load4(const float *__restrict__ p, const int col, 
     }
 }
 
+// the same of a bfloat16 row, widened exactly.  VEC = 4: one 8-byte access where it stays inside the row's d columns or (not the table's
+// last row) inside its pitch
+__device__ __forceinline__ float widen(const uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
+template <int VEC>
+__device__ __forceinline__ f4 load4(const uint16_t *__restrict__ p, const int col, const int d, const bool last_row) {
+    f4 v;
+    if (VEC == 4 && (col + 4 <= d || !last_row)) {
+        const uint2 u = *reinterpret_cast<const uint2 *>(p + col);
+        v = f4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
+#pragma unroll
+        for (int e = 1; e < 4; ++e)
+            if (col + e >= d) v[e] = 0.f;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? widen(p[col + e]) : 0.f;
+    }
+    return v;
+}
+__device__ __forceinline__ float widen(const float v) { return v; }
+
+// ROWS: the table row a batch row reads -- idx[row] (NULL: row itself), negative ones count from the end; `bad`: outside [-n_rows, n_rows),
+// the row then reads as NaN and row 0 stands in for its address
+__device__ __forceinline__ int64_t source_row(const int64_t *__restrict__ idx, const int64_t row, const int64_t n_rows, bool &bad) {
+    int64_t s = idx ? idx[row] : row;
+    if (s < 0) s += n_rows;
+    bad = s < 0 || s >= n_rows;
+    return bad ? 0 : s;
+}
+
 // columns c0 .. c0 + wc - 1 of the c rows of W into the tile, zeros from column d on: one wavefront per row
 template <int VEC>
 __device__ __forceinline__ void stage_weights(float *__restrict__ tile, const float *__restrict__ wt, const int64_t ldw, const int c,
@@ -99,8 +140,11 @@ __device__ __forceinline__ int halves_min(const int v) {
     return imin((int)r[0], (int)r[1]);
 }
 
-template <int VEC, int NT, int R>
-__global__ __launch_bounds__(256) void linear_class_kernel(const float *__restrict__ x, const int64_t ldx, const int64_t n, const int d,
+// <float, false>: K21, row i of x [n, d].  ROWS: batch row i is row idx[i] of the table x [n_rows, d] of T; VEC is x's lane width alone
+// and w_vec W's
+template <typename T, bool ROWS, int VEC, int NT, int R>
+__global__ __launch_bounds__(256) void linear_class_kernel(const T *__restrict__ x, const int64_t ldx, const int64_t n, const int d,
+                                                           const int64_t *__restrict__ idx, const int64_t n_rows, const bool w_vec,
                                                            const float *__restrict__ wt, const int64_t ldw, const int c,
                                                            const float *__restrict__ bias, const int64_t *__restrict__ labels,
                                                            const float wgt, const int w, const int p, const int64_t n_batches,
@@ -115,15 +159,21 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const float *__restri
     for (int j = threadIdx.x; j < NT * 32; j += 256) bs[j] = (bias && j < c) ? bias[j] : 0.f;
     __syncthreads();
     for (int64_t b = blockIdx.x; b < n_batches; b += gridDim.x) {
-        bool in[R], last[R];
-        const float *xp[R];
+        bool in[R], last[R], bad[R];
+        const T *xp[R];
         f16v acc[R][NT];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int64_t row = (b * 4 * R + wave * R + r) * 32 + i;
             in[r] = row < n;
-            const int64_t from = in[r] ? row : 0;    // a tile row beyond the matrix loads nothing and writes nothing
-            last[r] = from == n - 1;
+            int64_t from = in[r] ? row : 0;          // a tile row beyond the matrix loads nothing and writes nothing
+            bad[r] = false;
+            if constexpr (ROWS) {
+                if (in[r]) from = source_row(idx, row, n_rows, bad[r]);
+                last[r] = from == n_rows - 1;        // of the TABLE: the edge vector of any other row stays inside its pitch
+            } else {
+                last[r] = from == n - 1;
+            }
             xp[r] = x + from * ldx;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
@@ -134,7 +184,9 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const float *__restri
             const int left = (d - c0 + 7) / 8 * 8, wc = left < w ? left : w;
             if (!(staged && one_chunk)) {            // all columns fit: staged once per workgroup, not once per batch
                 __syncthreads();                     // the tile's last readers are done
-                stage_weights<VEC>(tile, wt, ldw, c, d, c0, wc, p);
+                if constexpr (!ROWS) stage_weights<VEC>(tile, wt, ldw, c, d, c0, wc, p);
+                else if (w_vec) stage_weights<4>(tile, wt, ldw, c, d, c0, wc, p);
+                else stage_weights<1>(tile, wt, ldw, c, d, c0, wc, p);
                 __syncthreads();
                 staged = true;
             }
@@ -147,6 +199,12 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const float *__restri
                     for (int r = 0; r < R; ++r) {
                         f4 v = {0.f, 0.f, 0.f, 0.f};
                         if (q0 + 8 * t < wc && in[r] && col < d) v = load4<VEC>(xp[r], col, d, last[r]);
+                        if constexpr (ROWS) {
+                            if (bad[r]) {            // a row of NaN in its d columns: every logit of the row is NaN, nothing traps
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? __uint_as_float(0x7fc00000u) : 0.f;
+                            }
+                        }
                         xr[r][t] = v;
                     }
                 }
@@ -267,8 +325,11 @@ bool wgrad_rule(int64_t n, int64_t d, int64_t c, WgradRule &out) {
     return true;
 }
 
-template <int CT>
-__global__ __launch_bounds__(256) void linear_wgrad_kernel(const float *__restrict__ x, const int64_t ldx, const int64_t n, const int d,
+// <float, false>: K21.  ROWS: row `row` of dz meets row idx[row] of the table x [n_rows, d] of T -- the same for a whole half-wave,
+// resolved once per pair; 2-byte reads for bfloat16 (64 bytes per half-wave and row), widened exactly
+template <typename T, bool ROWS, int CT>
+__global__ __launch_bounds__(256) void linear_wgrad_kernel(const T *__restrict__ x, const int64_t ldx, const int64_t n, const int d,
+                                                           const int64_t *__restrict__ idx, const int64_t n_rows,
                                                            const float *__restrict__ dz, const int64_t lddz, const int c,
                                                            const int64_t rows, const int slabs, float *__restrict__ part) {
     constexpr int UT = kTiles / CT;
@@ -293,6 +354,12 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float *__restri
         for (int k = 0; k < kPairs; ++k) {
             const int64_t row = r0 + 2 * (p0 + 4 * k) + h;
             const bool on = row < r1;                // the odd row of a last pair, the pairs beyond the block: zeros
+            int64_t src = row;
+            bool bad = false;
+            if constexpr (ROWS) {
+                if (on) src = source_row(idx, row, n_rows, bad);
+            }
+            const T *xrow = x + src * ldx;
 #pragma unroll
             for (int t = 0; t < CT; ++t) {
                 const int j = 32 * t + i;
@@ -301,7 +368,9 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const float *__restri
 #pragma unroll
             for (int u = 0; u < UT; ++u) {
                 const int col = 32 * (u0 + u) + i;
-                bb[k][u] = (on && col < d) ? x[row * ldx + col] : ((on && col == d) ? 1.f : 0.f);
+                float v = (on && col == d) ? 1.f : 0.f;
+                if (on && col < d) v = bad ? __uint_as_float(0x7fc00000u) : widen(xrow[col]);
+                bb[k][u] = v;
             }
         }
 #pragma unroll
@@ -387,39 +456,77 @@ SGL_EXPORT int sgl_linear_class_rule(int64_t d, int64_t c, int rule[4]) {
     return SGL_OK;
 }
 
-SGL_EXPORT int sgl_linear_class_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_w, int64_t ldw, int64_t c,
-                                    const float *d_bias, const int64_t *d_labels, float w, float *d_row_loss, int64_t *d_pred, float *d_dz,
-                                    int64_t lddz, float *d_z, int64_t ldz, void *stream) {
-    const char *who = "sgl_linear_class_f32";
-    SGL_REQUIRE(n >= 0 && d >= 0 && d < INT32_MAX && c >= 1 && c < INT32_MAX, "%s: bad sizes (n >= 0, d >= 0, c >= 1)", who);
+namespace {
+
+// Both headers' class entry points: batch row i is row d_idx[i] of the table x [n_rows, d].  K21 passes its matrix x [n, d] without an
+// index (n_rows = n); a float32 table without an index list IS K21's matrix and takes K21's instance
+template <typename T>
+int linear_class(const char *who, const T *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t n, int64_t d,
+                 const float *d_w, int64_t ldw, int64_t c, const float *d_bias, const int64_t *d_labels, float w, float *d_row_loss,
+                 int64_t *d_pred, float *d_dz, int64_t lddz, float *d_z, int64_t ldz, void *stream) {
+    SGL_REQUIRE(n >= 0 && n_rows >= 0 && d >= 0 && d < INT32_MAX && c >= 1 && c < INT32_MAX, "%s: bad sizes (n >= 0, d >= 0, c >= 1)", who);
     SGL_REQUIRE_WIDTH(who, "d", d);
+    SGL_REQUIRE(d_idx || n == n_rows, "%s: without d_idx every row is taken, m must be n_rows", who);
+    SGL_REQUIRE(n_rows > 0 || n == 0, "%s: indices into a table without rows", who);
     SGL_REQUIRE(d_row_loss || d_pred || d_dz || d_z || n == 0, "%s: at least one of d_row_loss, d_pred, d_dz and d_z is needed", who);
     SGL_REQUIRE((d_x || n == 0 || d == 0) && (d_w || d == 0), "%s: NULL arguments", who);
     SGL_REQUIRE(d_labels || n == 0 || !(d_dz || d_row_loss), "%s: d_labels may be NULL only without d_row_loss and d_dz", who);
     SGL_REQUIRE(ldx >= d && ldw >= d && (lddz >= c || !d_dz) && (ldz >= c || !d_z), "%s: row pitch smaller than the row", who);
-    SGL_REQUIRE(aligned_to(d_x, 4) && aligned_to(d_w, 4) && aligned_to(d_bias, 4) && aligned_to(d_dz, 4) && aligned_to(d_z, 4) &&
-                    aligned_to(d_row_loss, 4) && aligned_to(d_labels, 8) && aligned_to(d_pred, 8),
+    SGL_REQUIRE(aligned_to(d_x, sizeof(T)) && aligned_to(d_w, 4) && aligned_to(d_bias, 4) && aligned_to(d_dz, 4) && aligned_to(d_z, 4) &&
+                    aligned_to(d_row_loss, 4) && aligned_to(d_labels, 8) && aligned_to(d_pred, 8) && aligned_to(d_idx, 8),
                 "%s: pointers must be aligned to their element size", who);
     ClassRule rule;
     if (!class_rule(d, c, rule))
         return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: c=%lld is beyond the compiled range (c <= %d)", who, (long long)c, SGL_LINEAR_HEAD_MAX_C);
     if (n == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
-    const bool vec4 = ldx % 4 == 0 && ldw % 4 == 0 && aligned_to(d_x, 16) && aligned_to(d_w, 16);
+    const bool x_vec = ldx % 4 == 0 && aligned_to(d_x, 4 * sizeof(T)), w_vec = ldw % 4 == 0 && aligned_to(d_w, 16);
     const bool dz_vec = d_dz && lddz % 4 == 0 && aligned_to(d_dz, 16), z_vec = d_z && ldz % 4 == 0 && aligned_to(d_z, 16);
     if (!sgl::launch_fits(kMaxBlocks, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
     const int di = (int)d, ci = (int)c;
+    const bool dense = std::is_same<T, float>::value && !d_idx;
     with_chunks(sgl::KmeansMatrixTiles{}, rule.nt, [&](auto N) {
-        with_vec(vec4, [&](auto V) {
+        with_vec(dense ? x_vec && w_vec : x_vec, [&](auto V) {
             constexpr int R = row_tiles(N);
             const sgl::BatchGrid grid = sgl::loss_batch_grid(n, 4, R * 32, kMaxBlocks);
             const size_t lds = ((size_t)ci * rule.p + N * 32) * sizeof(float);
-            hipLaunchKernelGGL((linear_class_kernel<V, N, R>), dim3((unsigned)grid.blocks), dim3(256), lds, st, d_x, ldx, n, di, d_w, ldw, ci,
-                               d_bias, d_labels, w, rule.w, rule.p, grid.n_batches, d_row_loss, d_pred, d_dz, lddz, dz_vec, d_z, ldz, z_vec);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)grid.blocks), dim3(256), lds, st, d_x, ldx, n, di, d_idx, n_rows, w_vec, d_w, ldw, ci,
+                                   d_bias, d_labels, w, rule.w, rule.p, grid.n_batches, d_row_loss, d_pred, d_dz, lddz, dz_vec, d_z, ldz, z_vec);
+            };
+            if constexpr (std::is_same<T, float>::value) {
+                if (dense) launch(linear_class_kernel<float, false, V, N, R>);
+                else launch(linear_class_kernel<float, true, V, N, R>);
+            } else {
+                launch(linear_class_kernel<T, true, V, N, R>);
+            }
         });
     });
     SGL_LAUNCH_CHECK(who);
     return SGL_OK;
+}
+
+}  // namespace
+
+SGL_EXPORT int sgl_linear_class_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_w, int64_t ldw, int64_t c,
+                                    const float *d_bias, const int64_t *d_labels, float w, float *d_row_loss, int64_t *d_pred, float *d_dz,
+                                    int64_t lddz, float *d_z, int64_t ldz, void *stream) {
+    return linear_class("sgl_linear_class_f32", d_x, ldx, n, nullptr, n, d, d_w, ldw, c, d_bias, d_labels, w, d_row_loss, d_pred, d_dz,
+                        lddz, d_z, ldz, stream);
+}
+
+SGL_EXPORT int sgl_linear_class_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t m, int64_t d,
+                                         const float *d_w, int64_t ldw, int64_t c, const float *d_bias, const int64_t *d_labels, float w,
+                                         float *d_row_loss, int64_t *d_pred, float *d_dz, int64_t lddz, float *d_z, int64_t ldz, void *stream) {
+    return linear_class("sgl_linear_class_rows_f32", d_x, ldx, n_rows, d_idx, m, d, d_w, ldw, c, d_bias, d_labels, w, d_row_loss, d_pred,
+                        d_dz, lddz, d_z, ldz, stream);
+}
+
+SGL_EXPORT int sgl_linear_class_rows_bf16(const uint16_t *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t m, int64_t d,
+                                          const float *d_w, int64_t ldw, int64_t c, const float *d_bias, const int64_t *d_labels, float w,
+                                          float *d_row_loss, int64_t *d_pred, float *d_dz, int64_t lddz, float *d_z, int64_t ldz, void *stream) {
+    return linear_class("sgl_linear_class_rows_bf16", d_x, ldx, n_rows, d_idx, m, d, d_w, ldw, c, d_bias, d_labels, w, d_row_loss, d_pred,
+                        d_dz, lddz, d_z, ldz, stream);
 }
 
 SGL_EXPORT int sgl_linear_wgrad_rule(int64_t n, int64_t d, int64_t c, int64_t *out) {
@@ -436,16 +543,23 @@ SGL_EXPORT int64_t sgl_linear_wgrad_scratch(int64_t n, int64_t d, int64_t c) {
     return check_wgrad("sgl_linear_wgrad_scratch", n, d, c, r) == SGL_OK ? r.blocks * r.slabs * kTableFloats * (int64_t)sizeof(float) : -1;
 }
 
-SGL_EXPORT int sgl_linear_wgrad_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_dz, int64_t lddz, int64_t c,
-                                    float *d_dw, int64_t lddw, float *d_db, void *d_scratch, void *stream) {
-    const char *who = "sgl_linear_wgrad_f32";
+namespace {
+
+// Both headers' weight gradients: the row source as in linear_class; the rule and the scratch are sgl_linear_wgrad_rule's with n = the
+// rows of dz
+template <typename T>
+int linear_wgrad(const char *who, const T *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t n, int64_t d, const float *d_dz,
+                 int64_t lddz, int64_t c, float *d_dw, int64_t lddw, float *d_db, void *d_scratch, void *stream) {
     WgradRule rule;
     const int rc = check_wgrad(who, n, d, c, rule);
     if (rc != SGL_OK) return rc;
+    SGL_REQUIRE(n_rows >= 0 && (d_idx || n == n_rows), "%s: without d_idx every row is taken, m must be n_rows", who);
+    SGL_REQUIRE(n_rows > 0 || n == 0, "%s: indices into a table without rows", who);
     SGL_REQUIRE((d_x || n == 0 || d == 0) && (d_dz || n == 0 || c == 0) && (d_dw || c == 0 || d == 0) && (d_scratch || rule.blocks == 0),
                 "%s: NULL arguments", who);
     SGL_REQUIRE(ldx >= d && lddz >= c && lddw >= d, "%s: row pitch smaller than the row", who);
-    SGL_REQUIRE(aligned_to(d_x, 4) && aligned_to(d_dz, 4) && aligned_to(d_dw, 4) && aligned_to(d_db, 4) && aligned_to(d_scratch, 16),
+    SGL_REQUIRE(aligned_to(d_x, sizeof(T)) && aligned_to(d_dz, 4) && aligned_to(d_dw, 4) && aligned_to(d_db, 4) && aligned_to(d_scratch, 16) &&
+                    aligned_to(d_idx, 8),
                 "%s: pointers must be aligned to their element size (the scratch to 16 bytes)", who);
     if (c == 0) return SGL_OK;
     hipStream_t st = sgl::as_stream(stream);
@@ -455,8 +569,16 @@ SGL_EXPORT int sgl_linear_wgrad_f32(const float *d_x, int64_t ldx, int64_t n, in
         const int64_t grid = rule.blocks * rule.slabs;
         if (!sgl::launch_fits(grid, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
         with_one_of<1, 2, 4, 8>(rule.ct, [&](auto CT) {
-            hipLaunchKernelGGL((linear_wgrad_kernel<CT>), dim3((unsigned)grid), dim3(256), 0, st, d_x, ldx, n, di, d_dz, lddz, ci, rule.rows,
-                               rule.slabs, part);
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, st, d_x, ldx, n, di, d_idx, n_rows, d_dz, lddz, ci, rule.rows,
+                                   rule.slabs, part);
+            };
+            if constexpr (std::is_same<T, float>::value) {
+                if (!d_idx) launch(linear_wgrad_kernel<float, false, CT>);
+                else launch(linear_wgrad_kernel<float, true, CT>);
+            } else {
+                launch(linear_wgrad_kernel<T, true, CT>);
+            }
         });
         SGL_LAUNCH_CHECK(who);
     }
@@ -466,4 +588,23 @@ SGL_EXPORT int sgl_linear_wgrad_f32(const float *d_x, int64_t ldx, int64_t n, in
                        di, d_dw, lddw, d_db);
     SGL_LAUNCH_CHECK(who);
     return SGL_OK;
+}
+
+}  // namespace
+
+SGL_EXPORT int sgl_linear_wgrad_f32(const float *d_x, int64_t ldx, int64_t n, int64_t d, const float *d_dz, int64_t lddz, int64_t c,
+                                    float *d_dw, int64_t lddw, float *d_db, void *d_scratch, void *stream) {
+    return linear_wgrad("sgl_linear_wgrad_f32", d_x, ldx, n, nullptr, n, d, d_dz, lddz, c, d_dw, lddw, d_db, d_scratch, stream);
+}
+
+SGL_EXPORT int sgl_linear_wgrad_rows_f32(const float *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t m, int64_t d,
+                                         const float *d_dz, int64_t lddz, int64_t c, float *d_dw, int64_t lddw, float *d_db, void *d_scratch,
+                                         void *stream) {
+    return linear_wgrad("sgl_linear_wgrad_rows_f32", d_x, ldx, n_rows, d_idx, m, d, d_dz, lddz, c, d_dw, lddw, d_db, d_scratch, stream);
+}
+
+SGL_EXPORT int sgl_linear_wgrad_rows_bf16(const uint16_t *d_x, int64_t ldx, int64_t n_rows, const int64_t *d_idx, int64_t m, int64_t d,
+                                          const float *d_dz, int64_t lddz, int64_t c, float *d_dw, int64_t lddw, float *d_db, void *d_scratch,
+                                          void *stream) {
+    return linear_wgrad("sgl_linear_wgrad_rows_bf16", d_x, ldx, n_rows, d_idx, m, d, d_dz, lddz, c, d_dw, lddw, d_db, d_scratch, stream);
 }

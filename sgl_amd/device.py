@@ -2301,13 +2301,37 @@ def linear_class_loss(x, weight, bias, labels, w, dz=False, row_loss=False, pred
     is written in place, None / False leaves it out; at least one is needed.  labels may be None without dz and row_loss: no exp is
     evaluated then.  C <= LINEAR_HEAD_MAX_C: a larger C raises ValueError, nothing falls back to torch.  Returns (dz, row_loss, pred,
     logits).  No atomics: two runs are bit-equal; the header states the error bounds.  Nothing here synchronises."""
-    who = "linear_class_loss"
-    _refuse_bf16(who, x, weight, bias, dz, logits)
-    _check_mat(x, "x")
+    return _linear_class("linear_class_loss", None, x, None, weight, bias, labels, w, dz, row_loss, pred, logits)
+
+
+def _table(who, x, *others):
+    """the checks of a row table (float32 or bfloat16, read in place) of the *_rows entry points; `others` stay float32"""
+    _refuse_bf16(who, *others)
+    try:
+        _check_mat(x, "x", bf16=True)
+    except TypeError as e:
+        raise ValueError(f"{who}: {e}") from None
+    return "bf16" if x.dtype == torch.bfloat16 else "f32"
+
+
+def _table_index(idx, x):
+    """the index of a *_rows call as the library takes it: None -- every row in order, no index is built or uploaded -- for None and
+    for a range over the whole table, else _device_index's flat int64 tensor on x's device (a tensor that already is one passes)"""
+    if idx is None or (isinstance(idx, range) and idx == range(x.shape[0])):
+        return None
+    return _device_index(idx, x.shape[0], x.device)
+
+
+def _linear_class(who, kind, x, idx, weight, bias, labels, w, dz, row_loss, pred, logits):
+    """linear_class_loss (kind None: x is the [n, d] float32 matrix) and linear_class_loss_rows (kind = _table's: x is the table, idx a
+    flat int64 device tensor or None for every row): one set of checks, one call"""
+    if kind is None:
+        _refuse_bf16(who, x, weight, bias, dz, logits)
+        _check_mat(x, "x")
     _check_mat(weight, "weight")
     if x.shape[1] != weight.shape[1] or x.device != weight.device:
         raise ValueError(f"{who}: x and weight must have the same row length and live on one device")
-    n, c = x.shape[0], weight.shape[0]
+    n, c = (x.shape[0] if idx is None else idx.numel()), weight.shape[0]
     if c < 1:
         raise ValueError(f"{who}: at least one class is needed")
     if c > LINEAR_HEAD_MAX_C:
@@ -2338,11 +2362,28 @@ def linear_class_loss(x, weight, bias, labels, w, dz=False, row_loss=False, pred
         _row_vector(who, "row_loss", row_loss, n, torch.float32, x)
     if pred is not None:
         _row_vector(who, "pred", pred, n, torch.int64, x)
-    _call(x.device, "sgl_linear_class_f32", ptr(x), _ld(x), n, x.shape[1], ptr(weight), _ld(weight), c, _opt_ptr(bias), _opt_ptr(labels),
-          float(w), _opt_ptr(row_loss), _opt_ptr(pred), _opt_ptr(dz), _ld(dz) if dz is not None else 0, _opt_ptr(logits),
-          _ld(logits) if logits is not None else 0)
+    head = (ptr(weight), _ld(weight), c, _opt_ptr(bias), _opt_ptr(labels), float(w), _opt_ptr(row_loss), _opt_ptr(pred), _opt_ptr(dz),
+            _ld(dz) if dz is not None else 0, _opt_ptr(logits), _ld(logits) if logits is not None else 0)
+    if kind:
+        _call(x.device, f"sgl_linear_class_rows_{kind}", ptr(x), _ld(x), x.shape[0], _opt_ptr(idx), n, x.shape[1], *head)
+    else:
+        _call(x.device, "sgl_linear_class_f32", ptr(x), _ld(x), n, x.shape[1], *head)
     _wrote(dz, row_loss, pred, logits)
     return dz, row_loss, pred, logits
+
+
+def linear_class_loss_rows(x, idx, weight, bias, labels, w, dz=False, row_loss=False, pred=False, logits=False):
+    """linear_class_loss on the rows x[idx] of a stored table WITHOUT gathering them (sgl_linear_class_rows_f32 / _bf16,
+    include/sgl_linear_rows.h): batch row i is x[idx[i]].  x: [n_rows, d] float32 or bfloat16 CUDA matrix read in place (padded buffers,
+    column views; bf16 hop storage); idx: whatever gather_rows takes (range, list, ndarray, CPU or CUDA tensor; negative indices count
+    from the end; host indices are validated on the host), or None -- or a range over the whole table -- for every row in order.  weight, bias stay float32.  labels and every
+    output have len(idx) rows and are indexed by the position in idx.  Bit for bit what linear_class_loss(gather_rows(x, idx), ...)
+    gives, output by output.  A device index out of range cannot be reported without a host read: that batch row's logits are NaN.
+    Everything else -- the outputs, the ValueErrors, C <= LINEAR_HEAD_MAX_C -- as in linear_class_loss."""
+    who = "linear_class_loss_rows"
+    kind = _table(who, x, weight, bias, dz, logits)
+    return _linear_class(who, kind, x, _table_index(idx, x), weight, bias, labels, w, dz,
+                         row_loss, pred, logits)
 
 
 def linear_wgrad(x, dz):
@@ -2352,21 +2393,39 @@ def linear_wgrad(x, dz):
     runs are bit-equal, and the bits do not depend on the pitches or the alignment.  C <= LINEAR_HEAD_MAX_C: a larger C raises
     ValueError.  dX = dz weight is not computed here (pre-propagated features need no gradient): that stays a torch matmul.  The
     partial tables are a scratch tensor of this call (torch's caching allocator)."""
-    _refuse_bf16("linear_wgrad", x, dz)
-    _check_mat(x, "x")
+    return _linear_wgrad("linear_wgrad", None, x, None, dz)
+
+
+def linear_wgrad_rows(x, idx, dz):
+    """linear_wgrad on the rows x[idx] of a stored table without gathering them (sgl_linear_wgrad_rows_f32 / _bf16,
+    include/sgl_linear_rows.h): dW = dz^T x[idx], db = dz.sum(0).  x, idx: as in linear_class_loss_rows; dz: [len(idx), C] float32.
+    Bit for bit what linear_wgrad(gather_rows(x, idx), dz) gives under the same "loss_blocks"."""
+    who = "linear_wgrad_rows"
+    kind = _table(who, x, dz)
+    return _linear_wgrad(who, kind, x, _table_index(idx, x), dz)
+
+
+def _linear_wgrad(who, kind, x, idx, dz):
+    if kind is None:
+        _refuse_bf16(who, x, dz)
+        _check_mat(x, "x")
     _check_mat(dz, "dz")
-    if x.shape[0] != dz.shape[0] or x.device != dz.device:
-        raise ValueError("linear_wgrad: x and dz must have the same number of rows and live on one device")
-    (n, d), c = x.shape, dz.shape[1]
+    n, d, c = (x.shape[0] if idx is None else idx.numel()), x.shape[1], dz.shape[1]
+    if n != dz.shape[0] or x.device != dz.device:
+        raise ValueError(f"{who}: x{'[idx]' if kind else ''} and dz must have the same number of rows and live on one device")
     if c > LINEAR_HEAD_MAX_C:
-        raise ValueError(f"linear_wgrad: at most {LINEAR_HEAD_MAX_C} classes, got {c}")
+        raise ValueError(f"{who}: at most {LINEAR_HEAD_MAX_C} classes, got {c}")
     dw = torch.empty((c, d), dtype=torch.float32, device=x.device)
     db = torch.empty(c, dtype=torch.float32, device=x.device)
     nbytes = int(_call(None, "sgl_linear_wgrad_scratch", n, d, c, raw=True))
     if nbytes < 0:
         raise _lib.SglHipError(f"sgl_linear_wgrad_scratch failed: {_lib.last_error()}")
     scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
-    _call(x.device, "sgl_linear_wgrad_f32", ptr(x), _ld(x), n, d, ptr(dz), _ld(dz), c, ptr(dw), max(d, 1), ptr(db), ptr(scratch))
+    tail = (ptr(dz), _ld(dz), c, ptr(dw), max(d, 1), ptr(db), ptr(scratch))
+    if kind:
+        _call(x.device, f"sgl_linear_wgrad_rows_{kind}", ptr(x), _ld(x), x.shape[0], _opt_ptr(idx), n, d, *tail)
+    else:
+        _call(x.device, "sgl_linear_wgrad_f32", ptr(x), _ld(x), n, d, *tail)
     return dw, db
 
 

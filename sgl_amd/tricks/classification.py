@@ -145,10 +145,15 @@ class _LinearCrossEntropy(torch.autograd.Function):
     device.linear_wgrad for dW and db, and forms dX = dLogits weight in torch only when x asks for a gradient."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, labels, w, scale, want_pred):
-        dz, row_loss, pred, _ = dev.linear_class_loss(x, weight, bias, labels, w, dz=True, row_loss=True, pred=want_pred)
-        ctx.dz, ctx.scale = dz, scale
-        ctx.save_for_backward(x, weight)
+    def forward(ctx, x, weight, bias, labels, w, scale, want_pred, in_place=False, rows=None):
+        # in_place: x is a stored table and the batch its rows `rows` (device._table_index's: a device index, or None for every row),
+        # read where they are stored -- the table and the index are saved, no copy of the batch exists
+        if in_place:
+            dz, row_loss, pred, _ = dev.linear_class_loss_rows(x, rows, weight, bias, labels, w, dz=True, row_loss=True, pred=want_pred)
+        else:
+            dz, row_loss, pred, _ = dev.linear_class_loss(x, weight, bias, labels, w, dz=True, row_loss=True, pred=want_pred)
+        ctx.dz, ctx.scale, ctx.in_place = dz, scale, in_place
+        ctx.save_for_backward(x, weight, rows)
         loss = (row_loss.sum(dtype=torch.float64) * (w if scale is None else scale)).to(torch.float32)
         if want_pred:
             ctx.mark_non_differentiable(pred)
@@ -160,16 +165,16 @@ class _LinearCrossEntropy(torch.autograd.Function):
         dz, ctx.dz = ctx.dz, None
         if dz is None:
             raise RuntimeError("linear_cross_entropy: backward ran twice; the gradient buffer of the forward launch was handed out the first time")
-        x, weight = ctx.saved_tensors
+        x, weight, rows = ctx.saved_tensors
         if ctx.scale is not None:
             g = (g * ctx.scale).to(torch.float32)
         dz.mul_(g)
-        dw, db = dev.linear_wgrad(x, dz)
+        dw, db = dev.linear_wgrad_rows(x, rows, dz) if ctx.in_place else dev.linear_wgrad(x, dz)
         dx = dz @ weight if ctx.needs_input_grad[0] else None
-        return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None)
+        return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
 
 
-def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index=-100, check=True, return_pred=False):
+def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index=-100, check=True, return_pred=False, rows=None):
     """cross_entropy(F.linear(x, weight, bias), labels, ...) -- its value, its label semantics (ignore_index, check, the mean over no
     live row is NaN) and its gradients -- without the [n, C] logits: ONE launch (device.linear_class_loss -> sgl_linear_class_f32,
     csrc/sgl_linear_head.hip) forms the logits on the matrix cores and writes the per-row losses, the arg-max when return_pred=True and,
@@ -177,12 +182,21 @@ def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index
     dx = dLogits weight is a torch matmul and is formed only when x requires grad (pre-propagated features do not).
     x: [n, d] float32 CUDA matrix read in place; weight [C, d], bias [C] or None: an nn.Linear's parameters, C <=
     device.LINEAR_HEAD_MAX_C (ValueError beyond; nothing falls back).  The loss is the float64 sum of the float32 row losses; a second
-    backward raises.  return_pred=True returns (loss, pred int64 [n]).  No atomics: two runs are bit-equal."""
+    backward raises.  return_pred=True returns (loss, pred int64 [n]).  No atomics: two runs are bit-equal.
+    rows (anything device.gather_rows takes): x is a stored TABLE, float32 or bfloat16, and the batch its rows x[rows], read where they
+    are stored (device.linear_class_loss_rows, device.linear_wgrad_rows; include/sgl_linear_rows.h) -- labels has len(rows) entries, the
+    backward keeps the table and the index instead of a copy of the batch, and every bit is that of the call on gather_rows(x, rows).
+    A table that requires grad is refused (there is no dX in place)."""
     if reduction not in ("mean", "sum"):
         raise ValueError("linear_cross_entropy: reduction must be 'mean' or 'sum'")
     if not (torch.is_tensor(x) and x.dim() == 2 and torch.is_tensor(weight) and weight.dim() == 2 and weight.shape[0] >= 1):
         raise TypeError("linear_cross_entropy: x must be a [n, d] matrix and weight a [C >= 1, d] matrix")
-    n, c = x.shape[0], weight.shape[0]
+    in_place = rows is not None
+    if in_place:
+        if x.requires_grad:
+            raise ValueError("linear_cross_entropy: with `rows`, x is a stored table and gets no gradient; detach it")
+        rows = dev._table_index(rows, x)                  # None: a range over the whole table, every row in order
+    n, c = (x.shape[0] if rows is None else rows.numel()), weight.shape[0]
     y, live = _class_labels(labels, c, n, x.device, ignore_index, check)
     w, scale = 1.0, None
     if reduction == "mean":
@@ -192,19 +206,24 @@ def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index
             scale = 1.0 / live.to(torch.float64)
     params = [t for t in (x, weight, bias) if t is not None]
     if torch.is_grad_enabled() and any(t.requires_grad for t in params):
-        loss, pred = _LinearCrossEntropy.apply(x, weight, bias, y, w, scale, bool(return_pred))
+        loss, pred = _LinearCrossEntropy.apply(x, weight, bias, y, w, scale, bool(return_pred), in_place, rows)
     else:
-        _, row_loss, pred, _ = dev.linear_class_loss(x.detach(), weight.detach(), None if bias is None else bias.detach(), y, w,
-                                                     row_loss=True, pred=bool(return_pred))
+        head = (weight.detach(), None if bias is None else bias.detach(), y, w)
+        outs = dict(row_loss=True, pred=bool(return_pred))
+        _, row_loss, pred, _ = dev.linear_class_loss_rows(x, rows, *head, **outs) if in_place else dev.linear_class_loss(x.detach(), *head, **outs)
         loss = (row_loss.sum(dtype=torch.float64) * (w if scale is None else scale)).to(torch.float32)
     return (loss, pred) if return_pred else loss
 
 
-def _fused_head(model, loss_fn="cross_entropy"):
+def _fused_head(model, loss_fn="cross_entropy", mode=True):
     """the nn.Linear of a model whose step can run on the fused head -- an SGAP model with a LogisticRegression head behind a message
-    operator that is not learnable -- and ValueError for everything else (and for a callable loss): fused_head=True never falls back"""
+    operator that is not learnable -- and ValueError for everything else (and for a callable loss): fused_head=True never falls back.
+    mode "in_place" (the head reads the rows where they are stored, include/sgl_linear_rows.h): the processed features must also be a
+    float32 or bfloat16 matrix on the device"""
     from ..models.base_model import BaseSGAPModel
     from ..models.simple_models import LogisticRegression
+    if mode is not True and mode != "in_place":
+        raise ValueError(f"fused_head must be False, True or 'in_place', not {mode!r}")
     if not isinstance(loss_fn, str):
         raise ValueError("fused_head=True needs a built-in loss ('cross_entropy' or 'loge'), not a callable")
     if not (isinstance(model, BaseSGAPModel) and isinstance(model._base_model, LogisticRegression)):
@@ -212,6 +231,9 @@ def _fused_head(model, loss_fn="cross_entropy"):
     if model._pre_msg_learnable or model._processed_feature is None:
         raise ValueError("fused_head=True needs pre-propagated features behind a message operator that is not learnable "
                          "(call model.preprocess first)")
+    feat = model._processed_feature
+    if mode == "in_place" and not (torch.is_tensor(feat) and feat.is_cuda and feat.dim() == 2 and feat.dtype in (torch.float32, torch.bfloat16)):
+        raise ValueError("fused_head='in_place' needs the processed features as a float32 or bfloat16 matrix on the device")
     return model._base_model.linear
 
 
@@ -224,26 +246,44 @@ def _head_rows(model, idx, device):
     return take_rows(feat, idx, device)
 
 
-def _fused_loss_and_pred(model, loss_fn, idx, y, device):
-    fc = _fused_head(model, loss_fn)
-    x = _head_rows(model, idx, device)
-    ce, pred = linear_cross_entropy(x, fc.weight, fc.bias, y, check=False, return_pred=True)
+def _head_input(model, idx, device, mode):
+    """(x, rows) of the head's calls: the gathered float32 rows and None, or ("in_place") the stored table and the index into it as
+    the caller gave it (a range over all its rows is "every row in order" to the *_rows calls); take_rows is not called"""
+    if mode != "in_place":
+        return _head_rows(model, idx, device), None
+    table, want = model._processed_feature, torch.device(device)
+    if want.type == "cuda" and want.index is None:        # "cuda" is the current device, as it is for tensor.to("cuda")
+        want = torch.device("cuda", torch.cuda.current_device())
+    if table.device != want:
+        raise ValueError(f"fused_head='in_place': the processed features live on {table.device}, not on {want}")
+    return table, idx
+
+
+def _head_outputs(model, idx, device, mode, **outs):
+    """(dz, row_loss, pred, logits) of one launch of the head without labels, on the gathered rows or in place"""
+    fc = _fused_head(model, mode=mode)
+    x, rows = _head_input(model, idx, device, mode)
+    head = (fc.weight.detach(), None if fc.bias is None else fc.bias.detach(), None, 1.0)
+    return dev.linear_class_loss_rows(x, rows, *head, **outs) if mode == "in_place" else dev.linear_class_loss(x, *head, **outs)
+
+
+def _fused_loss_and_pred(model, loss_fn, idx, y, device, mode=True):
+    fc = _fused_head(model, loss_fn, mode)
+    x, rows = _head_input(model, idx, device, mode)
+    ce, pred = linear_cross_entropy(x, fc.weight, fc.bias, y, check=False, return_pred=True, rows=rows)
     return (ce if loss_fn == "cross_entropy" else torch.log(LOGE_EPSILON + ce) - math.log(LOGE_EPSILON)), pred
 
 
-def fused_head_predict(model, idx, device):
-    """the predicted classes of the rows idx from the arg-max-only launch of the fused head: no [n, C] matrix exists"""
-    fc = _fused_head(model)
-    return dev.linear_class_loss(_head_rows(model, idx, device), fc.weight.detach(), None if fc.bias is None else fc.bias.detach(),
-                                 None, 1.0, pred=True)[2]
+def fused_head_predict(model, idx, device, mode=True):
+    """the predicted classes of the rows idx from the arg-max-only launch of the fused head: no [n, C] matrix exists.  mode: the
+    fused_head argument of the callers (True, or "in_place": the rows are read where they are stored)"""
+    return _head_outputs(model, idx, device, mode, pred=True)[2]
 
 
-def fused_head_logits(model, idx, device):
+def fused_head_logits(model, idx, device, mode=True):
     """model_forward(idx, device) of a fused-head model from the head's own kernel (the logits output of device.linear_class_loss):
-    for the callers that need the [n, C] matrix itself -- post-processing, label reuse"""
-    fc = _fused_head(model)
-    return dev.linear_class_loss(_head_rows(model, idx, device), fc.weight.detach(), None if fc.bias is None else fc.bias.detach(),
-                                 None, 1.0, logits=True)[3]
+    for the callers that need the [n, C] matrix itself -- post-processing, label reuse.  mode: as in fused_head_predict"""
+    return _head_outputs(model, idx, device, mode, logits=True)[3]
 
 
 def predict(output):
@@ -296,16 +336,19 @@ def train(model, train_idx, labels, device, optimizer, loss_fn="cross_entropy", 
     backward, optimizer.step.  labels: the int64 labels of ALL nodes on `device`.  With a built-in loss one launch gives the loss,
     dLogits and the predictions.  Returns (loss, acc) as Python floats: one host read for both.
     fused_head=True (a LogisticRegression head on pre-propagated features, a built-in loss; ValueError otherwise): the step never
-    forms the logits -- the rows go to linear_cross_entropy, whose backward gives the head's two gradients."""
+    forms the logits -- the rows go to linear_cross_entropy, whose backward gives the head's two gradients.
+    fused_head="in_place" (the same rule, and the processed features must be a float32 or bfloat16 matrix on the device): the same
+    step with the same bits, but the head reads rows train_idx of the stored matrix itself (linear_cross_entropy's `rows`): nothing
+    is gathered or widened first, which is what bf16 hop storage otherwise pays before every step."""
     _check_loss_fn(loss_fn)
     if fused_head:
-        _fused_head(model, loss_fn)
+        _fused_head(model, loss_fn, fused_head)
     device = torch.device(device)
     model.train()
     optimizer.zero_grad()
     y = labels[_as_index(train_idx, labels.device)]
     if fused_head:
-        loss, pred = _fused_loss_and_pred(model, loss_fn, train_idx, y, device)
+        loss, pred = _fused_loss_and_pred(model, loss_fn, train_idx, y, device, fused_head)
     else:
         loss, pred = _loss_and_pred(loss_fn, model.model_forward(train_idx, device), y)
     correct = _correct(pred, y)
@@ -321,14 +364,14 @@ def mini_batch_train(model, train_idx, train_loader, labels, device, optimizer, 
     at the end of the epoch.  fused_head: as in train."""
     _check_loss_fn(loss_fn)
     if fused_head:
-        _fused_head(model, loss_fn)
+        _fused_head(model, loss_fn, fused_head)
     device = torch.device(device)
     model.train()
     losses, correct = [], None
     for batch in train_loader:
         y = labels[_as_index(batch, labels.device)]
         if fused_head:
-            loss, pred = _fused_loss_and_pred(model, loss_fn, batch, y, device)
+            loss, pred = _fused_loss_and_pred(model, loss_fn, batch, y, device, fused_head)
         else:
             loss, pred = _loss_and_pred(loss_fn, model.model_forward(batch, device), y)
         hit = _correct(pred, y)
@@ -344,7 +387,7 @@ def mini_batch_train(model, train_idx, train_loader, labels, device, optimizer, 
 
 
 def _forward_pred(model, idx, device, fused_head=False):
-    return fused_head_predict(model, idx, device) if fused_head else _pred_of(model.model_forward(idx, device))
+    return fused_head_predict(model, idx, device, fused_head) if fused_head else _pred_of(model.model_forward(idx, device))
 
 
 @torch.no_grad()
@@ -426,9 +469,9 @@ def node_classification(model, adj, x, y, train_idx, val_idx, test_idx, epochs, 
     model.preprocess(adj, x)
     model = model.to(device)
     if fused_head:
-        _fused_head(model, loss_fn)
-    forward = (lambda idx: fused_head_logits(model, idx, device)) if fused_head else (lambda idx: model.model_forward(idx, device))
-    head = dict(fused_head=True) if fused_head else {}       # the unfused calls keep the argument lists they have always had
+        _fused_head(model, loss_fn, fused_head)
+    forward = (lambda idx: fused_head_logits(model, idx, device, fused_head)) if fused_head else (lambda idx: model.model_forward(idx, device))
+    head = dict(fused_head=fused_head) if fused_head else {}       # the unfused calls keep the argument lists they have always had
     optimizer = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=weight_decay)
     if mini:
         ordered = {key: batches[key] if key in batches else epoch_batches(idx, eval_batch_size, None, device)

@@ -44,11 +44,11 @@ def add_labels(x, labels, idx, num_classes, out=None, device="cuda"):
 def predict_all(model, n, device, batch_size=None, fused_head=False):
     """model.model_forward over all n nodes (in batches of `batch_size`, the reference's label_reuse_batch_size) -> [n, C] on device.
     fused_head=True (a LogisticRegression head on pre-propagated features; ValueError otherwise): the logits come from the fused
-    head's own kernel (classification.fused_head_logits), not from a torch GEMM."""
+    head's own kernel (classification.fused_head_logits), not from a torch GEMM; "in_place": it reads the stored rows themselves."""
     device = torch.device(device)
     if fused_head:
         from .classification import fused_head_logits
-        forward = lambda idx: fused_head_logits(model, idx, device)   # noqa: E731
+        forward = lambda idx: fused_head_logits(model, idx, device, fused_head)   # noqa: E731
     else:
         forward = lambda idx: model.model_forward(idx, device)        # noqa: E731
     # contiguous row ranges: the hop rows are views of the hop matrices, nothing is gathered (models/base_model.py take_rows)

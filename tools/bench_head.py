@@ -10,7 +10,16 @@ candidates are interleaved in one process, 3 warm-ups + 20 repetitions, HIP even
   (c) evaluation: the arg-max-only launch against F.linear + predict;
   (d) one read of X at the copy ceiling, the yardstick.
 Before timing, the fused outputs of 64 sampled rows are checked against float64 inside the header's bounds.  The comparison point is the
-torch path of the same process; nothing is compared against itself."""
+torch path of the same process; nothing is compared against itself.
+
+    python tools/bench_head.py --in-place [--out profiles/linear_head_rows.json]
+
+The head on stored rows (DESIGN K22) against ITS parent path, gather_rows + K21, in the same process and by the same method: a table
+of N = 2 449 029 rows, float32 and bfloat16, m = 196 615 random rows through a device index and m = N through idx=None (bfloat16
+only: a float32 table without an index is K21's own matrix, and the parent path reads it as a view).  Legs: (a) forward + loss + dZ,
+(b) a whole step -- the gather is part of the parent's step --, (c) evaluation, (d) one read of the gathered bytes m d e, (e) the
+weight gradient on its own: in place against K21's on a copy gathered beforehand (the parent pays for that copy in its forward).
+--rows: the largest entry is the table, every entry a batch size m."""
 import argparse
 import json
 import os
@@ -28,6 +37,7 @@ from sgl_amd.tricks import classification as cl  # noqa: E402
 COPY_CEILING_BYTES_PER_S = 6.29e12
 SHAPES = ((100, 47), (128, 172), (500, 3))
 ROWS = (2449029, 196615)
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "linear_head.json")
 
 
 def timed(fn):
@@ -45,7 +55,7 @@ def stats(ms):
     return {"median": float(np.median(a)), "min": float(a.min()), "max": float(a.max())}
 
 
-def compare(fused, torch_path, args, tag):
+def compare(fused, torch_path, args, tag, names=("fused", "torch")):
     for _ in range(args.warmup):
         fused()
         torch_path()
@@ -55,10 +65,11 @@ def compare(fused, torch_path, args, tag):
         ms_f.append(timed(fused))
         ms_t.append(timed(torch_path))
     sf, st = stats(ms_f), stats(ms_t)
-    r = {"fused_ms": sf, "torch_ms": st, "ratio_fused_over_torch": sf["median"] / st["median"],
+    ratio = sf["median"] / st["median"]
+    r = {f"{names[0]}_ms": sf, f"{names[1]}_ms": st, f"ratio_{names[0]}_over_{names[1]}": ratio,
          "expectation_lower_time": "confirmed" if sf["max"] < st["min"] else ("refuted" if sf["min"] > st["max"] else "undecided")}
-    print(f"EXP head {tag}: fused {sf['median']:.3f} ms ({sf['min']:.3f}-{sf['max']:.3f}), torch {st['median']:.3f} ms "
-          f"({st['min']:.3f}-{st['max']:.3f}), ratio {r['ratio_fused_over_torch']:.3f} {r['expectation_lower_time']}", flush=True)
+    print(f"EXP head {tag}: {names[0]} {sf['median']:.3f} ms ({sf['min']:.3f}-{sf['max']:.3f}), {names[1]} {st['median']:.3f} ms "
+          f"({st['min']:.3f}-{st['max']:.3f}), ratio {ratio:.3f} {r['expectation_lower_time']}", flush=True)
     return r
 
 
@@ -115,16 +126,81 @@ def one_shape(n, d, c, args):
     return out
 
 
+def one_table(n_rows, m, d, c, dtype, args):
+    """the in-place head on rows of a stored table against gather_rows + K21"""
+    dev_ = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev_).manual_seed(args.seed)
+    table = dev.alloc_rows(n_rows, d, dev_, dtype=dtype)
+    table.copy_(torch.randn((n_rows, d), generator=gen, device=dev_))
+    idx = None if m == n_rows else torch.randint(0, n_rows, (m,), generator=gen, device=dev_)
+    at = torch.arange(n_rows, device=dev_) if idx is None else idx       # the parent's index lives on the device too: no upload is timed
+    lin = torch.nn.Linear(d, c).to(dev_)
+    w, b = lin.weight, lin.bias
+    wd, bd = w.detach(), b.detach()
+    y = torch.randint(0, c, (m,), generator=gen, device=dev_)
+    dz_buf = dev.alloc_rows(m, c, dev_)
+    dz, loss, pred, _ = dev.linear_class_loss_rows(table, idx, wd, bd, y, 1.0, dz=dz_buf, row_loss=True, pred=True)
+    check_sample(dev.gather_rows(table, at), wd, bd, y, dz, loss, pred)
+    names = ("in_place", "gathered")
+    tag = f"n_rows={n_rows} m={m} d={d} C={c} {str(dtype).replace('torch.', '')}"
+    out = {"n_rows": n_rows, "m": m, "index": "none" if idx is None else "random", "d": d, "c": c, "dtype": str(dtype).replace("torch.", "")}
+    out["a_forward_loss_dz"] = compare(lambda: dev.linear_class_loss_rows(table, idx, wd, bd, y, 1.0, dz=dz_buf, row_loss=True, pred=True),
+                                       lambda: dev.linear_class_loss(dev.gather_rows(table, at), wd, bd, y, 1.0, dz=dz_buf, row_loss=True, pred=True),
+                                       args, f"(a) {tag}", names)
+
+    def step(in_place):
+        lin.zero_grad(set_to_none=True)
+        if in_place:
+            loss_ = cl.linear_cross_entropy(table, w, b, y, check=False, rows=range(n_rows) if idx is None else idx)
+        else:
+            loss_ = cl.linear_cross_entropy(dev.gather_rows(table, at), w, b, y, check=False)
+        loss_.backward()
+        return loss_
+
+    out["b_whole_step"] = compare(lambda: step(True), lambda: step(False), args, f"(b) {tag}", names)
+    out["c_evaluation"] = compare(lambda: dev.linear_class_loss_rows(table, idx, wd, bd, None, 1.0, pred=True),
+                                  lambda: dev.linear_class_loss(dev.gather_rows(table, at), wd, bd, None, 1.0, pred=True), args, f"(c) {tag}", names)
+    out["d_one_read_of_the_rows_ms"] = m * d * table.element_size() / COPY_CEILING_BYTES_PER_S * 1e3
+    g = dev.gather_rows(table, at)                                       # not timed: the parent's forward made this copy
+    out["e_weight_gradient"] = compare(lambda: dev.linear_wgrad_rows(table, idx, dz_buf), lambda: dev.linear_wgrad(g, dz_buf), args, f"(e) {tag}",
+                                       names)
+    return out
+
+
+def main_in_place(args):
+    sizes = sorted({int(n) for n in args.rows.split(",")})
+    n_rows = sizes[-1]
+    results = [one_table(n_rows, m, d, c, dtype, args) for dtype in (torch.float32, torch.bfloat16) for m in sizes for d, c in SHAPES
+               if not (dtype == torch.float32 and m == n_rows)]
+    doc = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "copy_ceiling_bytes_per_s": COPY_CEILING_BYTES_PER_S,
+           "protocol": "legs interleaved in one process, HIP events, median (min - max); in-place outputs of 64 sampled rows checked against "
+                       "float64 first; the comparison point is gather_rows + K21 of the same process, its index on the device",
+           "expectation": "fewer bytes (2 m d e against m d e + 12 m d), hence a lower time in (b) and (c)",
+           "not_measured": ["hardware counters (FETCH bytes, L2 hit rates of the random rows)", "sorted or clustered index lists",
+                            "mini-batches below 196 615 rows", "C > 172",
+                            "host index lists (their upload is the same on both sides; for a bfloat16 full pass the parent uploads N indices per "
+                            "call, which the in-place path does not)",
+                            "a float32 table without an index (K21's own instance)", "the in-place step inside node_classification end to end"],
+           "results": results}
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "linear_head_rows.json")
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--in-place", action="store_true", help="measure the head on stored rows (K22) against gather_rows + K21")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--rows", default=",".join(str(n) for n in ROWS))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linear_head.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     args = ap.parse_args()
     _lib.require_gpu()
     torch.cuda.set_device(0)
+    if args.in_place:
+        return main_in_place(args)
     results = [one_shape(int(n), d, c, args) for n in args.rows.split(",") for d, c in SHAPES]
     doc = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "copy_ceiling_bytes_per_s": COPY_CEILING_BYTES_PER_S,
            "protocol": "legs interleaved in one process, HIP events, median (min - max); fused outputs of 64 sampled rows checked against float64 first",
