@@ -24,13 +24,17 @@ from sgl_amd.tricks import classification as cl  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nodes", type=int, default=19717)
-    ap.add_argument("--feat", type=int, default=500)
+    ap.add_argument("--feat", type=int, default=None, help="default 500; 200 with --one-pass")
     ap.add_argument("--classes", type=int, default=3)
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--prop-steps", type=int, default=3)
     ap.add_argument("--in-place", action="store_true", help="also run fused_head='in_place' and compare its bits with fused_head=True")
+    ap.add_argument("--one-pass", action="store_true",
+                    help="also run fused_head='one_pass' and 'one_pass_in_place' (DESIGN K23: loss, dW and db from one read of the rows) and "
+                         "compare their weights with fused_head=True; --feat then defaults to 200, inside sgl_linear_step_rule")
     ap.add_argument("--hop-dtype", default="float32", choices=("float32", "bfloat16"))
     a = ap.parse_args()
+    a.feat = a.feat or (200 if a.one_pass else 500)
     device = torch.device("cuda")
     config.hop_dtype = a.hop_dtype
     adj, y = planted_graph(a.nodes, a.classes, 5, 0.8, seed=0)
@@ -42,7 +46,7 @@ def main():
 
     first = SGC(prop_steps=a.prop_steps, feat_dim=a.feat, output_dim=a.classes)
     weights = {}
-    for fused in (True, False) + (("in_place",) if a.in_place else ()):
+    for fused in (True, False) + (("in_place",) if a.in_place else ()) + (("one_pass", "one_pass_in_place") if a.one_pass else ()):
         model = copy.deepcopy(first)
         model.preprocess(adj, x)
         model.to(device)
@@ -55,6 +59,11 @@ def main():
         assert test > 1.5 / a.classes, "SGC failed to learn the planted communities"
     if a.in_place:
         assert torch.equal(weights[True], weights["in_place"]), "the in-place head must give the bits of the fused head"
+    if a.one_pass:                                      # another order of the rows in dW: close, not bit-equal
+        assert torch.equal(weights["one_pass"], weights["one_pass_in_place"]), "the stored rows must give the bits of the gathered rows"
+        gap = float((weights["one_pass"] - weights[True]).abs().max() / weights[True].abs().max())
+        print(f"fused_head='one_pass': weights within {gap:.2e} (relative to the largest weight) of fused_head=True")
+        assert gap < 1e-2, "the one-pass head drifted from the fused head"
 
 
 if __name__ == "__main__":

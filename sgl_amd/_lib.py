@@ -232,6 +232,16 @@ LINEAR_ROWS_PROTOTYPES = {
     "sgl_linear_wgrad_rows_bf16": _WGRAD_ROWS,
 }
 
+# include/sgl_linear_step.h: K23, the head's training step in one pass over X (loss, dW and db) -- a header and a table of their own
+_STEP_TAIL = [c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]
+LINEAR_STEP_PROTOTYPES = {
+    "sgl_linear_step_rule": (c_int, [c_int64, c_int64, c_int64, POINTER(c_int64)]),
+    "sgl_linear_step_scratch": (c_int64, [c_int64, c_int64, c_int64]),
+    "sgl_linear_step_f32": (c_int, [c_void_p, c_int64, c_int64, *_STEP_TAIL]),
+    "sgl_linear_step_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, *_STEP_TAIL]),
+    "sgl_linear_step_rows_bf16": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, *_STEP_TAIL]),
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -263,7 +273,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items(),
                                   *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items(), *KMEANS_SEED_PROTOTYPES.items(),
-                                  *LINEAR_HEAD_PROTOTYPES.items(), *LINEAR_ROWS_PROTOTYPES.items()):
+                                  *LINEAR_HEAD_PROTOTYPES.items(), *LINEAR_ROWS_PROTOTYPES.items(), *LINEAR_STEP_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -33,23 +33,14 @@
 // widened rows.  In flight per wavefront and look-ahead step (kStep = 32 columns): 4 R row loads per lane, 16 bytes each for float32
 // (R x 4 KiB per wavefront), 8 bytes each for bfloat16 (R x 2 KiB).  The lane width of W is a run-time flag here (staging is once per
 // workgroup), so a table's wide lanes do not depend on W's pitch as they do in K21.
-#include <climits>
-#include <cmath>
+#include "sgl_linear_common.h"   // the row source, the staging of W, the chain, the epilogue, the block rule and the fold: shared with K23
 
-#include "sgl_rows.h"   // f4, edge_load, store_cols, with_vec, with_chunks, SGL_LAUNCH_CHECK
-
-#include "../../include/sgl_linear_head.h"
 #include "../../include/sgl_linear_rows.h"
 
 namespace {
 
-using f16v = float __attribute__((ext_vector_type(16)));
-
-constexpr int kMaxBlocks = 2048;                     // K9's cap: 256 CUs x 8 resident workgroups, the batches beyond are strided over
 constexpr int kTileFloats = 16384;                   // LDS of a workgroup of linear_class_kernel: 64 KiB
-constexpr int kPitchPad = 4;                         // floats: makes pitch / 4 odd
 constexpr int kStep = 32;                            // columns of X a lane pair takes per step: 4 vectors in each half
-constexpr int kNoIndex = INT32_MAX;                  // "no candidate" of the index minimum
 
 constexpr int row_tiles(int nt) { return nt <= 4 ? 2 : 1; }   // R: 2 x NT x 16 accumulator registers stay within 128
 
@@ -68,76 +59,6 @@ bool class_rule(int64_t d, int64_t c, ClassRule &out) {
     if (c * (dp + kPitchPad) > budget) w = (budget / c - kPitchPad) / 8 * 8;   // >= 48 at c = 256
     out = {nt, row_tiles(nt), (int)w, (int)w + kPitchPad};
     return true;
-}
-
-// columns col .. col + 3 of a row, zeros from column d on; col < d.  VEC = 1: the four elements one by one
-template <int VEC>
-__device__ __forceinline__ f4 load4(const float *__restrict__ p, const int col, const int d, const bool last_row) {
-    if constexpr (VEC == 4) {
-        return edge_load<4>(p, col, d, last_row);
-    } else {
-        f4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? p[col + e] : 0.f;
-        return v;
-    }
-}
-
-// the same of a bfloat16 row, widened exactly.  VEC = 4: one 8-byte access where it stays inside the row's d columns or (not the table's
-// last row) inside its pitch
-__device__ __forceinline__ float widen(const uint16_t v) { return __uint_as_float((uint32_t)v << 16); }
-template <int VEC>
-__device__ __forceinline__ f4 load4(const uint16_t *__restrict__ p, const int col, const int d, const bool last_row) {
-    f4 v;
-    if (VEC == 4 && (col + 4 <= d || !last_row)) {
-        const uint2 u = *reinterpret_cast<const uint2 *>(p + col);
-        v = f4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
-#pragma unroll
-        for (int e = 1; e < 4; ++e)
-            if (col + e >= d) v[e] = 0.f;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? widen(p[col + e]) : 0.f;
-    }
-    return v;
-}
-__device__ __forceinline__ float widen(const float v) { return v; }
-
-// ROWS: the table row a batch row reads -- idx[row] (NULL: row itself), negative ones count from the end; `bad`: outside [-n_rows, n_rows),
-// the row then reads as NaN and row 0 stands in for its address
-__device__ __forceinline__ int64_t source_row(const int64_t *__restrict__ idx, const int64_t row, const int64_t n_rows, bool &bad) {
-    int64_t s = idx ? idx[row] : row;
-    if (s < 0) s += n_rows;
-    bad = s < 0 || s >= n_rows;
-    return bad ? 0 : s;
-}
-
-// columns c0 .. c0 + wc - 1 of the c rows of W into the tile, zeros from column d on: one wavefront per row
-template <int VEC>
-__device__ __forceinline__ void stage_weights(float *__restrict__ tile, const float *__restrict__ wt, const int64_t ldw, const int c,
-                                              const int d, const int c0, const int wc, const int p) {
-    const int lane = threadIdx.x % 64;
-    for (int j = threadIdx.x / 64; j < c; j += 4) {
-        const float *wrow = wt + (int64_t)j * ldw;
-        for (int lc = lane * 4; lc < wc; lc += 256) {
-            const int col = c0 + lc;
-            f4 v = {0.f, 0.f, 0.f, 0.f};
-            if (col < d) v = load4<VEC>(wrow, col, d, j == c - 1);
-            *reinterpret_cast<f4 *>(tile + j * p + lc) = v;
-        }
-    }
-}
-
-__device__ __forceinline__ int imin(const int a, const int b) { return a < b ? a : b; }
-// the two halves' values of a lane pair: [0] is half 0's in both lanes, [1] half 1's
-__device__ __forceinline__ auto halves(const unsigned v) { return __builtin_amdgcn_permlane32_swap(v, v, false, false); }
-__device__ __forceinline__ float halves_sum(const float v) {
-    const auto r = halves(__float_as_uint(v));
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ int halves_min(const int v) {
-    const auto r = halves((unsigned)v);
-    return imin((int)r[0], (int)r[1]);
 }
 
 // <float, false>: K21, row i of x [n, d].  ROWS: batch row i is row idx[i] of the table x [n_rows, d] of T; VEC is x's lane width alone
@@ -200,10 +121,7 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const T *__restrict__
                         f4 v = {0.f, 0.f, 0.f, 0.f};
                         if (q0 + 8 * t < wc && in[r] && col < d) v = load4<VEC>(xp[r], col, d, last[r]);
                         if constexpr (ROWS) {
-                            if (bad[r]) {            // a row of NaN in its d columns: every logit of the row is NaN, nothing traps
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = (col + e < d) ? __uint_as_float(0x7fc00000u) : 0.f;
-                            }
+                            if (bad[r]) v = nan_cols(col, d);
                         }
                         xr[r][t] = v;
                     }
@@ -211,17 +129,10 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const T *__restrict__
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     if (q0 + 8 * t < wc) {           // the same for every lane
-                        const int lc = q0 + 8 * t + 4 * h;
+                        f4 xv[R];
 #pragma unroll
-                        for (int ct = 0; ct < NT; ++ct) {
-                            const int j = ct * 32 + i;
-                            f4 a = *reinterpret_cast<const f4 *>(tile + (j < c ? j : c - 1) * p + lc);
-                            if (j >= c) a = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                                for (int r = 0; r < R; ++r) acc[r][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], xr[r][t][e], acc[r][ct], 0, 0, 0);
-                        }
+                        for (int r = 0; r < R; ++r) xv[r] = xr[r][t];
+                        logit_group<NT, R>(acc, tile, p, c, i, q0 + 8 * t + 4 * h, xv);
                     }
                 }
             }
@@ -229,58 +140,8 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const T *__restrict__
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int64_t row = (b * 4 * R + wave * R + r) * 32 + i;
-            // this lane's logits in ascending class order: the bias, the logits out, K14's candidates
-            float top = -INFINITY;
-            int at = kNoIndex, nan_at = kNoIndex;
-#pragma unroll
-            for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int j0 = ct * 32 + 8 * g + 4 * h;
-                    const f4 bb = *reinterpret_cast<const f4 *>(bs + j0);
-                    f4 run;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = acc[r][ct][4 * g + e] + bb[e];
-                        acc[r][ct][4 * g + e] = run[e] = v;
-                        if (j0 + e < c) {
-                            if (v != v) {
-                                if (nan_at == kNoIndex) nan_at = j0 + e;
-                            } else if (at == kNoIndex || v > top) {
-                                top = v;
-                                at = j0 + e;
-                            }
-                        }
-                    }
-                    if (z && in[r] && j0 < c) store_cols<4>(z + row * ldz, j0, c, run, z_vec);
-                }
-            const auto tt = halves(__float_as_uint(top));
-            const float m = fmaxf(__uint_as_float(tt[0]), __uint_as_float(tt[1]));   // of the entries that are not NaN
-            if (pred) {
-                const int first_nan = halves_min(nan_at);
-                const int first_top = halves_min((at != kNoIndex && top == m) ? at : kNoIndex);
-                if (in[r] && h == 0) pred[row] = first_nan != kNoIndex ? first_nan : first_top;
-            }
-            if (!want_exp) continue;                 // (uniform: the same for every lane of the launch)
-            const int64_t label = in[r] ? labels[row] : -1;
-            const bool live = label >= 0 && label < c;
-            const int y = live ? (int)label : -1;
-            float part = 0.f, zy = 0.f;
-#pragma unroll
-            for (int ct = 0; ct < NT; ++ct)
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    const int j = ct * 32 + 8 * (v / 4) + 4 * h + v % 4;
-                    const float lz = acc[r][ct][v];
-                    const float ex = j < c ? expf(lz - m) : 0.f;
-                    zy = j == y ? lz : zy;
-                    acc[r][ct][v] = ex;
-                    part += ex;
-                }
-            const float s = halves_sum(part);
-            zy = halves_sum(zy);                     // the other half holds 0: exact
-            if (!in[r]) continue;
-            if (row_loss && h == 0) row_loss[row] = live ? (m + logf(s)) - zy : 0.f;
+            const RowState st = class_epilogue<NT>(acc[r], bs, c, h, in[r], row, labels, want_exp, row_loss, pred, z, ldz, z_vec);
+            if (!want_exp || !in[r]) continue;
             if (dz) {
                 float *orow = dz + row * lddz;
 #pragma unroll
@@ -290,7 +151,7 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const T *__restrict__
                         const int j0 = ct * 32 + 8 * g + 4 * h;
                         f4 o;
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] = live ? wgt * (acc[r][ct][4 * g + e] / s - (j0 + e == y ? 1.f : 0.f)) : 0.f;
+                        for (int e = 0; e < 4; ++e) o[e] = dz_value(st, wgt, acc[r][ct][4 * g + e], j0 + e);
                         if (j0 < c) store_cols<4>(orow, j0, c, o, dz_vec);
                     }
             }
@@ -299,31 +160,7 @@ __global__ __launch_bounds__(256) void linear_class_kernel(const T *__restrict__
 }
 
 // ---- the weight gradient -------------------------------------------------------------------------------------------------------------
-constexpr int kTiles = 8;                            // 32 x 32 accumulator tiles per wavefront: 128 registers
-constexpr int kTableFloats = kTiles * 1024;          // one workgroup's table: 32 KiB
 constexpr int kPairs = 8;                            // row pairs a wavefront loads before their MFMA steps
-constexpr int kRowsPerClass = 40;                    // R >= 40 C (d + 1) / d: the tables, 2 C (d + 1) floats per block, are <= 5 % of X
-constexpr int kFold = 32;                            // tables in flight per thread of the fold
-
-struct WgradRule {
-    int64_t blocks, rows;                            // B, R
-    int ct, ut, slabs;                               // class tiles x column tiles of a slab, S
-};
-bool wgrad_rule(int64_t n, int64_t d, int64_t c, WgradRule &out) {
-    if (c > SGL_LINEAR_HEAD_MAX_C) return false;
-    const int ct = c <= 32 ? 1 : (c <= 64 ? 2 : (c <= 128 ? 4 : 8)), ut = kTiles / ct;
-    const int64_t tu = (d + 1 + 31) / 32;
-    out = {0, 0, ct, ut, (int)((tu + ut - 1) / ut)};
-    if (n == 0 || c == 0) return true;
-    const int64_t forced = sgl::tuning("loss_blocks", 0);
-    const int64_t rmin = d ? (kRowsPerClass * c * (d + 1) + d - 1) / d : kRowsPerClass * c;
-    int64_t want = forced > 0 ? forced : (n / rmin > 1 ? n / rmin : 1);
-    if (want > kMaxBlocks) want = kMaxBlocks;
-    if (want > n) want = n;
-    out.rows = (n + want - 1) / want;
-    out.blocks = (n + out.rows - 1) / out.rows;
-    return true;
-}
 
 // <float, false>: K21.  ROWS: row `row` of dz meets row idx[row] of the table x [n_rows, d] of T -- the same for a whole half-wave,
 // resolved once per pair; 2-byte reads for bfloat16 (64 bytes per half-wave and row), widened exactly
@@ -384,54 +221,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const T *__restrict__
             }
         }
     }
-    // ((wave 0 + wave 1) + wave 2) + wave 3 in LDS; element (tile, v, lane) at tile * 1024 + v * 64 + lane: consecutive lanes, no conflict
-    for (int turn = 0; turn < 4; ++turn) {
-        if (wave == turn) {
-#pragma unroll
-            for (int t = 0; t < CT; ++t)
-#pragma unroll
-                for (int u = 0; u < UT; ++u)
-                    if (t < tiles_c && u < tiles_u) {
-#pragma unroll
-                        for (int v = 0; v < 16; ++v) {
-                            float *at = table + (t * UT + u) * 1024 + v * 64 + lane;
-                            *at = turn ? *at + acc[t][u][v] : acc[t][u][v];
-                        }
-                    }
-        }
-        __syncthreads();
-    }
-    // the table as [32 CT classes][32 UT columns]; only classes < c and columns <= d are written (and read by the fold)
-    float *out = part + (int64_t)blockIdx.x * kTableFloats;
-    for (int e = threadIdx.x; e < kTableFloats; e += 256) {
-        const int tile = e / 1024, v = e / 64 % 16, l = e % 64, t = tile / UT, u = tile % UT;
-        const int jl = 32 * t + 8 * (v / 4) + 4 * (l / 32) + v % 4, cl = 32 * u + l % 32;
-        if (jl < c && 32 * u0 + cl <= d) out[jl * (32 * UT) + cl] = table[e];
-    }
-}
-
-// dw[j, col] / db[j] = the B tables' values in ascending block order, one float32 add each; kFold loads are issued before their adds
-__global__ __launch_bounds__(256) void linear_fold_kernel(const float *__restrict__ part, const int64_t blocks, const int slabs, const int ut,
-                                                          const int c, const int d, float *__restrict__ dw, const int64_t lddw,
-                                                          float *__restrict__ db) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)c * (d + 1)) return;
-    const int64_t j = idx / (d + 1);
-    const int col = (int)(idx % (d + 1)), s = col / (32 * ut);
-    const float *p = part + (int64_t)s * kTableFloats + j * (32 * ut) + (col - s * 32 * ut);
-    const int64_t stride = (int64_t)slabs * kTableFloats;
-    float a = 0.f;
-    int64_t b = 0;
-    for (; b + kFold <= blocks; b += kFold) {
-        float t[kFold];
-#pragma unroll
-        for (int e = 0; e < kFold; ++e) t[e] = p[(b + e) * stride];
-#pragma unroll
-        for (int e = 0; e < kFold; ++e) a = a + t[e];
-    }
-    for (; b < blocks; ++b) a = a + p[b * stride];
-    if (col < d) dw[j * lddw + col] = a;
-    else if (db) db[j] = a;
+    add_wavefront_tables<CT, UT>(table, acc, tiles_c, tiles_u, u0, c, d, part + (int64_t)blockIdx.x * kTableFloats);
 }
 
 int check_wgrad(const char *who, int64_t n, int64_t d, int64_t c, WgradRule &rule) {
@@ -582,12 +372,7 @@ int linear_wgrad(const char *who, const T *d_x, int64_t ldx, int64_t n_rows, con
         });
         SGL_LAUNCH_CHECK(who);
     }
-    const int64_t cells = c * (d + 1);
-    if (!sgl::launch_fits((cells + 255) / 256, 256)) return sgl::fail(SGL_ERR_UNSUPPORTED, "%s: the grid does not fit one launch", who);
-    hipLaunchKernelGGL(linear_fold_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, part, rule.blocks, rule.slabs, rule.ut, ci,
-                       di, d_dw, lddw, d_db);
-    SGL_LAUNCH_CHECK(who);
-    return SGL_OK;
+    return launch_fold(who, st, part, rule.blocks, rule.slabs, rule.ut, ci, di, d_dw, lddw, d_db);
 }
 
 }  // namespace

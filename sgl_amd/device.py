@@ -52,7 +52,8 @@ def _esize(dtype):
 _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy", "sgl_chain_graph_create", "sgl_chain_graph_destroy",
                         "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule",
                         "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch", "sgl_kmeans_seed_rule", "sgl_kmeans_seed_scratch",
-                        "sgl_linear_class_rule", "sgl_linear_wgrad_rule", "sgl_linear_wgrad_scratch"})
+                        "sgl_linear_class_rule", "sgl_linear_wgrad_rule", "sgl_linear_wgrad_scratch",
+                        "sgl_linear_step_rule", "sgl_linear_step_scratch"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2427,6 +2428,74 @@ def _linear_wgrad(who, kind, x, idx, dz):
     else:
         _call(x.device, "sgl_linear_wgrad_f32", ptr(x), _ld(x), n, d, *tail)
     return dw, db
+
+
+def linear_step_rule(n, d, c):
+    """(B, R, class tiles, column tiles, LDS bytes) of sgl_linear_step_rule (include/sgl_linear_step.h) for a batch of n rows, d
+    columns and c classes; ValueError, quoting the rule, for a shape the one-pass step does not serve.  Host only."""
+    out = (ctypes.c_int64 * 5)()
+    if lib().sgl_linear_step_rule(int(n), int(d), int(c), out) != 0:     # host only: no device is touched
+        raise ValueError(f"linear_step: {_lib.last_error()}")
+    return tuple(int(v) for v in out)
+
+
+def linear_step(x, weight, bias, labels, w, row_loss=True, pred=False):
+    """The whole training step of a linear head from ONE read of x (sgl_linear_step_f32, include/sgl_linear_step.h): the logits, their
+    loss and dLogits stay on chip, and dW = dLogits^T x [C, d] and db [C] come out of the same pass -- a partial table per row block,
+    then the ordered fold of linear_wgrad.  Arguments and ValueErrors as in linear_class_loss (labels is required); row_loss / pred:
+    True allocates, a tensor is written in place, None / False leaves it out.  A shape outside sgl_linear_step_rule (C <= 32 up to
+    d = 222, C <= 64 up to d = 127, C <= 128 up to d = 63) raises ValueError: nothing falls back.  row_loss and pred are bit-equal to linear_class_loss; no
+    atomics, two runs are bit-equal.  Returns (dW, db, row_loss, pred).  The scratch is a tensor of this call."""
+    return _linear_step("linear_step", None, x, None, weight, bias, labels, w, row_loss, pred)
+
+
+def linear_step_rows(x, idx, weight, bias, labels, w, row_loss=True, pred=False):
+    """linear_step on the rows x[idx] of a stored float32 or bfloat16 table without gathering them (sgl_linear_step_rows_f32 / _bf16):
+    x, idx as in linear_class_loss_rows.  Bit for bit what linear_step(gather_rows(x, idx), ...) gives."""
+    who = "linear_step_rows"
+    kind = _table(who, x, weight, bias)
+    return _linear_step(who, kind, x, _table_index(idx, x), weight, bias, labels, w, row_loss, pred)
+
+
+def _linear_step(who, kind, x, idx, weight, bias, labels, w, row_loss, pred):
+    try:
+        if kind is None:
+            _refuse_bf16(who, x, weight, bias)
+            _check_mat(x, "x")
+        _check_mat(weight, "weight")
+    except TypeError as e:
+        raise ValueError(f"{who}: {e}") from None
+    if x.shape[1] != weight.shape[1] or x.device != weight.device:
+        raise ValueError(f"{who}: x and weight must have the same row length and live on one device")
+    n, d, c = (x.shape[0] if idx is None else idx.numel()), x.shape[1], weight.shape[0]
+    if c < 1:
+        raise ValueError(f"{who}: at least one class is needed")
+    if c > LINEAR_HEAD_MAX_C:
+        raise ValueError(f"{who}: at most {LINEAR_HEAD_MAX_C} classes, got {c}")
+    nbytes = int(_call(None, "sgl_linear_step_scratch", n, d, c, raw=True))
+    if nbytes < 0:
+        raise ValueError(f"{who}: {_lib.last_error()}")
+    if bias is not None:
+        _row_vector(who, "bias", bias, c, torch.float32, x)
+    _row_vector(who, "labels", labels, n, torch.int64, x)
+    row_loss, pred = (None if t is False else t for t in (row_loss, pred))
+    row_loss = torch.empty(n, dtype=torch.float32, device=x.device) if row_loss is True else row_loss
+    pred = torch.empty(n, dtype=torch.int64, device=x.device) if pred is True else pred
+    if row_loss is not None:
+        _row_vector(who, "row_loss", row_loss, n, torch.float32, x)
+    if pred is not None:
+        _row_vector(who, "pred", pred, n, torch.int64, x)
+    dw = torch.empty((c, d), dtype=torch.float32, device=x.device)
+    db = torch.empty(c, dtype=torch.float32, device=x.device)
+    scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    tail = (d, ptr(weight), _ld(weight), c, _opt_ptr(bias), ptr(labels), float(w), _opt_ptr(row_loss), _opt_ptr(pred), ptr(dw), max(d, 1),
+            ptr(db), ptr(scratch))
+    if kind:
+        _call(x.device, f"sgl_linear_step_rows_{kind}", ptr(x), _ld(x), x.shape[0], _opt_ptr(idx), n, *tail)
+    else:
+        _call(x.device, "sgl_linear_step_f32", ptr(x), _ld(x), n, *tail)
+    _wrote(row_loss, pred)
+    return dw, db, row_loss, pred
 
 
 def gather_rows(x, idx, out=None):

@@ -174,7 +174,37 @@ class _LinearCrossEntropy(torch.autograd.Function):
         return (dx, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
 
 
-def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index=-100, check=True, return_pred=False, rows=None):
+class _LinearStepCrossEntropy(torch.autograd.Function):
+    """_LinearCrossEntropy in one pass over x (device.linear_step, include/sgl_linear_step.h): the forward launch leaves the loss, the
+    predictions AND dweight, dbias; dLogits never exists, so the backward launches nothing -- it scales the two kept gradients by the
+    upstream gradient -- and x gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels, w, scale, want_pred, in_place=False, rows=None):
+        if in_place:
+            dw, db, row_loss, pred = dev.linear_step_rows(x, rows, weight, bias, labels, w, row_loss=True, pred=want_pred)
+        else:
+            dw, db, row_loss, pred = dev.linear_step(x, weight, bias, labels, w, row_loss=True, pred=want_pred)
+        ctx.grads, ctx.scale = (dw, db), scale
+        loss = (row_loss.sum(dtype=torch.float64) * (w if scale is None else scale)).to(torch.float32)
+        if want_pred:
+            ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _):
+        grads, ctx.grads = ctx.grads, None
+        if grads is None:
+            raise RuntimeError("linear_cross_entropy: backward ran twice; the gradients of the forward launch were handed out the first time")
+        if ctx.scale is not None:
+            g = (g * ctx.scale).to(torch.float32)
+        dw, db = grads[0].mul_(g), grads[1].mul_(g)
+        return (None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None, None, None, None, None, None, None)
+
+
+def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index=-100, check=True, return_pred=False, rows=None,
+                         one_pass=False):
     """cross_entropy(F.linear(x, weight, bias), labels, ...) -- its value, its label semantics (ignore_index, check, the mean over no
     live row is NaN) and its gradients -- without the [n, C] logits: ONE launch (device.linear_class_loss -> sgl_linear_class_f32,
     csrc/sgl_linear_head.hip) forms the logits on the matrix cores and writes the per-row losses, the arg-max when return_pred=True and,
@@ -186,7 +216,12 @@ def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index
     rows (anything device.gather_rows takes): x is a stored TABLE, float32 or bfloat16, and the batch its rows x[rows], read where they
     are stored (device.linear_class_loss_rows, device.linear_wgrad_rows; include/sgl_linear_rows.h) -- labels has len(rows) entries, the
     backward keeps the table and the index instead of a copy of the batch, and every bit is that of the call on gather_rows(x, rows).
-    A table that requires grad is refused (there is no dX in place)."""
+    A table that requires grad is refused (there is no dX in place).
+    one_pass=True (opt-in; include/sgl_linear_step.h): when weight or bias wants a gradient, the forward is ONE launch that reads x once
+    and also leaves dweight and dbias (device.linear_step / linear_step_rows); the backward scales them and launches nothing.  The loss
+    and pred keep their bits; the gradients are within the header's bound, in another order of the rows than linear_wgrad's.  x must
+    not require grad (ValueError: no dLogits exists to form dx from), and (d, C) must be inside sgl_linear_step_rule (ValueError).
+    Without a gradient wanted the call is what it is with one_pass=False."""
     if reduction not in ("mean", "sum"):
         raise ValueError("linear_cross_entropy: reduction must be 'mean' or 'sum'")
     if not (torch.is_tensor(x) and x.dim() == 2 and torch.is_tensor(weight) and weight.dim() == 2 and weight.shape[0] >= 1):
@@ -205,7 +240,11 @@ def linear_cross_entropy(x, weight, bias, labels, reduction="mean", ignore_index
         else:
             scale = 1.0 / live.to(torch.float64)
     params = [t for t in (x, weight, bias) if t is not None]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in params):
+    if one_pass and torch.is_grad_enabled() and any(t.requires_grad for t in params):
+        if x.requires_grad:
+            raise ValueError("linear_cross_entropy: one_pass=True forms no dLogits, so x gets no gradient; detach it")
+        loss, pred = _LinearStepCrossEntropy.apply(x, weight, bias, y, w, scale, bool(return_pred), in_place, rows)
+    elif torch.is_grad_enabled() and any(t.requires_grad for t in params):
         loss, pred = _LinearCrossEntropy.apply(x, weight, bias, y, w, scale, bool(return_pred), in_place, rows)
     else:
         head = (weight.detach(), None if bias is None else bias.detach(), y, w)
@@ -219,11 +258,13 @@ def _fused_head(model, loss_fn="cross_entropy", mode=True):
     """the nn.Linear of a model whose step can run on the fused head -- an SGAP model with a LogisticRegression head behind a message
     operator that is not learnable -- and ValueError for everything else (and for a callable loss): fused_head=True never falls back.
     mode "in_place" (the head reads the rows where they are stored, include/sgl_linear_rows.h): the processed features must also be a
-    float32 or bfloat16 matrix on the device"""
+    float32 or bfloat16 matrix on the device.  "one_pass" / "one_pass_in_place": the training step of True / "in_place" as one pass
+    over the rows (include/sgl_linear_step.h); everything else of the mode is that of True / "in_place".
+    """
     from ..models.base_model import BaseSGAPModel
     from ..models.simple_models import LogisticRegression
-    if mode is not True and mode != "in_place":
-        raise ValueError(f"fused_head must be False, True or 'in_place', not {mode!r}")
+    if mode is not True and mode not in ("in_place", "one_pass", "one_pass_in_place"):
+        raise ValueError(f"fused_head must be False, True, 'in_place', 'one_pass' or 'one_pass_in_place', not {mode!r}")
     if not isinstance(loss_fn, str):
         raise ValueError("fused_head=True needs a built-in loss ('cross_entropy' or 'loge'), not a callable")
     if not (isinstance(model, BaseSGAPModel) and isinstance(model._base_model, LogisticRegression)):
@@ -232,9 +273,16 @@ def _fused_head(model, loss_fn="cross_entropy", mode=True):
         raise ValueError("fused_head=True needs pre-propagated features behind a message operator that is not learnable "
                          "(call model.preprocess first)")
     feat = model._processed_feature
-    if mode == "in_place" and not (torch.is_tensor(feat) and feat.is_cuda and feat.dim() == 2 and feat.dtype in (torch.float32, torch.bfloat16)):
-        raise ValueError("fused_head='in_place' needs the processed features as a float32 or bfloat16 matrix on the device")
-    return model._base_model.linear
+    if _reads_in_place(mode) and not (torch.is_tensor(feat) and feat.is_cuda and feat.dim() == 2 and feat.dtype in (torch.float32, torch.bfloat16)):
+        raise ValueError(f"fused_head={mode!r} needs the processed features as a float32 or bfloat16 matrix on the device")
+    fc = model._base_model.linear
+    if mode in ("one_pass", "one_pass_in_place"):
+        dev.linear_step_rule(1, fc.in_features, fc.out_features)       # ValueError, quoting the rule, before any work
+    return fc
+
+
+def _reads_in_place(mode):
+    return mode in ("in_place", "one_pass_in_place")
 
 
 def _head_rows(model, idx, device):
@@ -249,13 +297,13 @@ def _head_rows(model, idx, device):
 def _head_input(model, idx, device, mode):
     """(x, rows) of the head's calls: the gathered float32 rows and None, or ("in_place") the stored table and the index into it as
     the caller gave it (a range over all its rows is "every row in order" to the *_rows calls); take_rows is not called"""
-    if mode != "in_place":
+    if not _reads_in_place(mode):
         return _head_rows(model, idx, device), None
     table, want = model._processed_feature, torch.device(device)
     if want.type == "cuda" and want.index is None:        # "cuda" is the current device, as it is for tensor.to("cuda")
         want = torch.device("cuda", torch.cuda.current_device())
     if table.device != want:
-        raise ValueError(f"fused_head='in_place': the processed features live on {table.device}, not on {want}")
+        raise ValueError(f"fused_head={mode!r}: the processed features live on {table.device}, not on {want}")
     return table, idx
 
 
@@ -264,13 +312,14 @@ def _head_outputs(model, idx, device, mode, **outs):
     fc = _fused_head(model, mode=mode)
     x, rows = _head_input(model, idx, device, mode)
     head = (fc.weight.detach(), None if fc.bias is None else fc.bias.detach(), None, 1.0)
-    return dev.linear_class_loss_rows(x, rows, *head, **outs) if mode == "in_place" else dev.linear_class_loss(x, *head, **outs)
+    return dev.linear_class_loss_rows(x, rows, *head, **outs) if _reads_in_place(mode) else dev.linear_class_loss(x, *head, **outs)
 
 
 def _fused_loss_and_pred(model, loss_fn, idx, y, device, mode=True):
     fc = _fused_head(model, loss_fn, mode)
     x, rows = _head_input(model, idx, device, mode)
-    ce, pred = linear_cross_entropy(x, fc.weight, fc.bias, y, check=False, return_pred=True, rows=rows)
+    ce, pred = linear_cross_entropy(x, fc.weight, fc.bias, y, check=False, return_pred=True, rows=rows,
+                                    one_pass=mode in ("one_pass", "one_pass_in_place"))
     return (ce if loss_fn == "cross_entropy" else torch.log(LOGE_EPSILON + ce) - math.log(LOGE_EPSILON)), pred
 
 
@@ -339,7 +388,10 @@ def train(model, train_idx, labels, device, optimizer, loss_fn="cross_entropy", 
     forms the logits -- the rows go to linear_cross_entropy, whose backward gives the head's two gradients.
     fused_head="in_place" (the same rule, and the processed features must be a float32 or bfloat16 matrix on the device): the same
     step with the same bits, but the head reads rows train_idx of the stored matrix itself (linear_cross_entropy's `rows`): nothing
-    is gathered or widened first, which is what bf16 hop storage otherwise pays before every step."""
+    is gathered or widened first, which is what bf16 hop storage otherwise pays before every step.
+    fused_head="one_pass" / "one_pass_in_place": the step of True / "in_place" in ONE pass over the rows (linear_cross_entropy's
+    one_pass): the forward launch leaves the head's two gradients, the backward launches nothing.  Evaluation and prediction under
+    either value are those of True / "in_place"."""
     _check_loss_fn(loss_fn)
     if fused_head:
         _fused_head(model, loss_fn, fused_head)

@@ -19,7 +19,15 @@ of N = 2 449 029 rows, float32 and bfloat16, m = 196 615 random rows through a d
 only: a float32 table without an index is K21's own matrix, and the parent path reads it as a view).  Legs: (a) forward + loss + dZ,
 (b) a whole step -- the gather is part of the parent's step --, (c) evaluation, (d) one read of the gathered bytes m d e, (e) the
 weight gradient on its own: in place against K21's on a copy gathered beforehand (the parent pays for that copy in its forward).
---rows: the largest entry is the table, every entry a batch size m."""
+--rows: the largest entry is the table, every entry a batch size m.
+
+    python tools/bench_head.py --one-pass [--out profiles/linear_head_step.json]
+
+The one-pass step (DESIGN K23) against ITS parent paths, same process, same method, (d, C) = (100, 47) and (200, 3), a table of
+N = 2 449 029 rows in float32 and bfloat16, m = 196 615 random rows and m = N.  Leg (f), a whole step = linear_cross_entropy + backward
+(autograd and the float64 loss sum included, no optimizer): (f1) one_pass=True on the batch matrix against the K21 step on it -- the
+gather is part of both steps, and a float32 table with m = N is the matrix itself --; (f2) one_pass=True with rows= against the K22
+in-place step.  Before timing, loss and pred of 64 sampled rows and dW, db are checked against float64."""
 import argparse
 import json
 import os
@@ -167,6 +175,67 @@ def one_table(n_rows, m, d, c, dtype, args):
     return out
 
 
+ONE_PASS_SHAPES = ((100, 47), (200, 3))
+
+
+def one_pass_table(n_rows, m, d, c, dtype, args):
+    """leg (f): the one-pass step against the K21 step on the batch matrix and against the K22 in-place step on the stored rows"""
+    dev_ = torch.device("cuda", 0)
+    gen = torch.Generator(device=dev_).manual_seed(args.seed)
+    table = dev.alloc_rows(n_rows, d, dev_, dtype=dtype)
+    table.copy_(torch.randn((n_rows, d), generator=gen, device=dev_))
+    idx = None if m == n_rows else torch.randint(0, n_rows, (m,), generator=gen, device=dev_)
+    at = torch.arange(n_rows, device=dev_) if idx is None else idx
+    dense = idx is None and dtype == torch.float32                     # the table is the batch matrix: nothing is gathered
+    lin = torch.nn.Linear(d, c).to(dev_)
+    w, b = lin.weight, lin.bias
+    wd, bd = w.detach(), b.detach()
+    y = torch.randint(0, c, (m,), generator=gen, device=dev_)
+    g = table if dense else dev.gather_rows(table, at)
+    dw, db, loss, pred = dev.linear_step_rows(table, idx, wd, bd, y, 1.0, row_loss=True, pred=True)
+    dz = dev.linear_class_loss(g, wd, bd, y, 1.0, dz=True)[0]
+    check_sample(g, wd, bd, y, dz, loss, pred)
+    want = dz.double().t() @ torch.cat((g.double(), torch.ones((m, 1), dtype=torch.float64, device=dev_)), 1)
+    have = torch.cat((dw, db[:, None]), 1).double()
+    assert float((have - want).abs().max()) <= 1e-4 * float(want.abs().max()), "dW / db of the one-pass step are off float64"
+    del g, dz, want
+    tag = f"n_rows={n_rows} m={m} d={d} C={c} {str(dtype).replace('torch.', '')}"
+    out = {"n_rows": n_rows, "m": m, "index": "none" if idx is None else "random", "d": d, "c": c, "dtype": str(dtype).replace("torch.", "")}
+    rows = range(n_rows) if idx is None else idx
+
+    def step(one_pass, in_place):
+        lin.zero_grad(set_to_none=True)
+        if in_place:
+            loss_ = cl.linear_cross_entropy(table, w, b, y, check=False, rows=rows, one_pass=one_pass)
+        else:
+            loss_ = cl.linear_cross_entropy(table if dense else dev.gather_rows(table, at), w, b, y, check=False, one_pass=one_pass)
+        loss_.backward()
+        return loss_
+
+    out["f1_step_on_the_batch_matrix"] = compare(lambda: step(True, False), lambda: step(False, False), args, f"(f1) {tag}", ("one_pass", "k21"))
+    out["f2_step_on_stored_rows"] = compare(lambda: step(True, True), lambda: step(False, True), args, f"(f2) {tag}", ("one_pass", "k22"))
+    out["d_one_read_of_the_rows_ms"] = m * d * table.element_size() / COPY_CEILING_BYTES_PER_S * 1e3
+    return out
+
+
+def main_one_pass(args):
+    sizes = sorted({int(n) for n in args.rows.split(",")})
+    n_rows = sizes[-1]
+    results = [one_pass_table(n_rows, m, d, c, dtype, args) for dtype in (torch.float32, torch.bfloat16) for m in sizes for d, c in ONE_PASS_SHAPES]
+    doc = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "copy_ceiling_bytes_per_s": COPY_CEILING_BYTES_PER_S,
+           "protocol": "legs interleaved in one process, HIP events, median (min - max); loss and pred of 64 sampled rows and dW, db checked "
+                       "against float64 first; a step is linear_cross_entropy + backward, the gather is part of both candidates of (f1)",
+           "expectation": "m d e bytes of features against 2 m d 4 + 2 m C 4 (plus the gather): a lower time than the K21 step and than the "
+                          "K22 in-place step",
+           "not_measured": ["hardware counters (LDS bank conflicts, FETCH bytes)", "a sweep of loss_blocks", "mini-batches below 196 615 rows",
+                            "the step inside node_classification end to end"],
+           "results": results}
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "linear_head_step.json")
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", out)
+
+
 def main_in_place(args):
     sizes = sorted({int(n) for n in args.rows.split(",")})
     n_rows = sizes[-1]
@@ -191,6 +260,7 @@ def main_in_place(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--in-place", action="store_true", help="measure the head on stored rows (K22) against gather_rows + K21")
+    ap.add_argument("--one-pass", action="store_true", help="measure the one-pass step (K23) against the K21 step and the K22 in-place step")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
@@ -201,6 +271,8 @@ def main():
     torch.cuda.set_device(0)
     if args.in_place:
         return main_in_place(args)
+    if args.one_pass:
+        return main_one_pass(args)
     results = [one_shape(int(n), d, c, args) for n in args.rows.split(",") for d, c in SHAPES]
     doc = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "copy_ceiling_bytes_per_s": COPY_CEILING_BYTES_PER_S,
            "protocol": "legs interleaved in one process, HIP events, median (min - max); fused outputs of 64 sampled rows checked against float64 first",
