@@ -30,7 +30,12 @@ def main():
     ap.add_argument("--prop-steps", type=int, default=5)
     ap.add_argument("--classes", type=int, default=47)
     ap.add_argument("--batch", type=int, default=50_000)
+    ap.add_argument("--in-place", action="store_true",
+                    help="the aggregator reads the batch rows of the stored hop matrices in place (config.aggregate_in_place, K24)")
     a = ap.parse_args()
+    if a.in_place:
+        from sgl_amd import config
+        config.aggregate_in_place = True
     device = torch.device("cuda")
     wl = synthetic.WORKLOADS[a.workload]
     n, d, C = wl["n"], 100, a.classes

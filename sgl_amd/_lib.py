@@ -242,6 +242,27 @@ LINEAR_STEP_PROTOTYPES = {
     "sgl_linear_step_rows_bf16": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, *_STEP_TAIL]),
 }
 
+# include/sgl_hop_rows.h: K24, the learnable hop aggregators on rows idx[i] of stored float32 / bfloat16 hop tables -- a header and a
+# table of their own.  Every entry starts with the row source: n_hops, tables, pitches, n_rows, idx, m
+SGL_HOP_ROWS_MAX_HOPS = 16
+SGL_HOP_ROWS_MAX_D = 512
+_ROW_SOURCE = [c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64]
+_ROWS_SCORES = (c_int, [*_ROW_SOURCE, c_void_p, c_int64, c_uint64, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p])
+_ROWS_WSUM = (c_int, [*_ROW_SOURCE, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p])
+_ROWS_WSUM_BWD = (c_int, [*_ROW_SOURCE, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p])
+_ROWS_COLSUM = (c_int, [*_ROW_SOURCE, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p])
+HOP_ROWS_PROTOTYPES = {
+    "sgl_hop_rows_scores_f32": _ROWS_SCORES,
+    "sgl_hop_rows_scores_bf16": _ROWS_SCORES,
+    "sgl_hop_rows_wsum_f32": _ROWS_WSUM,
+    "sgl_hop_rows_wsum_bf16": _ROWS_WSUM,
+    "sgl_hop_rows_wsum_bwd_f32": _ROWS_WSUM_BWD,
+    "sgl_hop_rows_wsum_bwd_bf16": _ROWS_WSUM_BWD,
+    "sgl_hop_rows_colsum_scratch": (c_int64, [c_int, c_int64, c_int64]),
+    "sgl_hop_rows_colsum_f32": _ROWS_COLSUM,
+    "sgl_hop_rows_colsum_bf16": _ROWS_COLSUM,
+}
+
 
 # libsgl_probe.so (include/sgl_probe.h): measurement and test support -- memory probes, placed allocations, synthetic workloads
 PROBE_LIB_PATH = os.environ.get("SGL_PROBE_LIB") or os.path.join(_HERE, "csrc", "libsgl_probe.so")
@@ -273,7 +294,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (*PROTOTYPES.items(), *ENSEMBLE_PROTOTYPES.items(), *SPGEMM_PROTOTYPES.items(),
                                   *KMEANS_MATRIX_PROTOTYPES.items(), *CLUSTER_SUMS_PROTOTYPES.items(), *KMEANS_SEED_PROTOTYPES.items(),
-                                  *LINEAR_HEAD_PROTOTYPES.items(), *LINEAR_ROWS_PROTOTYPES.items(), *LINEAR_STEP_PROTOTYPES.items()):
+                                  *LINEAR_HEAD_PROTOTYPES.items(), *LINEAR_ROWS_PROTOTYPES.items(), *LINEAR_STEP_PROTOTYPES.items(),
+                                  *HOP_ROWS_PROTOTYPES.items()):
             fn = getattr(handle, name)  # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

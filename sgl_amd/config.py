@@ -63,6 +63,14 @@ hop_dtype     "float32" (default) -> hop matrices are stored as float32: the 1e-
               device-resident hops only: with host_output or slab_hops it raises; delta_propagate, share_hops and the on-disk hop
               cache are bypassed (they hold float32 entries only).  Read by GraphOp (LaplacianGraphOp / PprGraphOp) only: the
               multi-GPU ShardedGraphOp has no bfloat16 form, takes no hop_dtype argument (a TypeError) and always stores float32
+aggregate_in_place  False (default) -> BaseSGAPModel.forward gathers the mini-batch rows of every hop matrix into float32 copies
+              (device.gather_hops) and the learnable aggregator reads the copies.  True (SGL_AMD_AGGREGATE_IN_PLACE=1) -> OPT-IN: a
+              LearnableWeightedMessageOp pre-aggregator (simple, simple_allow_neg, gate, ori_ref, jk: GAMLP) reads row idx[i] of the
+              stored float32 or bfloat16 hop matrices in its kernels (MessageOp.aggregate_rows, include/sgl_hop_rows.h, DESIGN.md
+              K24): no B x H x d copy per step.  'jk', 'ori_ref' and 'gate' give the gathered route's bits ('gate' takes the two-pass route
+              there -- scores, then the sum -- with the one-pass kernel's arithmetic).  Every other aggregator, hop matrices that
+              do not live on the step's device (host_output) and matrices the row kernels cannot read (more than 16 hops, d > 512,
+              unaligned rows) take the gathered route as before
 hop_cache_dir None -> every propagate() computes; a directory -> the hop matrices of propagate() are kept on disk under a key of
               the CONTENT of adjacency + features + operator parameters and loaded on a hit (sgl_amd/hopcache.py; the reference
               recomputes them in every run of every task)
@@ -97,3 +105,4 @@ reorder = os.environ.get("SGL_AMD_REORDER") or None
 hop_cache_dir = os.environ.get("SGL_AMD_HOP_CACHE") or None
 hop_dtype = (os.environ.get("SGL_AMD_HOP_DTYPE") or "float32").strip().lower()
 trace = _env_bool("SGL_AMD_TRACE", False)
+aggregate_in_place = _env_bool("SGL_AMD_AGGREGATE_IN_PLACE", False)

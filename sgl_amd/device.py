@@ -20,6 +20,7 @@ __all__ = [
     "placed_empty", "MEM_MODES",
     "hop_reduce", "hop_concat", "hop_reduce_grad", "hop_concat_grad", "hop_lincomb", "hop_wsum1d", "hop_wsum2d", "hop_scores", "hop_scores2", "hop_gate", "gate_fusable", "nafs_aggregate", "nafs_prefix",
     "gather_rows", "edge_dot", "ensemble_combine", "csr_matmul",
+    "hop_rows_fusable", "hop_scores2_rows", "hop_wsum2d_rows", "hop_colsum_rows",
 ]
 
 
@@ -53,7 +54,7 @@ _NO_STREAM = frozenset({"sgl_csr_set_values", "sgl_csr_info", "sgl_csr_destroy",
                         "sgl_hop_colsum_scratch", "sgl_hop_wsum1d_bwd_scratch", "sgl_ensemble_combine_bwd_scratch", "sgl_csr_matmul_rule",
                         "sgl_cluster_sums_rule", "sgl_cluster_sums_scratch", "sgl_kmeans_seed_rule", "sgl_kmeans_seed_scratch",
                         "sgl_linear_class_rule", "sgl_linear_wgrad_rule", "sgl_linear_wgrad_scratch",
-                        "sgl_linear_step_rule", "sgl_linear_step_scratch"})
+                        "sgl_linear_step_rule", "sgl_linear_step_scratch", "sgl_hop_rows_colsum_scratch"})
 
 
 def _call(device, name, *args, raw=False):
@@ -2509,6 +2510,165 @@ def gather_rows(x, idx, out=None):
         if out.shape != (idx.numel(), x.shape[1]):
             raise ValueError("gather_rows: `out` must be [len(idx), d]")
     return _gather([x], idx, None if out is None else [out])[0]
+
+
+# ---- K24: the learnable hop aggregators on stored hop rows (include/sgl_hop_rows.h) -----------------------------------------------
+def _hop_rows_refusal(feats):
+    """why the row kernels cannot read these hop tables in place, or None: up to 16 float32 or bfloat16 CUDA matrices of one dtype,
+    shape and device without a gradient, 0 < d <= 512, rows 16-byte (bfloat16: 8-byte) aligned on pitches that are multiples of 4
+    elements, the storage holding the vector that straddles column d of the last row too"""
+    if len(feats) < 1 or len(feats) > _lib.SGL_HOP_ROWS_MAX_HOPS:
+        return f"between 1 and {_lib.SGL_HOP_ROWS_MAX_HOPS} hop tables are supported"
+    f0 = feats[0]
+    if not all(torch.is_tensor(f) and f.is_cuda and f.dim() == 2 and f.dtype in (torch.float32, torch.bfloat16) for f in feats):
+        return "the hop tables must be 2-D float32 or bfloat16 CUDA tensors"
+    if any(f.dtype != f0.dtype or f.shape != f0.shape or f.device != f0.device for f in feats):
+        return "the hop tables must have one dtype, one shape and one device"
+    if any(f.requires_grad for f in feats):
+        return "a hop table that requires grad cannot be read in place (there is no dX)"
+    n, d = f0.shape
+    if n < 1 or not 0 < d <= _lib.SGL_HOP_ROWS_MAX_D:
+        return f"the tables need at least one row of 1 to {_lib.SGL_HOP_ROWS_MAX_D} columns"
+    dp = round_up(d, 4)
+    for f in feats:
+        have = f.untyped_storage().nbytes() // f.element_size() - f.storage_offset()
+        if ((d > 1 and f.stride(1) != 1) or f.data_ptr() % (4 * f.element_size()) or (n > 1 and (f.stride(0) % 4 or f.stride(0) < dp))
+                or have < (n - 1) * f.stride(0) * (n > 1) + dp):
+            return "the rows must be 16-byte (bfloat16: 8-byte) aligned on a pitch that is a multiple of 4 elements and covers round_up(d, 4)"
+    return None
+
+
+def hop_rows_fusable(feats):
+    """can hop_scores2_rows / hop_wsum2d_rows / hop_colsum_rows read these hop tables in place?  What GraphOp.propagate returns
+    (float32 or bfloat16 hop storage) can, up to 16 hops of at most 512 columns."""
+    return _hop_rows_refusal(list(feats)) is None
+
+
+def _row_source(who, feats, idx):
+    """(kind, the row-source arguments of an sgl_hop_rows_* call, idx, m, d, device); idx: None, or what _table_index made of it"""
+    feats = list(feats)
+    why = _hop_rows_refusal(feats)
+    if why is not None:
+        raise ValueError(f"{who}: {why}")
+    f0 = feats[0]
+    idx = _table_index(idx, f0)
+    m = f0.shape[0] if idx is None else int(idx.numel())
+    ptrs, lds = _lib.hop_arrays(feats)
+    if f0.shape[0] == 1:
+        lds = (c_int64 * len(feats))(*[round_up(f0.shape[1], 4)] * len(feats))
+    kind = "bf16" if f0.dtype == torch.bfloat16 else "f32"
+    return kind, (len(feats), ptrs, lds, f0.shape[0], _opt_ptr(idx), m), idx, m, f0.shape[1], f0.device
+
+
+def _batch_weights(who, w, m, H, device, vector_ok=False):
+    w = w.detach().to(device=device, dtype=torch.float32).contiguous()
+    if not (tuple(w.shape) == (m, H) or (vector_ok and tuple(w.shape) == (H,))):
+        raise ValueError(f"{who}: the weights must be [len(idx), H]{' or [H]' if vector_ok else ''}, got {tuple(w.shape)}")
+    return w
+
+
+def hop_colsum_rows(feats, idx, w, shared=False):
+    """hop_colsum on the rows idx of stored hop tables, without gathering them (sgl_hop_rows_colsum_f32 / _bf16): the [H, d] matrix of
+    sum_i w[i, h] * X_h[idx[i], :] (shared=True: w is [len(idx)], one weight per row for every hop).  Two runs give the same bits."""
+    who = "hop_colsum_rows"
+    kind, source, idx, m, d, device = _row_source(who, feats, idx)
+    H = source[0]
+    w = w.detach().to(device=device, dtype=torch.float32).contiguous()
+    if tuple(w.shape) != ((m,) if shared else (m, H)):
+        raise ValueError(f"{who}: the weights must be {'[len(idx)]' if shared else '[len(idx), H]'}, got {tuple(w.shape)}")
+    if m == 0:
+        return torch.zeros((H, d), dtype=torch.float32, device=device)
+    out = torch.empty((H, d), dtype=torch.float32, device=device)
+    scratch = torch.empty(int(_call(None, "sgl_hop_rows_colsum_scratch", H, m, d, raw=True)), dtype=torch.float32, device=device)
+    _call(device, f"sgl_hop_rows_colsum_{kind}", *source, ptr(w), 1 if shared else H, 0 if shared else 1, ptr(out), d, ptr(scratch), d)
+    return out
+
+
+class _HopScores2Rows(torch.autograd.Function):
+    """_HopScores2 on the row source: the forward is sgl_hop_rows_scores_*, the gradients of v and U are column sums over the same
+    rows (hop_colsum_rows).  The tables carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, v, u, mask, h0, h1, idx, *feats):
+        who = "hop_scores2_rows"
+        kind, source, idx, m, d, device = _row_source(who, feats, idx)
+        L = source[0]
+        if not (0 <= h0 <= h1 <= L) or mask >> L:
+            raise ValueError(f"{who}: the hop range and the mask must lie inside the {L} tables")
+        vp = _padded_vec(v, d, device)
+        ldu = round_up(d, 4)
+        up = None
+        if mask:
+            up = torch.zeros((L, ldu), dtype=torch.float32, device=device)
+            up[:, :d] = u.detach().to(torch.float32).view(L, d)
+        p = torch.empty((m, h1 - h0), dtype=torch.float32, device=device)
+        a = torch.zeros(m, dtype=torch.float32, device=device) if not mask else torch.empty(m, dtype=torch.float32, device=device)
+        _call(device, f"sgl_hop_rows_scores_{kind}", *source, _opt_ptr(up), ldu, ctypes.c_uint64(mask), ptr(vp), h0, h1, ptr(p),
+              max(h1 - h0, 1), ptr(a), d)
+        ctx.feats, ctx.idx, ctx.meta = [f.detach() for f in feats], idx, (mask, h0, h1, L, d)
+        ctx.save_for_backward(v.detach(), u.detach() if u is not None else None)
+        return p, a
+
+    @staticmethod
+    def backward(ctx, gp, ga):
+        v, u = ctx.saved_tensors
+        mask, h0, h1, L, d = ctx.meta
+        dv = du = None
+        if ctx.needs_input_grad[0]:
+            dv = (hop_colsum_rows(ctx.feats[h0:h1], ctx.idx, gp).sum(0) if h1 > h0 else torch.zeros(d, dtype=torch.float32, device=gp.device)).view_as(v)
+        if u is not None and ctx.needs_input_grad[1]:
+            du = torch.zeros((L, d), dtype=torch.float32, device=gp.device)
+            ref = [j for j in range(L) if (mask >> j) & 1]
+            if ref:
+                part = hop_colsum_rows([ctx.feats[j] for j in ref], ctx.idx, ga, shared=True)
+                for k_, j in enumerate(ref):
+                    du[j] = part[k_]
+            du = du.view_as(u)
+        return (dv, du, None, None, None, None, *([None] * L))
+
+
+def hop_scores2_rows(feats, idx, v, u, mask, h0, h1):
+    """hop_scores2 on the rows idx of stored hop tables, without gathering them (sgl_hop_rows_scores_f32 / _bf16): (P [len(idx), h1 -
+    h0], A [len(idx)]) with P[i, h - h0] = <X_h[idx[i]], v> and A[i] = sum over the hops j of `mask` of <X_j[idx[i]], U[j]>; mask = 0
+    (u may be None): the plain gate scores, A is zeros.  feats: float32 or bfloat16 tables (hop_rows_fusable); idx: whatever
+    gather_rows takes, or None for every row in order.  Bit for bit hop_scores2 over gather_hops(feats, idx).  A device index out of
+    range cannot be reported without a host read: that row's scores are NaN.  Differentiable in v and u."""
+    return _HopScores2Rows.apply(v, u, int(mask), int(h0), int(h1), idx, *feats)
+
+
+class _WSum2DRows(torch.autograd.Function):
+    """out[i, :] = sum_h W[i, h] X_h[idx[i], :] (sgl_hop_rows_wsum_*); backward: dW[i, h] = <dOut[i], X_h[idx[i]]> (sgl_hop_rows_wsum_bwd_*),
+    summed over the rows for a weight vector"""
+
+    @staticmethod
+    def forward(ctx, w, idx, *feats):
+        who = "hop_wsum2d_rows"
+        kind, source, idx, m, d, device = _row_source(who, feats, idx)
+        wd = _batch_weights(who, w, m, source[0], device, vector_ok=True)
+        out, pad = _alloc_out(m, d, device)
+        if m > 0:
+            _call(device, f"sgl_hop_rows_wsum_{kind}", *source, ptr(wd), 0 if wd.dim() == 1 else source[0], ptr(out), _ld(out), pad, d)
+        ctx.call = (kind, source, m, d, device, wd.dim() == 1, tuple(w.shape))
+        ctx.keep = (idx, [f.detach() for f in feats])          # the pointers in `source` stay valid as long as these live
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        kind, source, m, d, device, vector, shape = ctx.call
+        if not ctx.needs_input_grad[0]:
+            return (None,) * (2 + source[0])
+        g = _grad_rows(gout, m, d)
+        dw = torch.zeros((m, source[0]), dtype=torch.float32, device=device)
+        if m > 0:
+            _call(device, f"sgl_hop_rows_wsum_bwd_{kind}", *source, ptr(g), _ld(g), ptr(dw), source[0], d)
+        return (dw.sum(0).view(shape) if vector else dw, None, *([None] * source[0]))
+
+
+def hop_wsum2d_rows(feats, idx, w):
+    """hop_wsum2d on the rows idx of stored hop tables, without gathering them (sgl_hop_rows_wsum_f32 / _bf16): out[i] = sum_h w[i, h]
+    X_h[idx[i]] as a new padded float32 [len(idx), d] matrix; w: [len(idx), H], or [H] -- one weight vector for every row.  feats, idx:
+    as in hop_scores2_rows.  Bit for bit hop_wsum2d over gather_hops(feats, idx), forward and dW.  Differentiable in w only."""
+    return _WSum2DRows.apply(w, idx, *feats)
 
 
 # ---- K16: the sub-graph ensemble aggregators of the heterogeneous models (include/sgl_ensemble.h) -----------------------------------

@@ -47,6 +47,14 @@ def take_hop_rows(feats, idx, device):
     return [t.to(device) for t in dev.gather_hops(feats, idx)]
 
 
+def _resident_on(feats, device):
+    """is every hop matrix a tensor on `device` ("cuda" = the current device)?"""
+    target = torch.device(device)
+    if target.type == "cuda" and target.index is None:
+        target = torch.device("cuda", torch.cuda.current_device())
+    return isinstance(feats, list) and len(feats) > 0 and all(torch.is_tensor(f) and f.device == target for f in feats)
+
+
 class BaseSGAPModel(nn.Module):
     def __init__(self, prop_steps, feat_dim, output_dim):
         super(BaseSGAPModel, self).__init__()
@@ -197,8 +205,17 @@ class BaseSGAPModel(nn.Module):
 
     def forward(self, idx, device):
         if self._pre_msg_learnable:
-            hop_rows = take_hop_rows(self._processed_feat_list, idx, device)
-            processed_feature = self._pre_msg_op.aggregate(hop_rows)
+            processed_feature = None
+            if config.aggregate_in_place and _resident_on(self._processed_feat_list, device):
+                # K24: the learnable aggregator reads the batch rows where the hop matrices are stored (None: it cannot, gather).
+                # Only for hop matrices that live on the step's device: host-resident hops, or hops on another device than the
+                # model, are gathered and moved as before
+                processed_feature = self._pre_msg_op.aggregate_rows(self._processed_feat_list, idx)
+                if processed_feature is not None:
+                    processed_feature = processed_feature.to(device)
+            if processed_feature is None:
+                hop_rows = take_hop_rows(self._processed_feat_list, idx, device)
+                processed_feature = self._pre_msg_op.aggregate(hop_rows)
         else:
             feat = self._processed_feature
             if isinstance(feat, np.ndarray):  # no pre-graph-op: the raw feature matrix

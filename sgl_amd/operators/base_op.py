@@ -613,3 +613,11 @@ class MessageOp(nn.Module):
                 feat_list = dev.widen_hops(feat_list)
 
         return self._combine(feat_list)
+
+    def aggregate_rows(self, feat_list, idx):
+        """aggregate() over the rows idx of stored hop matrices: here the rows are gathered first (device.gather_hops for
+        device-resident hops, a float32 copy of len(idx) rows per hop), then aggregated.  An operator whose kernels read the stored
+        rows in place overrides this (LearnableWeightedMessageOp) and returns None where they do not apply: the caller then gathers.
+        The rows stay on the hop matrices' device; BaseSGAPModel.forward asks only for hops that live on the step's device."""
+        from ..models.base_model import take_hop_rows
+        return self.aggregate(take_hop_rows(feat_list, idx, feat_list[0].device))

@@ -135,3 +135,49 @@ class LearnableWeightedMessageOp(MessageOp):
         if self.__combination_type in _VECTOR_KINDS:
             return one_dim_weighted_add(hops, weight_list=weight_list)
         return two_dim_weighted_add(hops, weight_list=weight_list)
+
+    def aggregate_rows(self, feat_list, idx):
+        """aggregate([x[idx] for x in feat_list]) WITHOUT gathering the rows (config.aggregate_in_place): the scores,
+        the weighted sum, its backward and the parameter gradients read row idx[i] of the stored float32 or bfloat16 hop matrices
+        (device.hop_scores2_rows / hop_wsum2d_rows / hop_colsum_rows).  The scores' scramble over the len(idx) batch rows and the
+        [len(idx), H] sigmoid / soft-max stay in torch, as in hop_weights; 'gate' takes the two-pass route (scores, then the sum) with the
+        one-pass kernel's arithmetic.  None when the row kernels cannot read these matrices (device.hop_rows_fusable): the caller gathers."""
+        from ... import device as dev
+        kind = self.__combination_type
+        s, e = self._start, self._end
+        L = len(feat_list) if isinstance(feat_list, list) else 0
+        if not (L and isinstance(s, int) and isinstance(e, int) and 0 <= s < e <= L and dev.hop_rows_fusable(feat_list)):
+            return None
+        H = e - s
+        idx = dev._table_index(idx, feat_list[0])                       # validated and uploaded once for the whole chain
+        hops = feat_list[s:e]
+        if kind in _VECTOR_KINDS:
+            return dev.hop_wsum2d_rows(hops, idx, self.hop_weights(feat_list))
+        lin = self.__learnable_weight
+        w = lin.weight.view(-1)
+        d = hops[0].shape[1]
+        if kind == "gate":
+            if w.numel() != d:
+                return None
+            # Gathered, these rows go through the one-pass gate kernel (device.hop_gate); the [m, H] sigmoid / soft-max here is
+            # written operation by operation as that kernel evaluates it -- 1 / (1 + exp(-(s + b))), the row maximum, exp, the sum
+            # in hop order, one division -- so that the two routes give the same bits, not F.softmax's rounding
+            per_hop, _ = dev.hop_scores2_rows(hops, idx, w, None, 0, 0, H)
+            gate = 1.0 / (1.0 + torch.exp(-(per_hop + lin.bias.view(1, 1))))
+            ex = torch.exp(gate - gate.max(dim=1, keepdim=True).values)
+            total = ex[:, 0]
+            for h in range(1, H):
+                total = total + ex[:, h]
+            return dev.hop_wsum2d_rows(hops, idx, ex / total.unsqueeze(1))
+        d_ref = d if kind == "ori_ref" else L * d
+        if w.numel() != d_ref + d:
+            return None
+        if kind == "ori_ref":
+            u = torch.cat([w[:d].view(1, d), torch.zeros((L - 1, d), dtype=w.dtype, device=w.device)]) if L > 1 else w[:d].view(1, d)
+            mask = 1
+        else:
+            u, mask = w[:d_ref].view(L, d), (1 << L) - 1
+        per_hop, shared = dev.hop_scores2_rows(feat_list, idx, w[d_ref:], u, mask, s, e)
+        flat = (per_hop + (shared + lin.bias).view(-1, 1)).t().reshape(-1)
+        weights = F.softmax(torch.sigmoid(flat.view(-1, H)), dim=1)        # reference's scrambled pairing
+        return dev.hop_wsum2d_rows(hops, idx, weights)
